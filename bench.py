@@ -92,6 +92,12 @@ def parse():
     ap.add_argument("--scene", default=None, help="a scene PLY in the reference's layout (street_gaussian_model.py:94-117, "
                     "read with street_gaussians_amd.plyio) to render instead of the synthetic Gaussians")
     ap.add_argument("--cpu-sample-gaussians", type=int, default=0, help="override the CPU sample size")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its LAST step computed (the rasterizer's images, radii and the "
+                         "gradients of every input) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: a fixed, "
+                         "seeded sample of pixels and of Gaussians when the full arrays are larger (the sampled rows are in "
+                         "DIR/pixel_index.npy and DIR/gaussian_index.npy).  The inputs depend on the arguments only, so two "
+                         "builds run with the same arguments can be compared output for output")
     return ap.parse_args()
 
 
@@ -285,6 +291,7 @@ class Workload:
             projmatrix=cam.projmatrix.to(dev), sh_degree=3, campos=cam.campos.to(dev), prefiltered=False, debug=False)
         self.rast = GaussianRasterizer(self.st)
         self.radii = None
+        self.keep_images, self.images = False, None  # --dump-outputs: the images of the timed region's last step
         # exchange step (N > 1): the optimiser's gradients.  dL/dmeans2D is not one of them -- it feeds per-view
         # densification statistics (multiview.reduce_densification_stats) -- so it stays local.
         self.reducer = None
@@ -331,6 +338,40 @@ class Workload:
             else:
                 self.reducer.all_reduce()
         self.radii = radii
+        if self.keep_images:  # detached: the step's autograd graph must not outlive the step (--dump-outputs)
+            self.images = {k: (v.detach() if v is not None else None)
+                           for k, v in (("color", color), ("depth", depth), ("alpha", alpha), ("semantic", sem))}
+
+    def sample_outputs(self, budget=64 << 20, seed=1234):
+        """--dump-outputs: the last step's images, radii and input gradients as host arrays (float32; the sampled indices as
+        float64), gathered on the device.  Full arrays while they fit in `budget` bytes; otherwise a seeded sample of pixels
+        and of Gaussians that depends on H, W, P and S only, halved until it fits."""
+        p, H, W = self.params, self.args.height, self.args.width
+        pix = {k: v.detach().reshape(v.shape[0], -1) for k, v in self.images.items() if v is not None and v.numel()}
+        gau = {"radii": self.radii.reshape(self.P, 1), "grad_means2D": self.means2D.grad}
+        gau.update({"grad_" + k: v.grad for k, v in p.items()})
+        gau = {k: v.detach().reshape(self.P, -1) for k, v in gau.items() if v is not None}
+        pix_row = 4 * sum(v.shape[0] for v in pix.values())  # bytes per sampled pixel (channel-major images)
+        gau_row = 4 * sum(v.shape[1] for v in gau.values())  # bytes per sampled Gaussian
+        n_pix, n_gau = H * W, self.P
+        if n_pix * pix_row + n_gau * gau_row > budget:
+            n_pix, n_gau = min(n_pix, 1 << 17), min(n_gau, 1 << 16)
+            while n_pix * (pix_row + 8) + n_gau * (gau_row + 8) > budget:
+                n_pix, n_gau = max(1, n_pix // 2), max(1, n_gau // 2)
+        g = torch.Generator().manual_seed(seed)
+        pick = lambda n, m: (torch.arange(n) if m == n else torch.randperm(n, generator=g)[:m].sort().values)
+        ip, ig = pick(H * W, n_pix), pick(self.P, n_gau)
+        out = {}
+        if n_pix < H * W:
+            out["pixel_index"] = ip.double().numpy()
+        if n_gau < self.P:
+            out["gaussian_index"] = ig.double().numpy()
+        ipd, igd = ip.to(self.dev), ig.to(self.dev)
+        for k, v in pix.items():
+            out[k] = v.index_select(1, ipd).float().cpu().numpy()
+        for k, v in gau.items():
+            out[k] = v.index_select(0, igd).float().cpu().numpy()
+        return out
 
     def drain(self):
         """Joins an exchange that is still in flight (end of a timed region)."""
@@ -821,7 +862,12 @@ def main():
     # (at most every 8th step whatever --steps is: an event pair drains the queue ~10 us each side of the launch it
     # brackets, which taxed a 20-step region by ~1 % when every step carried one; at least 3 samples)
     every = max(1, min(8, (args.steps - 1) // 2))
+    wl.keep_images = bool(args.dump_outputs) and rank == 0
     dt, timed = profiled_steps(L, wl, fence, args.steps, 1 << 7, every=every)
+    # --dump-outputs: what the timed region's last step computed, taken before any further step runs (written at the end);
+    # from here on the workload holds no extra references, as without the flag
+    dumped = wl.sample_outputs() if wl.keep_images else None
+    wl.keep_images, wl.images = False, None
     if os.environ.get("SGR_BENCH_REGION_TRACE"):  # debug: the same region again, and once more after 50 ms of host sleep
         profiled_steps(L, wl, fence, args.steps, 1 << 7, every=every)
         time.sleep(0.05)
@@ -1211,6 +1257,15 @@ def main():
                 line["cpu_baseline"]["configs0_smoke_recipe"] = cpu_smoke_recipe()
             except Exception as ex:
                 line["cpu_baseline"]["configs0_smoke_recipe"] = {"error": str(ex)[:160]}
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for k, v in dumped.items():
+                np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+            line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": int(sum(v.nbytes for v in dumped.values())),
+                                    "arrays": {k: list(v.shape) for k, v in dumped.items()},
+                                    "what": "the timed region's last step: images [C, pixels], radii and input gradients "
+                                            "[Gaussians, ...]; *_index = the sampled pixel / Gaussian rows when sampled"}
         # LAST key: the figures a reader of the tail of this line needs, in one short object
         line["summary"] = {
             "value": value, "mode": args.mode, "conforming": args.mode == "strict", "ms_per_step": ms_per_step, "steps": args.steps,

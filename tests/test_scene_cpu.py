@@ -1,5 +1,5 @@
 """CPU tests for the scene-graph rows: the torch restatement (tests/torch_ref_scene.py) is pinned against the
-reference's own quaternion helpers when /root/reference is present, its analytic structure is checked with float64
+reference's own quaternion helpers (live where the reference checkout is present, else its recorded outputs), its analytic structure is checked with float64
 finite differences, and the C ABI of include/sgr_scene.h must be exported by the built library."""
 import ctypes as C
 import importlib.util
@@ -10,15 +10,16 @@ import pytest
 import torch
 
 import torch_ref_scene as ref
+from golden.refpin import Pin, reference_path
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-GU = "/root/reference/lib/utils/general_utils.py"
+GU = "lib/utils/general_utils.py"  # under the reference checkout (golden/refpin.py)
 
 
 def _reference_fn(name):
     """Extracts ONE pure function from the reference's general_utils.py (the module itself imports CUDA-only code)."""
-    src = open(GU).read()
+    src = open(reference_path(GU)).read()
     m = re.search(rf"^def {name}\(.*?(?=^def |\Z)", src, re.S | re.M)
     ns = {"torch": torch, "F": torch.nn.functional}
     helper = re.search(r"^def _sqrt_positive_part\(.*?(?=^def |\Z)", src, re.S | re.M)
@@ -28,17 +29,18 @@ def _reference_fn(name):
     return ns[name]
 
 
-@pytest.mark.skipif(not os.path.exists(GU), reason="reference checkout not present on this machine")
 def test_restated_quaternion_helpers_match_the_reference():
+    pin = Pin("scene_cpu.quaternion_helpers", GU)
     g = torch.Generator().manual_seed(0)
     a, b = torch.randn(50, 4, generator=g), torch.randn(50, 4, generator=g)
-    assert torch.equal(ref.quaternion_raw_multiply(a, b), _reference_fn("quaternion_raw_multiply")(a, b))
-    assert torch.equal(ref.quaternion_to_matrix(a), _reference_fn("quaternion_to_matrix")(a))
+    pin.equal("quaternion_raw_multiply", ref.quaternion_raw_multiply(a, b), lambda: _reference_fn("quaternion_raw_multiply")(a, b))
+    pin.equal("quaternion_to_matrix", ref.quaternion_to_matrix(a), lambda: _reference_fn("quaternion_to_matrix")(a))
     # the flip quaternion the reference derives (street_gaussian_model.py:58-61) is what Segment defaults to
     flip = torch.eye(3) * -1
     flip[1, 1] = 1
-    q = _reference_fn("matrix_to_quaternion")(flip.unsqueeze(0))[0]
+    q = pin.get("flip_quaternion", lambda: _reference_fn("matrix_to_quaternion")(flip.unsqueeze(0))[0])
     assert torch.allclose(q, torch.tensor([0.0, 0.0, 1.0, 0.0]))
+    pin.close()
 
 
 def _segments(dtype=torch.float64, S=3, M=4, seed=1):
@@ -97,13 +99,13 @@ def test_scene_abi_symbols_are_exported():
 
 # ---- pin of the flattening itself: the reference's OWN property getters, cut out of its source and executed on stub
 # objects (street_gaussian_model.py:287-449, gaussian_model.py:224-251, gaussian_model_actor.py:55-80) ----------------
-SGM = "/root/reference/lib/models/street_gaussian_model.py"
-GMP = "/root/reference/lib/models/gaussian_model.py"
-GMA = "/root/reference/lib/models/gaussian_model_actor.py"
+SGM = "lib/models/street_gaussian_model.py"
+GMP = "lib/models/gaussian_model.py"
+GMA = "lib/models/gaussian_model_actor.py"
 
 
 def _getters(path, names, ns, prop=True):
-    src = open(path).read()
+    src = open(reference_path(path)).read()
     out = {}
     for name in names:
         pat = rf"^    @property\n    def {name}\(self.*?(?=^    def |^    @|\Z)" if prop else rf"^    def {name}\(self.*?(?=^    def |^    @|\Z)"
@@ -116,10 +118,10 @@ def _getters(path, names, ns, prop=True):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(SGM), reason="reference checkout not present on this machine")
 @pytest.mark.parametrize("train,sem_mode", [(True, "logits"), (False, "probabilities")])
 def test_restated_flattening_matches_the_reference_getters(train, sem_mode):
     import types
+    pin = Pin(f"scene_cpu.flattening.train={train}", SGM, GMP, GMA, GU)
     S, M = 4, 16
     g = torch.Generator().manual_seed(11)
     r = lambda *s: torch.randn(*s, generator=g)
@@ -128,15 +130,18 @@ def test_restated_flattening_matches_the_reference_getters(train, sem_mode):
 
     def IDFT(time, dim):  # lib/utils/general_utils.py: only its result is used here; the row is an input of the test
         return idft_rows[dim][None]
-    ns = {"torch": torch, "cfg": cfg, "quaternion_raw_multiply": _reference_fn("quaternion_raw_multiply"),
-          "quaternion_to_matrix": _reference_fn("quaternion_to_matrix"), "IDFT": IDFT,
-          "GaussianModel": object, "GaussianModelActor": object}
+    if pin.live:
+        ns = {"torch": torch, "cfg": cfg, "quaternion_raw_multiply": _reference_fn("quaternion_raw_multiply"),
+              "quaternion_to_matrix": _reference_fn("quaternion_to_matrix"), "IDFT": IDFT,
+              "GaussianModel": object, "GaussianModelActor": object}
 
-    Base = type("Base", (), _getters(GMP, ["get_scaling", "get_rotation", "get_xyz", "get_features", "get_semantic", "get_opacity"], ns))
-    actor_ns = dict(ns)
-    Actor = type("Actor", (Base,), {**_getters(GMA, ["get_semantic"], actor_ns),
-                                    **_getters(GMA, ["get_features_fourier"], actor_ns, prop=False)})
-    Street = type("Street", (), _getters(SGM, ["get_scaling", "get_rotation", "get_xyz", "get_features", "get_semantic", "get_opacity"], dict(ns)))
+        Base = type("Base", (), _getters(GMP, ["get_scaling", "get_rotation", "get_xyz", "get_features", "get_semantic", "get_opacity"], ns))
+        actor_ns = dict(ns)
+        Actor = type("Actor", (Base,), {**_getters(GMA, ["get_semantic"], actor_ns),
+                                        **_getters(GMA, ["get_features_fourier"], actor_ns, prop=False)})
+        Street = type("Street", (), _getters(SGM, ["get_scaling", "get_rotation", "get_xyz", "get_features", "get_semantic", "get_opacity"], dict(ns)))
+    else:  # the same inputs, drawn in the same order; the reference's outputs come from the record
+        Base = Actor = Street = type("Stub", (), {})
 
     def model(cls, n, C, sem_cols):
         m = cls()
@@ -179,9 +184,10 @@ def test_restated_flattening_matches_the_reference_getters(train, sem_mode):
         d.update(pose=p, idft=idft_rows[a.fourier_dim], class_label=a.obj_class_label, flip_mask=fm if train else None)
         segs.append(d)
     xyz, rot, scale, opac, feats, sem = ref.compose(segs, M, S)
-    assert torch.equal(xyz, st.get_xyz)
-    assert torch.equal(rot, st.get_rotation)
-    assert torch.equal(scale, st.get_scaling)
-    assert torch.equal(opac, st.get_opacity)
-    assert torch.equal(feats, st.get_features)
-    assert torch.equal(sem, st.get_semantic)
+    pin.equal("xyz", xyz, lambda: st.get_xyz)
+    pin.equal("rotation", rot, lambda: st.get_rotation)
+    pin.equal("scaling", scale, lambda: st.get_scaling)
+    pin.equal("opacity", opac, lambda: st.get_opacity)
+    pin.equal("features", feats, lambda: st.get_features)
+    pin.equal("semantic", sem, lambda: st.get_semantic)
+    pin.close()
