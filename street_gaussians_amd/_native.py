@@ -28,7 +28,8 @@ SYMBOLS = [
     "sgr_l1_workspace_floats", "sgr_l1_forward", "sgr_l1_backward", "sgr_color_loss_backward", "sgr_bce_forward", "sgr_bce_backward",
     "sgr_lidar_work_bytes", "sgr_lidar_depth_forward", "sgr_lidar_depth_backward", "sgr_densify_work_bytes", "sgr_densify_plan",
     "sgr_densify_map", "sgr_densify_gather", "sgr_densify_split_children", "sgr_densify_prune_mask",
-    "sgr_densify_compact", "sgr_reset_opacity",
+    "sgr_densify_compact", "sgr_reset_opacity", "sgr_texture_cube_workspace_bytes", "sgr_texture_cube_forward",
+    "sgr_texture_cube_backward",
 ]
 
 
@@ -130,6 +131,12 @@ def lib():
         L.sgr_densify_compact.argtypes = [i, vp, vp, vp, C.POINTER(C.c_int64), vp]
         L.sgr_reset_opacity.restype = i
         L.sgr_reset_opacity.argtypes = [i, vp, vp, vp, vp]
+        L.sgr_texture_cube_workspace_bytes.restype = C.c_size_t
+        L.sgr_texture_cube_workspace_bytes.argtypes = [i, i, i, i, C.c_int64]
+        L.sgr_texture_cube_forward.restype = i
+        L.sgr_texture_cube_forward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp]
+        L.sgr_texture_cube_backward.restype = i
+        L.sgr_texture_cube_backward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp, vp]
         L.sgr_knn.restype = i
         L.sgr_knn.argtypes = [i, vp, vp, ALLOC_FN, vp, vp]
         L.sgr_export_internal.restype = i

@@ -1,0 +1,454 @@
+// sgr_texture.hip -- bilinear cube-map lookup and its deterministic backward (include/sgr_texture.h) on gfx950.
+//
+// Forward: one lane per sample.  The face / (u, v) arithmetic is the contract of include/sgr_texture.h; a footprint that
+// stays inside its face reads four texels directly, one that leaves it goes through the seam table (derived once on the
+// host from the face orientation) and the corner rule.
+//
+// Backward, without float atomics and writing every gradient element once:
+//   1. key     every sample gets the id of the 2x2 texel cell of its footprint on an EXTENDED grid of (R + 1)^2 cells
+//              per face (cell (x0, y0), x0, y0 in [-1, R-1]): footprints that leave the face are cells of the border
+//              ring, so they need no list of their own.  Samples with no footprint get the sentinel key ncells.
+//   2. sort    stable LSD radix sort of (key, sample index) -- sgr_launch_sort_pairs32, iota values.
+//   3. starts  starts[c] = first sorted position with key >= c, for c in [0, ncells] (a binary search per cell: every
+//              entry written once; empty cells, e.g. the faces a camera does not see, cost no serial fill).
+//   4. records sorted position i -> (fx, fy) of its sample and its dL/dout, contiguous in cell order.
+//   5. gather  one lane per texel (per texel and channel for C != 3) walks the runs of the cells that have it as a tap:
+//              its four own cells and, on a face edge, the two border cells of each neighbouring face whose outside tap
+//              lands on it; a fixed order, so the sums are bit-reproducible.
+#include <string>
+
+#include "../../include/sgr_texture.h"
+#include "sgr_common.h"
+
+int sgr_set_error(int code, const std::string& msg);
+
+#define TX_HIP(call)                                                                                       \
+    do {                                                                                                   \
+        hipError_t e__ = (call);                                                                           \
+        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+
+// Edges of a face: 0 = column -1, 1 = column R, 2 = row -1, 3 = row R.  A tap at position k along edge e of face f is
+// texel (col, row) = (c0 (R-1) + c1 k, r0 (R-1) + r1 k) of face g; back = the edge of g that leads back to f.
+struct SgrCubeSeam {
+    int8_t g[6][4], c0[6][4], c1[6][4], r0[6][4], r1[6][4], back[6][4];
+};
+
+__device__ __forceinline__ float tx_su(int f) { return (f == 0 || f == 5) ? -1.f : 1.f; }  // SU = (-1, +1, +1, +1, +1, -1)
+__device__ __forceinline__ float tx_sv(int f) { return f == 2 ? 1.f : -1.f; }              // SV = (-1, -1, +1, -1, -1, -1)
+
+// Face and texel-space position (x, y) = (u R - 0.5, v R - 0.5) of direction d; false when (u, v) is not finite.
+__device__ __forceinline__ bool tx_coords(float dx, float dy, float dz, int R, int& face, float& x, float& y) {
+    const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
+    float c, s, t;
+    if (az > fmaxf(ax, ay)) { c = dz; s = dx; t = dy; face = 4 + (c < 0.f); }
+    else if (ay > ax) { c = dy; s = dx; t = dz; face = 2 + (c < 0.f); }
+    else { c = dx; s = dz; t = dy; face = 0 + (c < 0.f); }
+    const float m = 0.5f / fabsf(c);
+    float u = s * tx_su(face) * m + 0.5f, v = t * tx_sv(face) * m + 0.5f;
+    if (!isfinite(u) || !isfinite(v)) return false;
+    u = fminf(fmaxf(u, 0.f), 1.f);
+    v = fminf(fmaxf(v, 0.f), 1.f);
+    x = u * (float)R - 0.5f;
+    y = v * (float)R - 0.5f;
+    return true;
+}
+
+// Texel (within one batch's 6 R R texels) of footprint tap (col, row) of face f, or -1 when it lies outside two edges.
+__device__ __forceinline__ int64_t tx_tap(const SgrCubeSeam& sm, int R, int f, int col, int row) {
+    const bool ox = col < 0 || col >= R, oy = row < 0 || row >= R;
+    if (ox && oy) return -1;
+    if (ox || oy) {
+        const int e = ox ? (col < 0 ? 0 : 1) : (row < 0 ? 2 : 3);
+        const int k = ox ? row : col;
+        const int g = sm.g[f][e];
+        col = sm.c0[f][e] * (R - 1) + sm.c1[f][e] * k;
+        row = sm.r0[f][e] * (R - 1) + sm.r1[f][e] * k;
+        f = g;
+    }
+    return ((int64_t)f * R + row) * R + col;
+}
+
+// The four taps of cell (x0, y0) of face f in the order (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1); a missing corner
+// tap gets index -1.
+__device__ __forceinline__ int tx_cell_taps(const SgrCubeSeam& sm, int R, int f, int x0, int y0, int64_t idx[4]) {
+    int miss = -1;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        idx[k] = tx_tap(sm, R, f, x0 + (k & 1), y0 + (k >> 1));
+        if (idx[k] < 0) miss = k;
+    }
+    return miss;
+}
+
+__device__ __forceinline__ void tx_weights(float fx, float fy, float w[4]) {
+    w[0] = (1.f - fx) * (1.f - fy);
+    w[1] = fx * (1.f - fy);
+    w[2] = (1.f - fx) * fy;
+    w[3] = fx * fy;
+}
+
+// ---- forward --------------------------------------------------------------------------------------------------------
+// CT > 0: C = CT at compile time; CT = 0: C at run time.
+template <int CT>
+__global__ void __launch_bounds__(256)
+sgr_texture_cube_fwd_kernel(int Bt, int R, int Crt, int64_t n, int64_t total, const float* __restrict__ tex,
+                            const float* __restrict__ uv, float* __restrict__ out, SgrCubeSeam sm) {
+    const int C = CT > 0 ? CT : Crt;
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= total) return;
+    const int64_t b = s / n;
+    float* o = out + s * C;
+    int face;
+    float x, y;
+    if (!tx_coords(uv[3 * s], uv[3 * s + 1], uv[3 * s + 2], R, face, x, y)) {
+        for (int ch = 0; ch < C; ch++) o[ch] = 0.f;
+        return;
+    }
+    const float xf = floorf(x), yf = floorf(y);
+    const int x0 = (int)xf, y0 = (int)yf;
+    float w[4];
+    tx_weights(x - xf, y - yf, w);
+    const float* T = tex + (Bt == 1 ? 0 : b) * 6 * (int64_t)R * R * C;
+    int64_t idx[4];
+    if (x0 >= 0 && y0 >= 0 && x0 < R - 1 && y0 < R - 1) {
+        idx[0] = ((int64_t)face * R + y0) * R + x0;
+        idx[1] = idx[0] + 1;
+        idx[2] = idx[0] + R;
+        idx[3] = idx[2] + 1;
+    } else {
+        const int miss = tx_cell_taps(sm, R, face, x0, y0, idx);
+        if (miss >= 0) {  // the corner outside both edges: the mean of the other three texels
+            const float share = w[miss] * (1.f / 3.f);
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] += share;
+            w[miss] = 0.f;
+            idx[miss] = idx[miss ^ 3];  // any valid texel: its weight is 0
+        }
+    }
+    if constexpr (CT > 0) {
+        float acc[CT];
+#pragma unroll
+        for (int ch = 0; ch < CT; ch++) acc[ch] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float* t = T + idx[k] * CT;
+#pragma unroll
+            for (int ch = 0; ch < CT; ch++) acc[ch] += w[k] * t[ch];
+        }
+#pragma unroll
+        for (int ch = 0; ch < CT; ch++) o[ch] = acc[ch];
+    } else {
+        for (int ch = 0; ch < C; ch++) {
+            float a = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) a += w[k] * T[idx[k] * C + ch];
+            o[ch] = a;
+        }
+    }
+}
+
+// ---- backward -------------------------------------------------------------------------------------------------------
+struct TxGrid {
+    int Bt, R;
+    int64_t n, total;     // samples per batch, B * n
+    uint32_t ncells;      // Bt * 6 * (R + 1)^2; the sentinel key of samples with no footprint
+};
+
+__device__ __forceinline__ uint32_t tx_cell_key(const TxGrid& g, int bt, int f, int x0, int y0) {
+    const uint32_t E = (uint32_t)g.R + 1u;
+    return (((uint32_t)bt * 6u + (uint32_t)f) * E + (uint32_t)(y0 + 1)) * E + (uint32_t)(x0 + 1);
+}
+
+__global__ void __launch_bounds__(256)
+sgr_texture_cube_key_kernel(TxGrid g, const float* __restrict__ uv, uint32_t* __restrict__ keys) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= g.total) return;
+    int face;
+    float x, y;
+    uint32_t key = g.ncells;
+    if (tx_coords(uv[3 * s], uv[3 * s + 1], uv[3 * s + 2], g.R, face, x, y))
+        key = tx_cell_key(g, g.Bt == 1 ? 0 : (int)(s / g.n), face, (int)floorf(x), (int)floorf(y));
+    keys[s] = key;
+}
+
+__global__ void __launch_bounds__(256)
+sgr_texture_cube_starts_kernel(uint32_t ncells, uint32_t nsorted, const uint32_t* __restrict__ keys,
+                               uint32_t* __restrict__ starts) {
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > ncells) return;
+    uint32_t lo = 0, hi = nsorted;  // first position with key >= c
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < (uint32_t)c) lo = mid + 1; else hi = mid;
+    }
+    starts[c] = lo;
+}
+
+__global__ void __launch_bounds__(256)
+sgr_texture_cube_record_kernel(TxGrid g, int C, const float* __restrict__ uv, const float* __restrict__ dout,
+                               const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
+                               float2* __restrict__ rec, float* __restrict__ gs) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= g.total || keys[i] >= g.ncells) return;  // the sentinel run at the end is never read
+    const int64_t s = order[i];
+    int face;
+    float x, y;
+    tx_coords(uv[3 * s], uv[3 * s + 1], uv[3 * s + 2], g.R, face, x, y);
+    rec[i] = make_float2(x - floorf(x), y - floorf(y));
+    for (int ch = 0; ch < C; ch++) gs[i * C + ch] = dout[s * C + ch];
+}
+
+// Adds the contributions of the samples of cell (x0, y0) of face f to texel `t` (index within its batch's 6 R R).
+// CT > 0: all CT channels; CT = 0: channel ch of C.
+template <int CT>
+__device__ __forceinline__ void tx_walk_cell(const TxGrid& g, const SgrCubeSeam& sm, const uint32_t* __restrict__ starts,
+                                             const float2* __restrict__ rec, const float* __restrict__ gs, int C, int ch,
+                                             int bt, int f, int x0, int y0, int64_t t, double* acc) {
+    const uint32_t key = tx_cell_key(g, bt, f, x0, y0);
+    const uint32_t i0 = starts[key], i1 = starts[key + 1];
+    if (i0 == i1) return;
+    // weight of t in this cell = sum_k coef[k] w_k(fx, fy): coef[k] = 1 where tap k is t; a missing corner tap's weight
+    // is shared by the other three, so it carries 1/3 for each of them that is t
+    int64_t idx[4];
+    const int miss = tx_cell_taps(sm, g.R, f, x0, y0, idx);
+    float coef[4];
+    float hits = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        coef[k] = (idx[k] == t) ? 1.f : 0.f;
+        hits += coef[k];
+    }
+    if (miss >= 0) coef[miss] = hits * (1.f / 3.f);
+    for (uint32_t i = i0; i < i1; i++) {
+        const float2 r = rec[i];
+        float w[4];
+        tx_weights(r.x, r.y, w);
+        const float wt = coef[0] * w[0] + coef[1] * w[1] + coef[2] * w[2] + coef[3] * w[3];
+        if constexpr (CT > 0) {
+#pragma unroll
+            for (int c = 0; c < CT; c++) acc[c] += (double)(wt * gs[(size_t)i * CT + c]);
+        } else {
+            acc[0] += (double)(wt * gs[(size_t)i * C + ch]);
+        }
+    }
+}
+
+template <int CT>
+__global__ void __launch_bounds__(256)
+sgr_texture_cube_gather_kernel(TxGrid g, SgrCubeSeam sm, int Crt, const uint32_t* __restrict__ starts,
+                               const float2* __restrict__ rec, const float* __restrict__ gs, float* __restrict__ dtex) {
+    const int C = CT > 0 ? CT : Crt;
+    const int R = g.R;
+    const int64_t per = 6 * (int64_t)R * R;
+    const int64_t lane = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t tg = CT > 0 ? lane : lane / C;  // texel over all Bt batches
+    const int ch = CT > 0 ? 0 : (int)(lane - tg * C);
+    if (tg >= g.Bt * per) return;
+    const int bt = (int)(tg / per);
+    const int64_t t = tg - bt * per;
+    const int f = (int)(t / ((int64_t)R * R));
+    const int y = (int)((t / R) % R), x = (int)(t % R);
+    double acc[CT > 0 ? CT : 1];  // double sums: a texel of a small map collects thousands of samples
+#pragma unroll
+    for (int c = 0; c < (CT > 0 ? CT : 1); c++) acc[c] = 0.0;
+    // own cells: the texel is tap (x - x0, y - y0) of cells x0 in {x-1, x}, y0 in {y-1, y}
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        tx_walk_cell<CT>(g, sm, starts, rec, gs, C, ch, bt, f, x - 1 + (k & 1), y - 1 + (k >> 1), t, acc);
+    // a texel on edge e of its face is the outside tap of the two border cells of the neighbouring face next to it
+    for (int e = 0; e < 4; e++) {
+        const bool on = e == 0 ? x == 0 : e == 1 ? x == R - 1 : e == 2 ? y == 0 : y == R - 1;
+        if (!on) continue;
+        const int k = e < 2 ? y : x;
+        const int gf = sm.g[f][e], be = sm.back[f][e];
+        const int gc = sm.c0[f][e] * (R - 1) + sm.c1[f][e] * k, gr = sm.r0[f][e] * (R - 1) + sm.r1[f][e] * k;
+        for (int j = 0; j < 2; j++) {
+            int cx, cy;
+            if (be < 2) { cx = be == 0 ? -1 : R - 1; cy = gr - 1 + j; }
+            else { cy = be == 2 ? -1 : R - 1; cx = gc - 1 + j; }
+            tx_walk_cell<CT>(g, sm, starts, rec, gs, C, ch, bt, gf, cx, cy, t, acc);
+        }
+    }
+    if constexpr (CT > 0) {
+#pragma unroll
+        for (int c = 0; c < CT; c++) dtex[tg * CT + c] = (float)acc[c];
+    } else {
+        dtex[tg * C + ch] = (float)acc[0];
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------
+namespace {
+
+const int kSU[6] = {-1, 1, 1, 1, 1, -1}, kSV[6] = {-1, -1, 1, -1, -1, -1};
+
+// the contract's face choice and (u, v), in double
+void face_uv(const double d[3], int& f, double& u, double& v) {
+    const double ax = fabs(d[0]), ay = fabs(d[1]), az = fabs(d[2]);
+    double c, s, t;
+    if (az > fmax(ax, ay)) { c = d[2]; s = d[0]; t = d[1]; f = 4 + (c < 0); }
+    else if (ay > ax) { c = d[1]; s = d[0]; t = d[2]; f = 2 + (c < 0); }
+    else { c = d[0]; s = d[2]; t = d[1]; f = 0 + (c < 0); }
+    const double m = 0.5 / fabs(c);
+    u = s * kSU[f] * m + 0.5;
+    v = t * kSV[f] * m + 0.5;
+}
+
+// its inverse: the direction through texel centre (col, row) of face f, which may lie one texel outside the face
+void texel_dir(int f, int R, int col, int row, double d[3]) {
+    const double s = (2.0 * (col + 0.5) / R - 1.0) * kSU[f], t = (2.0 * (row + 0.5) / R - 1.0) * kSV[f];
+    const double c = (f & 1) ? -1.0 : 1.0;
+    if (f < 2) { d[0] = c; d[1] = t; d[2] = s; }
+    else if (f < 4) { d[0] = s; d[1] = c; d[2] = t; }
+    else { d[0] = s; d[1] = t; d[2] = c; }
+}
+
+// Seam table: a tap one texel across edge e of face f points into the neighbouring face; the texel it lands on there
+// is the one that shares the edge segment (the along-edge coordinate is kept, the across-edge one is the border texel).
+// Derived at two resolutions and checked at every edge position.
+bool derive_seam(SgrCubeSeam& sm) {
+    for (int f = 0; f < 6; f++)
+        for (int e = 0; e < 4; e++) {
+            for (int pass = 0; pass < 2; pass++) {
+                const int R = pass ? 7 : 8;
+                int coef[2][2] = {{0, 0}, {0, 0}}, g0 = -1;
+                for (int k = 0; k < R; k++) {
+                    const int col = e == 0 ? -1 : e == 1 ? R : k, row = e == 2 ? -1 : e == 3 ? R : k;
+                    double d[3], u, v;
+                    int g;
+                    texel_dir(f, R, col, row, d);
+                    face_uv(d, g, u, v);
+                    const int gc = (int)floor(u * R), gr = (int)floor(v * R);
+                    if (gc < 0 || gc >= R || gr < 0 || gr >= R || g == f) return false;
+                    if (k == 0) {
+                        g0 = g;
+                        coef[0][0] = gc == 0 ? 0 : gc == R - 1 ? 1 : -1;
+                        coef[1][0] = gr == 0 ? 0 : gr == R - 1 ? 1 : -1;
+                        if (coef[0][0] < 0 || coef[1][0] < 0) return false;
+                    } else if (k == 1) {
+                        coef[0][1] = gc - coef[0][0] * (R - 1);
+                        coef[1][1] = gr - coef[1][0] * (R - 1);
+                    }
+                    if (g != g0 || gc != coef[0][0] * (R - 1) + coef[0][1] * k || gr != coef[1][0] * (R - 1) + coef[1][1] * k)
+                        return false;
+                }
+                const int8_t ent[5] = {(int8_t)g0, (int8_t)coef[0][0], (int8_t)coef[0][1], (int8_t)coef[1][0],
+                                       (int8_t)coef[1][1]};
+                int8_t* dst[5] = {&sm.g[f][e], &sm.c0[f][e], &sm.c1[f][e], &sm.r0[f][e], &sm.r1[f][e]};
+                for (int q = 0; q < 5; q++) {
+                    if (pass && *dst[q] != ent[q]) return false;  // the same table at both resolutions
+                    *dst[q] = ent[q];
+                }
+            }
+        }
+    for (int f = 0; f < 6; f++)
+        for (int e = 0; e < 4; e++) {
+            const int g = sm.g[f][e];
+            int back = -1;
+            for (int b = 0; b < 4; b++)
+                if (sm.g[g][b] == f) back = back < 0 ? b : 4;  // exactly one edge of g leads back
+            if (back < 0 || back > 3) return false;
+            sm.back[f][e] = (int8_t)back;
+        }
+    return true;
+}
+
+const SgrCubeSeam* seam() {
+    static SgrCubeSeam sm;
+    static const bool ok = derive_seam(sm);
+    return ok ? &sm : nullptr;
+}
+
+int check_args(int Bt, int B, int R, int C, int64_t n, TxGrid& g) {
+    if (R < 1 || C < 1 || B < 1 || n < 0 || !(Bt == 1 || Bt == B))
+        return sgr_set_error(SGR_E_INVALID, "texture: need R >= 1, C >= 1, B >= 1, n >= 0 and Bt = 1 or B");
+    const uint64_t E = (uint64_t)R + 1, ncells = (uint64_t)Bt * 6 * E * E;
+    if (ncells >= 0xffffffffull)
+        return sgr_set_error(SGR_E_INVALID, "texture: Bt * 6 * (R + 1)^2 cell keys do not fit in 32 bits");
+    if ((uint64_t)B * (uint64_t)n > 0x7fffffffull)
+        return sgr_set_error(SGR_E_INVALID, "texture: more than 2^31 - 1 samples");
+    if (!seam()) return sgr_set_error(SGR_E_INVALID, "texture: the cube seam table could not be derived");
+    g.Bt = Bt;
+    g.R = R;
+    g.n = n;
+    g.total = (int64_t)B * n;
+    g.ncells = (uint32_t)ncells;
+    return 0;
+}
+
+struct TxWork {
+    uint32_t *keys[2], *vals[2], *hist, *scan_tmp, *starts;
+    float2* rec;
+    float* gs;
+};
+
+TxWork carve(char* base, const TxGrid& g, int C, char** end = nullptr) {
+    TxWork w;
+    char* p = base;
+    const size_t n = g.total ? (size_t)g.total : 1;
+    sgr_carve(p, w.keys[0], n);
+    sgr_carve(p, w.keys[1], n);
+    sgr_carve(p, w.vals[0], n);
+    sgr_carve(p, w.vals[1], n);
+    sgr_carve(p, w.hist, sgr_sort_hist_words(n));
+    sgr_carve(p, w.scan_tmp, sgr_scan_tmp_count(1));
+    sgr_carve(p, w.starts, (size_t)g.ncells + 1);
+    sgr_carve(p, w.rec, n);
+    sgr_carve(p, w.gs, n * C);
+    if (end) *end = p;
+    return w;
+}
+
+unsigned blocks(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+}  // namespace
+
+size_t sgr_texture_cube_workspace_bytes(int Bt, int B, int R, int C, int64_t n) {
+    TxGrid g;
+    if (check_args(Bt, B, R, C, n, g) < 0) return 0;
+    return sgr_required([&](char* base, char** end) { carve(base, g, C, end); });
+}
+
+int sgr_texture_cube_forward(int Bt, int B, int R, int C, int64_t n, const float* tex, const float* uv, float* out,
+                             void* stream_) {
+    TxGrid g;
+    if (const int rc = check_args(Bt, B, R, C, n, g)) return rc;
+    if (!tex || !uv || !out) return sgr_set_error(SGR_E_INVALID, "texture: tex, uv and out are required");
+    if (g.total == 0) return 0;
+    hipStream_t s = (hipStream_t)stream_;
+    const SgrCubeSeam& sm = *seam();
+    if (C == 3) sgr_texture_cube_fwd_kernel<3><<<blocks(g.total), 256, 0, s>>>(Bt, R, C, n, g.total, tex, uv, out, sm);
+    else sgr_texture_cube_fwd_kernel<0><<<blocks(g.total), 256, 0, s>>>(Bt, R, C, n, g.total, tex, uv, out, sm);
+    TX_HIP(hipGetLastError());
+    return 0;
+}
+
+int sgr_texture_cube_backward(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
+                              float* dL_dtex, void* workspace, void* stream_) {
+    TxGrid g;
+    if (const int rc = check_args(Bt, B, R, C, n, g)) return rc;
+    if (!uv || !dL_dout || !dL_dtex || !workspace)
+        return sgr_set_error(SGR_E_INVALID, "texture: uv, dL_dout, dL_dtex and workspace are required");
+    hipStream_t s = (hipStream_t)stream_;
+    const SgrCubeSeam& sm = *seam();
+    TxWork w = carve((char*)sgr_align_up((size_t)workspace, 256), g, C);
+    int cur = 0;
+    if (g.total) {
+        sgr_texture_cube_key_kernel<<<blocks(g.total), 256, 0, s>>>(g, uv, w.keys[0]);
+        int end_bit = 1;
+        while (end_bit < 32 && (g.ncells >> end_bit)) end_bit++;  // the sentinel ncells is the largest key
+        cur = sgr_launch_sort_pairs32(w.keys, w.vals, (uint32_t)g.total, end_bit, w.hist, w.scan_tmp, s, true);
+        sgr_texture_cube_record_kernel<<<blocks(g.total), 256, 0, s>>>(g, C, uv, dL_dout, w.keys[cur], w.vals[cur], w.rec,
+                                                                       w.gs);
+    }
+    sgr_texture_cube_starts_kernel<<<blocks((uint64_t)g.ncells + 1), 256, 0, s>>>(g.ncells, (uint32_t)g.total, w.keys[cur],
+                                                                                  w.starts);
+    const uint64_t texels = (uint64_t)Bt * 6 * R * R;
+    if (C == 3)
+        sgr_texture_cube_gather_kernel<3><<<blocks(texels), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
+    else
+        sgr_texture_cube_gather_kernel<0><<<blocks(texels * C), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
+    TX_HIP(hipGetLastError());
+    return 0;
+}
