@@ -29,7 +29,7 @@ SYMBOLS = [
     "sgr_lidar_work_bytes", "sgr_lidar_depth_forward", "sgr_lidar_depth_backward", "sgr_densify_work_bytes", "sgr_densify_plan",
     "sgr_densify_map", "sgr_densify_gather", "sgr_densify_split_children", "sgr_densify_prune_mask",
     "sgr_densify_compact", "sgr_reset_opacity", "sgr_texture_cube_workspace_bytes", "sgr_texture_cube_forward",
-    "sgr_texture_cube_backward",
+    "sgr_texture_cube_backward", "sgr_adam_span_elems", "sgr_adam_step",
 ]
 
 
@@ -137,6 +137,10 @@ def lib():
         L.sgr_texture_cube_forward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp]
         L.sgr_texture_cube_backward.restype = i
         L.sgr_texture_cube_backward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp, vp]
+        L.sgr_adam_span_elems.restype = i
+        L.sgr_adam_span_elems.argtypes = []
+        L.sgr_adam_step.restype = i
+        L.sgr_adam_step.argtypes = [vp, i, vp, i, C.c_int64, C.c_double, C.c_double, vp]
         L.sgr_knn.restype = i
         L.sgr_knn.argtypes = [i, vp, vp, ALLOC_FN, vp, vp]
         L.sgr_export_internal.restype = i
