@@ -45,7 +45,7 @@ int sgr_version(void);
  * reference's torch::full(0) would leave them).  Returns num_rendered (R) = the number of (tile, Gaussian) instances this
  * call emitted; it sizes the binning buffer and is what sgr_backward must be given.  By default a Gaussian is emitted
  * only for the tiles in which it can reach alpha >= 1/255 (a subset of the reference's getRect square: same images, see
- * sgr_test_switches bits 10 / 11), so R is smaller than the reference's count for the same frame. */
+ * SGR_SW_REF_RECT / SGR_SW_NO_TILE_MASK), so R is smaller than the reference's count for the same frame. */
 int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
                 sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
                 int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -207,49 +207,38 @@ int sgr_profile_sample(int every);
 int sgr_export_internal(int which, int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
                         char* image_buffer, void* dst, void* stream);
 
-/* ---- A/B switches of the blend kernels (tests, tools/gpu_ab.sh): bit 0 no quadrant cull, bit 1 no DPP wave
- * reduction, bit 2 no deterministic LDS combine, bit 3 the backward ignores the forward's hit record and redoes the
- * geometric cull, bit 4 the S = 0 backward runs the transposed-accumulation kernel (A/B design, slower),
- * bit 5 the radix sorts run in their one-sweep (decoupled look-back) form (A/B design, slower; SGR_ONESWEEP),
- * bit 7 (SGR_EXACT=1) PARITY MODE: the blend FORWARD evaluates the reference's own power expression, the device
- * library's expf and the unfused D += d * alpha * T of the depth, alpha and semantic sums -- alpha / depth / semantic images
- * and n_contrib bit-identical to the reference's kernels; the three COLOUR sums are formed as FMAs (their inputs, the SH
- * colours, already differ from the reference's in the last bit): the colour image is held to rel 1e-4, not bit-exact; the blend BACKWARD evaluates the reference's power expression and makes every blend / skip decision
- * exactly as the forward did (a visit with a pixel within 4e-6 of the 1/255 threshold falls back to the accurate expf), the
- * per-Gaussian backward runs without FP contraction -- gradients within rel 1e-4 end to end,
- * bit 8 (SGR_SW=1) the S = 0 blend backward runs its scalar-walk form (csrc/sgr_blend_bwd_sw.hip: A/B design, slower),
- * bit 9 (SGR_RS_WAVE=1) the per-Gaussian row sum runs its wave-cooperative form (A/B design, slower),
- * bit 6 (SGR_PRE_STAGE=1) the preprocess stages its SH rows through LDS whatever P is (default: from 3 M Gaussians),
- * bit 10 (SGR_REF_RECT=1) every Gaussian is emitted for the reference's whole tile rect (auxiliary.h getRect), so that
- * num_rendered, point_list, the sorted keys and the ranges are the reference's arrays entry for entry; default: the rect
- * cut down to the tiles where the Gaussian can pass the alpha >= 1/255 test -- fewer instances, bit-identical images (gradients: same terms, the row sum groups its additions differently),
- * bit 11 (SGR_NO_TILE_MASK=1) the cut-down rect is the bounding box of those tiles without the per-tile mask (A/B),
- * bit 13 (SGR_REF_RECT_PLAIN=1, with bit 10) the reference's rects without the marks described next (round-5 form, A/B).
- * Since round 6 bit 10 emits the reference's list with the instances that lie outside the cut-down rect / tile mask MARKED
- * (bit 31 of the internal list entry; export 8 strips it): they are counted, sorted and ranged exactly like the reference's
- * -- num_rendered, point_list, keys, ranges, n_contrib entry for entry -- but the blend kernels skip them without fetching
- * their record and they own no partial-gradient row.
- * bits 14 / 15: tile order of the two blend launches.  Default: decided per frame on the device -- one one-workgroup launch
- * per forward looks at the list lengths and, when the longest list is more than 2.5 x the mean (a street scene: empty sky
- * next to actors), sorts the tile ids longest list first; an even scene keeps the XCD-aware supertile order.  Same results
- * either way.  bit 14 (SGR_LPT=1) always longest-first, bit 15 (SGR_NO_LPT=1) never (and no extra launch).
- * bits 16 / 17: with the reference's rects (bit 10) the forward also writes the COMPACT list of the instances it blended
- * somewhere (exports 19 / 20) and the blend backward walks that list instead of the list positions (the marked-dead 40 % and
- * the instances behind saturated pixels are never staged); same gradients bit for bit.  bit 16 (SGR_NO_HLIST=1) never (the
- * round-5 walk, A/B), bit 17 (SGR_HLIST_ALWAYS=1) in every mode (with the cut-down rects it costs the forward more than it
- * saves the backward).  Read when the forward runs and recorded in the frame's buffers: the backward walks the list if its
- * frame has one (bit 16 at backward time forces the positional walk, which every frame supports).
- * bit 18 (SGR_KEY32=1) the instance list's tile keys stay 32-bit (default: 16-bit whenever the frame has fewer than 65535
- * tiles -- the tile sort then moves 6 instead of 8 bytes per pair and pass; same lists, A/B).
- * bit 12 (SGR_TILE_SORT=1) the binning chain runs in its per-tile form (csrc/sgr_tile_sort.hip: no depth pre-sort of the
- * Gaussians, emission in index order, stable tile sort, then every tile's list radix-sorted by depth in LDS) -- the same
- * lists entry for entry (tests/test_gpu_tile_sort.py); A/B design, measured in DESIGN.md section 3.
- * mask >= 0 sets them process-wide, mask < 0 only queries; returns the previous mask.  The initial
- * value comes from the environment (SGR_NO_CULL, SGR_NO_DPP, SGR_NO_DET, SGR_NO_HITS, SGR_V2), read once. */
+/* ---- A/B switches (tests, tools/gpu_ab.sh), one bit each; the environment names in parentheses set the initial mask */
+enum {
+    SGR_SW_NO_CULL = 1 << 0,         /* (SGR_NO_CULL) blend kernels: no quadrant cull */
+    SGR_SW_NO_DPP = 1 << 1,          /* (SGR_NO_DPP) blend backward: no DPP wave reduction */
+    SGR_SW_NO_DET = 1 << 2,          /* (SGR_NO_DET) blend backward: no deterministic LDS combine */
+    SGR_SW_NO_HITS = 1 << 3,         /* (SGR_NO_HITS) blend backward ignores the forward's hit record, redoes the cull */
+    SGR_SW_USE_V2 = 1 << 4,          /* (SGR_V2) S = 0 blend backward: transposed-accumulation kernel (variant build) */
+    SGR_SW_USE_ONESWEEP = 1 << 5,    /* (SGR_ONESWEEP) radix sorts in their one-sweep look-back form (variant build) */
+    SGR_SW_PRE_STAGE_SH = 1 << 6,    /* (SGR_PRE_STAGE) preprocess stages SH rows through LDS whatever P (default: P >= 3 M) */
+    SGR_SW_EXACT = 1 << 7,           /* (SGR_EXACT) parity mode: the reference's blend arithmetic */
+    SGR_SW_USE_SW = 1 << 8,          /* (SGR_SW, SGR_SW8) S = 0 blend backward: scalar-walk kernel (variant build) */
+    SGR_SW_USE_RS_WAVE = 1 << 9,     /* (SGR_RS_WAVE, SGR_SW9) per-Gaussian row sum: wave-cooperative form (variant build) */
+    SGR_SW_REF_RECT = 1 << 10,       /* (SGR_REF_RECT) the reference's tile rects and lists, out-of-rect instances marked dead */
+    SGR_SW_NO_TILE_MASK = 1 << 11,   /* (SGR_NO_TILE_MASK) cut-down rect = bounding box only, no per-tile mask */
+    SGR_SW_TILE_SORT = 1 << 12,      /* (SGR_TILE_SORT) binning chain in its per-tile form (csrc/sgr_tile_sort.hip) */
+    SGR_SW_REF_RECT_PLAIN = 1 << 13, /* (SGR_REF_RECT_PLAIN) with REF_RECT: the reference's rects without the dead marks */
+    SGR_SW_LPT = 1 << 14,            /* (SGR_LPT) blend launches always walk the tiles longest list first */
+    SGR_SW_NO_LPT = 1 << 15,         /* (SGR_NO_LPT) ... never (default: decided per frame on the device) */
+    SGR_SW_NO_HLIST = 1 << 16,       /* (SGR_NO_HLIST) no compact hit list: the blend backward walks list positions */
+    SGR_SW_HLIST_ALWAYS = 1 << 17,   /* (SGR_HLIST_ALWAYS) compact hit list (exports 19 / 20) in every rect mode */
+    SGR_SW_KEY32 = 1 << 18           /* (SGR_KEY32) 32-bit tile keys (default: 16-bit below 65535 tiles) */
+};
+/* Every call reads the mask once, at entry.  The forward records the rect mode (REF_RECT, REF_RECT_PLAIN, NO_TILE_MASK) and
+ * whether it wrote the compact hit list in the frame's buffers, and always leaves a valid tile-order flag: the backward and
+ * the exports follow the frame there.  Every other bit is read at the backward's / export's own call time and must match the
+ * forward's: NO_CULL, NO_HITS, EXACT and the variant bits pick the backward kernels, TILE_SORT (and sgr_set_lazy) decide
+ * which buffer holds the list, KEY32 the key width.  A library built without the variants ignores USE_V2, USE_ONESWEEP,
+ * USE_SW and USE_RS_WAVE.  mask >= 0 sets the switches process-wide, mask < 0 only queries; returns the previous mask. */
 int sgr_test_switches(int mask);
 /* 1 when the library was built with -DSGR_WITH_VARIANTS=1 (tools/build_variant.py): it then also contains the designs that
  * were measured slower and are kept as A/Bs -- the transposed-accumulation and scalar-walk blend backward, the one-sweep
- * radix sorts, the wave-cooperative row sum (sgr_test_switches bits 4, 5, 8, 9).  The shipped library returns 0 and
+ * radix sorts, the wave-cooperative row sum (USE_V2, USE_SW, USE_ONESWEEP, USE_RS_WAVE).  The shipped library returns 0 and
  * ignores those bits. */
 int sgr_has_variants(void);
 /* ---- the forward without a host wait (extension; the reference blocks on num_rendered, rasterizer_impl.cu:284) ---------

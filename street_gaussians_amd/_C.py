@@ -409,7 +409,6 @@ def sh_grad_from_rows(P, degree, M, V, means_ptr, means_stride, campos_ptr, camp
     return out
 
 
-NO_CULL, NO_DPP, NO_DET, NO_HITS, USE_V2, USE_ONESWEEP, PRE_STAGE_SH, EXACT, USE_SW, USE_RS_WAVE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 def has_variants() -> bool:
     """True when the loaded library also holds the rejected A/B designs (USE_V2, USE_ONESWEEP, USE_SW, USE_RS_WAVE): a
     tools/build_variant.py build with -DSGR_WITH_VARIANTS=1.  The shipped library ignores those switches."""
@@ -428,15 +427,26 @@ def lazy_status():
     return r.value, c.value, f.value
 
 
-NO_TILE_MASK = 2048  # bounding-box rects without the per-tile mask (A/B)
-TILE_SORT = 4096  # binning chain A/B: index-order emission + per-tile LDS radix sort by depth (csrc/sgr_tile_sort.hip)
-LPT = 16384  # blend launches ALWAYS walk the tiles longest list first (default: decided per frame, longest list > 2.5 x the mean)
-NO_HLIST = 65536  # the blend backward steps through list POSITIONS instead of the forward's compact list of hit instances (A/B)
-KEY32 = 262144  # 32-bit tile keys in the instance list (default: 16-bit whenever the frame has fewer than 65535 tiles; A/B)
-HLIST_ALWAYS = 131072  # ... the compact list in every mode (default: with the reference's rects, REF_RECT, only)
-NO_LPT = 32768  # blend launches never do: the XCD-aware supertile order without looking at the lists (round-5 behaviour)
-REF_RECT_PLAIN = 8192  # with REF_RECT: the reference's rects WITHOUT the dead-instance marks (the round-5 form of the strict mode, A/B)
-REF_RECT = 1024  # emit every Gaussian for the reference's whole tile rect (default: cut down to where alpha >= 1/255 is possible)
+# sgr_test_switches bits, in bit order: the SGR_SW_* enum of include/sgr.h (same names without the prefix)
+NO_CULL = 1 << 0  # blend kernels: no quadrant cull
+NO_DPP = 1 << 1  # blend backward: no DPP wave reduction
+NO_DET = 1 << 2  # blend backward: no deterministic LDS combine
+NO_HITS = 1 << 3  # blend backward ignores the forward's hit record and redoes the cull
+USE_V2 = 1 << 4  # S = 0 blend backward: transposed-accumulation kernel (variant build)
+USE_ONESWEEP = 1 << 5  # radix sorts in their one-sweep form (variant build)
+PRE_STAGE_SH = 1 << 6  # preprocess stages SH rows through LDS whatever P
+EXACT = 1 << 7  # parity mode of the blend kernels and the per-Gaussian backward
+USE_SW = 1 << 8  # S = 0 blend backward: scalar-walk kernel (variant build)
+USE_RS_WAVE = 1 << 9  # per-Gaussian row sum: wave-cooperative form (variant build)
+REF_RECT = 1 << 10  # emit every Gaussian for the reference's whole tile rect (default: cut down to where alpha >= 1/255 is possible)
+NO_TILE_MASK = 1 << 11  # bounding-box rects without the per-tile mask (A/B)
+TILE_SORT = 1 << 12  # binning chain A/B: index-order emission + per-tile LDS radix sort by depth (csrc/sgr_tile_sort.hip)
+REF_RECT_PLAIN = 1 << 13  # with REF_RECT: the reference's rects WITHOUT the dead-instance marks (A/B)
+LPT = 1 << 14  # blend launches ALWAYS walk the tiles longest list first (default: decided per frame, longest list > 2.5 x the mean)
+NO_LPT = 1 << 15  # ... never: the XCD-aware supertile order without looking at the lists
+NO_HLIST = 1 << 16  # the blend backward steps through list POSITIONS instead of the forward's compact list of hit instances (A/B)
+HLIST_ALWAYS = 1 << 17  # the forward writes the compact list in every mode (default: with REF_RECT only)
+KEY32 = 1 << 18  # 32-bit tile keys in the instance list (default: 16-bit whenever the frame has fewer than 65535 tiles; A/B)
 
 
 def test_switches(mask: int = -1) -> int:

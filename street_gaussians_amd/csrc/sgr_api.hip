@@ -75,31 +75,31 @@ static bool env_flag(const char* name) {
     return v && v[0] && v[0] != '0';
 }
 
-// (bit 6: the preprocess stages its SH rows through LDS -- an A/B that measured slower; bit 7: EXACT parity mode of the
-// blend kernels, sgr_math.h sgr_power_ref: the reference's power expression + accurate expf + true division)
-// A/B switches of the blend kernels (tests and tools/gpu_ab.sh): bit 0 no quadrant cull, 1 no DPP reduction,
-// 2 no deterministic LDS combine, 3 backward ignores the forward's hit record, 4 the S = 0 backward runs the
-// transposed-accumulation kernel (an A/B design that measured slower than the cross-lane reduction), 5 the
-// radix sorts run in their one-sweep form (an A/B design that measured slower, sgr_scan_sort.hip; SGR_ONESWEEP).  Process-wide, set through
-// sgr_test_switches(); the environment (SGR_NO_CULL / SGR_NO_DPP / SGR_NO_DET / SGR_NO_HITS / SGR_V2) only provides the
-// initial value, read ONCE -- the per-step path is one relaxed atomic load, no getenv.
+// The A/B switches (include/sgr.h SGR_SW_*), process-wide, set through sgr_test_switches().  The environment only provides
+// the initial value, read ONCE -- afterwards this is one relaxed atomic load, no getenv.  Read only by resolve_switches()
+// and sgr_test_switches().  (USE_ONESWEEP is not kept here: it is the sort's own flag, sgr_sort_set_one_sweep.)
 static std::atomic<int> g_switches{-1};
 #ifndef SGR_WITH_VARIANTS
 #define SGR_WITH_VARIANTS 0  // 1: the library also holds the designs that were measured slower (tools/build_variant.py)
 #endif
-// switch bits that select one of those designs: transposed backward (4), one-sweep sorts (5), scalar-walk backward (8),
-// wave-cooperative row sum (9) -- ignored by a build that does not contain them
-#define SGR_VARIANT_BITS (16 | 32 | 256 | 512)
+// switch bits that select one of those designs -- ignored by a build that does not contain them
+#define SGR_VARIANT_BITS (SGR_SW_USE_V2 | SGR_SW_USE_ONESWEEP | SGR_SW_USE_SW | SGR_SW_USE_RS_WAVE)
 static int switches() {
     int v = g_switches.load(std::memory_order_relaxed);
     if (v < 0) {
-        v = (env_flag("SGR_NO_CULL") ? 1 : 0) | (env_flag("SGR_NO_DPP") ? 2 : 0) | (env_flag("SGR_NO_DET") ? 4 : 0) |
-            (env_flag("SGR_NO_HITS") ? 8 : 0) | (env_flag("SGR_V2") ? 16 : 0) | (env_flag("SGR_PRE_STAGE") ? 64 : 0) |
-            (env_flag("SGR_EXACT") ? 128 : 0) | ((env_flag("SGR_SW8") || env_flag("SGR_SW")) ? 256 : 0) | ((env_flag("SGR_SW9") || env_flag("SGR_RS_WAVE")) ? 512 : 0) |
-            (env_flag("SGR_REF_RECT") ? 1024 : 0) | (env_flag("SGR_NO_TILE_MASK") ? 2048 : 0) | (env_flag("SGR_TILE_SORT") ? 4096 : 0) |
-            (env_flag("SGR_REF_RECT_PLAIN") ? 8192 : 0) | (env_flag("SGR_LPT") ? 16384 : 0) |
-            (env_flag("SGR_NO_LPT") ? 32768 : 0) | (env_flag("SGR_NO_HLIST") ? 65536 : 0) | (env_flag("SGR_HLIST_ALWAYS") ? 131072 : 0) |
-            (env_flag("SGR_KEY32") ? 262144 : 0);
+        static const struct { int bit; const char* names[2]; } env[] = {
+            {SGR_SW_NO_CULL, {"SGR_NO_CULL"}}, {SGR_SW_NO_DPP, {"SGR_NO_DPP"}}, {SGR_SW_NO_DET, {"SGR_NO_DET"}},
+            {SGR_SW_NO_HITS, {"SGR_NO_HITS"}}, {SGR_SW_USE_V2, {"SGR_V2"}}, {SGR_SW_PRE_STAGE_SH, {"SGR_PRE_STAGE"}},
+            {SGR_SW_EXACT, {"SGR_EXACT"}}, {SGR_SW_USE_SW, {"SGR_SW", "SGR_SW8"}},
+            {SGR_SW_USE_RS_WAVE, {"SGR_RS_WAVE", "SGR_SW9"}}, {SGR_SW_REF_RECT, {"SGR_REF_RECT"}},
+            {SGR_SW_NO_TILE_MASK, {"SGR_NO_TILE_MASK"}}, {SGR_SW_TILE_SORT, {"SGR_TILE_SORT"}},
+            {SGR_SW_REF_RECT_PLAIN, {"SGR_REF_RECT_PLAIN"}}, {SGR_SW_LPT, {"SGR_LPT"}}, {SGR_SW_NO_LPT, {"SGR_NO_LPT"}},
+            {SGR_SW_NO_HLIST, {"SGR_NO_HLIST"}}, {SGR_SW_HLIST_ALWAYS, {"SGR_HLIST_ALWAYS"}}, {SGR_SW_KEY32, {"SGR_KEY32"}},
+        };
+        v = 0;
+        for (const auto& e : env)
+            for (const char* name : e.names)
+                if (name && env_flag(name)) v |= e.bit;
         if (!SGR_WITH_VARIANTS) v &= ~SGR_VARIANT_BITS;
         g_switches.store(v, std::memory_order_relaxed);
     }
@@ -229,29 +229,6 @@ static hipError_t wait_for_readback_(uint32_t* host_vals, hipEvent_t landed) {
     return hipEventSynchronize(landed);
 }
 
-static bool tile_sort_on() { return (switches() & 4096) != 0; }
-// Tile rects of a frame (sgr_preprocess.hip `tight`): 2 = the reference's rect cut down to the bounding box of the tiles where
-// alpha >= 1/255 is possible + a tile mask inside it (default), 1 = the box alone (switch bit 11), 3 = switch bit 10
-// (SGR_REF_RECT): the reference's rects, i.e. its lists entry for entry, with the instances outside box / mask MARKED dead
-// (they are sorted and counted like the reference's, but the blend kernels skip them and they own no gradient row), 0 = bits
-// 10 + 13 (SGR_REF_RECT_PLAIN): the reference's rects without marks (round-5 form of the strict mode, A/B).
-static int rect_mode() {
-    const int sw = switches();
-    if (sw & 1024) return (sw & 8192) ? 0 : 3;
-    return (sw & 2048) ? 1 : 2;
-}
-// The compact hit list (SgrBinView::hlist) is written by the forward and walked by the blend backward where it pays: with the
-// reference's rects (switch bit 10) 40 % of a list cannot blend and the backward takes that many fewer rounds (-24 us at the
-// bench size against +10 us in the forward); with the cut-down rects the lists hold next to nothing to skip and the forward's
-// 10 us buy nothing (measured).  Bit 16 turns it off, bit 17 on in every mode (A/B and tests).
-static bool hit_list_on() {
-    const int sw = switches();
-    return SGR_HLIST && !(sw & 65536) && ((sw & 1024) || (sw & 131072));
-}
-// The tile keys of the instance list are 16-bit whenever the frame has fewer than 65535 tiles (the all-ones key is the padding of
-// the lazy mode): the tile sort moves 6 instead of 8 bytes per pair and pass and its histogram reads half.  Bit 18 (SGR_KEY32=1)
-// keeps 32-bit keys (A/B; frames with more tiles -- beyond 4096 x 4080 pixels -- take them anyway).  Same buffers either way.
-static int tile_key16(size_t T) { return (T < 65535u && !(switches() & 262144)) ? 1 : 0; }
 // depth pre-sort: three passes of 9-bit digits below this many Gaussians, four of 7 bits from it on (sgr_scan_sort.hip)
 static int depth9_max_p() {
     static const int v = [] { const char* e = getenv("SGR_DEPTH9_MAX_P"); return e ? atoi(e) : 750000; }();
@@ -260,63 +237,6 @@ static int depth9_max_p() {
 static int pre_stage_min_p() {
     static const int v = [] { const char* e = getenv("SGR_PRE_STAGE_MIN_P"); return e ? atoi(e) : 3000000; }();
     return v;
-}
-
-// rasterizer_impl.cu:35-50
-static uint32_t getHigherMsb(uint32_t n) {
-    uint32_t msb = sizeof(n) * 4;
-    uint32_t step = msb;
-    while (step > 1) {
-        step /= 2;
-        if (n >> msb) msb += step;
-        else msb -= step;
-    }
-    if (n >> msb) msb++;
-    return msb;
-}
-
-// The camera arrives as three device arrays; a small kernel packs it (plus the host-side scalars) into a
-// device-resident SgrCam so no device->host copy is needed.  The same launch clears what the forward needs cleared before
-// its first real kernel -- the 16 header words (flags, num_rendered) and the T tile ranges (rasterizer_impl.cu:313) --
-// which were two memset dispatches of ~5 us each.
-__global__ void __launch_bounds__(256)
-sgr_pack_camera_kernel(SgrCam* cam, const float* view, const float* proj, const float* campos, float tan_fovx,
-                       float tan_fovy, float focal_x, float focal_y, int W, int H, int gx, int gy, float scale_modifier,
-                       uint32_t* header, uint2* ranges, int T, uint32_t rect_mode) {
-    const int t = threadIdx.x;
-    for (int i = blockIdx.x * 256 + t; i < T; i += gridDim.x * 256) ranges[i] = make_uint2(0u, 0u);
-    if (blockIdx.x != 0) return;
-    if (t < 16) {
-        // word 6: the frame's tile-rect mode; word 7: whether its forward writes the compact hit list (the blend backward
-        // follows the FRAME's flag, whatever the switches say by the time it runs)
-        header[t] = t == 6 ? (rect_mode & 0xffu) : (t == 7 ? (rect_mode >> 8) : 0u);
-        cam->view[t] = view[t];
-        cam->proj[t] = proj ? proj[t] : 0.f;
-    }
-    if (t < 3) cam->campos[t] = campos ? campos[t] : 0.f;
-    if (t == 0) {
-        cam->tan_fovx = tan_fovx; cam->tan_fovy = tan_fovy;
-        cam->focal_x = focal_x; cam->focal_y = focal_y;
-        cam->W = W; cam->H = H; cam->gx = gx; cam->gy = gy;
-        cam->scale_modifier = scale_modifier;
-    }
-}
-
-// the SgrCam lives in the header block of the geometry buffer (words 16.. of the 64-word header)
-static SgrCam* cam_slot(const SgrGeomView& gv) { return reinterpret_cast<SgrCam*>(gv.header + 16); }
-static_assert(sizeof(SgrCam) <= 48 * 4, "SgrCam must fit the geometry header");
-static_assert(SGR_STAT_SEG_MAX == SGR_MAX_STAT_SEGMENTS, "sgr_common.h and include/sgr.h disagree");
-
-static void pack_camera(const SgrGeomView& gv, const float* view, const float* proj, const float* campos,
-                        float tan_fovx, float tan_fovy, int W, int H, float scale_modifier, uint2* ranges, int T,
-                        int rect_mode, hipStream_t s) {
-    const float focal_y = H / (2.0f * tan_fovy);  // rasterizer_impl.cu:225-226
-    const float focal_x = W / (2.0f * tan_fovx);
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const int nb = std::max(1, std::min(64, (T + 255) / 256));
-    sgr_pack_camera_kernel<<<nb, 256, 0, s>>>(cam_slot(gv), view, proj, campos, tan_fovx, tan_fovy, focal_x, focal_y, W, H,
-                                             gx, gy, scale_modifier, gv.header, ranges, T,
-                                             (uint32_t)rect_mode | (hit_list_on() ? 0x100u : 0u));
 }
 
 // ---- the forward without a host wait (sgr_set_lazy) ---------------------------------------------------------------
@@ -354,6 +274,127 @@ static thread_local LazyPending t_lazy;
 static int lazy_flags(const LazyPending& lp) {
     const uint32_t* hv = lp.host_vals;
     return (hv[4] > lp.cap ? 1 : 0) | ((hv[0] & 1u) ? 2 : 0) | (((hv[2] & 1u) && !lp.wide) ? 4 : 0);
+}
+
+// ---- the switches as one call sees them --------------------------------------------------------------------------------
+// Decoded from ONE load of the mask (and the lazy mode) at the entry of sgr_forward, sgr_backward_ex and sgr_export_internal
+// and passed down: a call that races with sgr_test_switches still runs entirely under one mask.
+struct Switches {
+    bool cull, dpp, det;  // blend kernels: quadrant cull, DPP wave reduction, deterministic LDS combine
+    bool use_hits;        // the blend backward follows the forward's hit record (else it redoes the geometric cull)
+    bool exact;           // parity mode: sgr_math.h sgr_power_ref in the blend kernels, sgr_gauss_bwd_strict.hip
+    bool v2, quad, rs_wave;  // variant builds: transposed S = 0 backward; scalar-walk S = 0 backward; wave-cooperative row sum
+    // Tile rects of a frame (sgr_preprocess.hip `tight`, header word 6): 2 = the bounding box of the tiles where alpha >= 1/255
+    // is possible + a tile mask inside it (default), 1 = the box alone, 3 = the reference's rects with the instances outside
+    // box / mask MARKED dead (REF_RECT), 0 = the reference's rects without marks (REF_RECT + REF_RECT_PLAIN, A/B).
+    int rect_mode;
+    // The compact hit list (SgrBinView::hlist) is written by the forward and walked by the blend backward where it pays: with
+    // the reference's rects 40 % of a list cannot blend and the backward takes that many fewer rounds (-24 us at the bench size
+    // against +10 us in the forward); with the cut-down rects the lists hold next to nothing to skip and the forward's 10 us buy
+    // nothing (measured).
+    bool hit_list;    // the forward writes it (header word 7: the backward follows its frame)
+    bool hlist_walk;  // the backward may walk it (NO_HLIST forces the positional walk, which every frame supports)
+    bool lazy_mode;   // sgr_set_lazy
+    bool tile_sort;   // per-tile binning chain (the lazy mode keeps the default chain)
+    // Tile order of the two blend launches: decided per frame on the device (sgr_tile_order_kernel), or forced longest-first
+    bool lpt, lpt_force;
+    bool pre_stage_forced, key32;
+    // SH rows staged through LDS (half a wave's rows at a time) or read per lane: bit-identical forms (tests); the staged one
+    // wins once the launch is deep enough to be throughput-bound -- measured 346 vs 360 us at 5 M Gaussians, 98.8 vs 90.2 us at
+    // 1 M -- so it is chosen by P (SGR_PRE_STAGE_MIN_P moves the threshold)
+    bool pre_stage(int P) const { return pre_stage_forced || P >= pre_stage_min_p(); }
+    // The tile keys of the instance list are 16-bit whenever the frame has fewer than 65535 tiles (the all-ones key is the
+    // padding of the lazy mode): the tile sort moves 6 instead of 8 bytes per pair and pass and its histogram reads half.
+    // Frames with more tiles -- beyond 4096 x 4080 pixels -- take 32-bit keys.  Same buffers either way.
+    int key16(size_t T) const { return (T < 65535u && !key32) ? 1 : 0; }
+};
+static Switches resolve_switches() {
+    const int m = switches();
+    const auto on = [m](int bits) { return (m & bits) != 0; };
+    Switches s;
+    s.cull = !on(SGR_SW_NO_CULL); s.dpp = !on(SGR_SW_NO_DPP); s.det = !on(SGR_SW_NO_DET); s.use_hits = !on(SGR_SW_NO_HITS);
+    s.exact = on(SGR_SW_EXACT); s.v2 = on(SGR_SW_USE_V2); s.rs_wave = on(SGR_SW_USE_RS_WAVE);
+    // (the scalar walk exists for the default blend settings only)
+    s.quad = SGR_WITH_VARIANTS && on(SGR_SW_USE_SW) &&
+             !on(SGR_SW_NO_CULL | SGR_SW_NO_DPP | SGR_SW_NO_DET | SGR_SW_NO_HITS | SGR_SW_USE_V2);
+    s.rect_mode = on(SGR_SW_REF_RECT) ? (on(SGR_SW_REF_RECT_PLAIN) ? 0 : 3) : (on(SGR_SW_NO_TILE_MASK) ? 1 : 2);
+    s.hlist_walk = SGR_HLIST && !on(SGR_SW_NO_HLIST);
+    s.hit_list = s.hlist_walk && on(SGR_SW_REF_RECT | SGR_SW_HLIST_ALWAYS);
+    s.lazy_mode = lazy_on();
+    s.tile_sort = on(SGR_SW_TILE_SORT) && !s.lazy_mode;
+    s.lpt = !on(SGR_SW_NO_LPT); s.lpt_force = on(SGR_SW_LPT);
+    s.pre_stage_forced = on(SGR_SW_PRE_STAGE_SH); s.key32 = on(SGR_SW_KEY32);
+    return s;
+}
+
+// rasterizer_impl.cu:35-50
+static uint32_t getHigherMsb(uint32_t n) {
+    uint32_t msb = sizeof(n) * 4;
+    uint32_t step = msb;
+    while (step > 1) {
+        step /= 2;
+        if (n >> msb) msb += step;
+        else msb -= step;
+    }
+    if (n >> msb) msb++;
+    return msb;
+}
+
+// Instance-list sizes requested from the caller sit on a coarse ladder (steps of 1/16 of the next lower power of two, at least
+// 1024), so that consecutive calls ask the caller's caching allocator for the SAME block size instead of a new, slightly
+// smaller one each time (every new size is a device allocation: tens of ms on some hosts).
+static uint32_t binning_ladder(size_t r) {
+    size_t step = 1;
+    while ((step << 1) <= r) step <<= 1;
+    step = std::max<size_t>(step >> 4, 1024);
+    return (uint32_t)std::min<size_t>((r + step - 1) / step * step, 0x7fffffffu);
+}
+
+// The camera arrives as three device arrays; a small kernel packs it (plus the host-side scalars) into a
+// device-resident SgrCam so no device->host copy is needed.  The same launch clears what the forward needs cleared before
+// its first real kernel -- the 16 header words (flags, num_rendered), the T tile ranges (rasterizer_impl.cu:313) and the
+// flag word of the tile-order block (sgr_wg_tile) -- which were two memset dispatches of ~5 us each.
+__global__ void __launch_bounds__(256)
+sgr_pack_camera_kernel(SgrCam* cam, const float* view, const float* proj, const float* campos, float tan_fovx,
+                       float tan_fovy, float focal_x, float focal_y, int W, int H, int gx, int gy, float scale_modifier,
+                       uint32_t* header, uint2* ranges, int T, uint32_t rect_mode) {
+    const int t = threadIdx.x;
+    for (int i = blockIdx.x * 256 + t; i < T; i += gridDim.x * 256) ranges[i] = make_uint2(0u, 0u);
+    if (blockIdx.x != 0) return;
+    if (t < 16) {
+        // word 6: the frame's tile-rect mode; word 7: whether its forward writes the compact hit list (the blend backward
+        // follows the FRAME's flag, whatever the switches say by the time it runs)
+        header[t] = t == 6 ? (rect_mode & 0xffu) : (t == 7 ? (rect_mode >> 8) : 0u);
+        cam->view[t] = view[t];
+        cam->proj[t] = proj ? proj[t] : 0.f;
+    }
+    if (t < 3) cam->campos[t] = campos ? campos[t] : 0.f;
+    if (t == 0) {
+        // frame order = the supertile order unless sgr_tile_order_kernel says otherwise: a backward always passes the
+        // frame-order form and walks the tiles as this frame's forward did, whether or not it ran the tile-order launch
+        reinterpret_cast<uint32_t*>(ranges + T)[T] = 0u;
+        cam->tan_fovx = tan_fovx; cam->tan_fovy = tan_fovy;
+        cam->focal_x = focal_x; cam->focal_y = focal_y;
+        cam->W = W; cam->H = H; cam->gx = gx; cam->gy = gy;
+        cam->scale_modifier = scale_modifier;
+    }
+}
+
+// the SgrCam lives in the header block of the geometry buffer (words 16.. of the 64-word header)
+static SgrCam* cam_slot(const SgrGeomView& gv) { return reinterpret_cast<SgrCam*>(gv.header + 16); }
+static_assert(sizeof(SgrCam) <= 48 * 4, "SgrCam must fit the geometry header");
+static_assert(SGR_STAT_SEG_MAX == SGR_MAX_STAT_SEGMENTS, "sgr_common.h and include/sgr.h disagree");
+
+static void pack_camera(const SgrGeomView& gv, const float* view, const float* proj, const float* campos,
+                        float tan_fovx, float tan_fovy, int W, int H, float scale_modifier, uint2* ranges, int T,
+                        const Switches& sw, hipStream_t s) {
+    const float focal_y = H / (2.0f * tan_fovy);  // rasterizer_impl.cu:225-226
+    const float focal_x = W / (2.0f * tan_fovx);
+    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
+    const int nb = std::max(1, std::min(64, (T + 255) / 256));
+    sgr_pack_camera_kernel<<<nb, 256, 0, s>>>(cam_slot(gv), view, proj, campos, tan_fovx, tan_fovy, focal_x, focal_y, W, H,
+                                             gx, gy, scale_modifier, gv.header, ranges, T,
+                                             (uint32_t)sw.rect_mode | (sw.hit_list ? 0x100u : 0u));
 }
 
 // One 256-byte device block per DEVICE for the whole process (allocated on first use, kept): the flag word of
@@ -397,6 +438,7 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
                 const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                 float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    const Switches sw = resolve_switches();
     const int W = width, H = height;
     if (P < 0 || W <= 0 || H <= 0) return fail(SGR_E_INVALID, "P, width and height must be positive");
     const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
@@ -440,7 +482,6 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
     uint32_t* host_vals = nullptr;
     const uint32_t* order = nullptr;
     char* bbase = nullptr;
-    size_t have_bytes = 0;
     static thread_local size_t r_hint = 0;
 
     // ---- lazy mode (sgr_set_lazy): what the previous lazy forward of this thread left to check
@@ -474,25 +515,54 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
             r_hint = 0;
         }
     }
-    const bool lazy = lazy_on() && r_hint > 0;
-    const bool tile_sort = tile_sort_on() && !lazy_on();  // (the lazy mode keeps the default chain: list_index())
-    const int rmode = rect_mode();
+    const bool lazy = sw.lazy_mode && r_hint > 0;
     // what the list is made of, in index order: {count, rect} records of 8 bytes, or (marked-list mode) 16-byte records whose
     // first half is the reference's count + rect and whose second half is the live part
-    const int aux16 = rmode == 3 ? 1 : 0;
+    const int aux16 = sw.rect_mode == 3 ? 1 : 0;
     const uint2* aux_emit = aux16 ? reinterpret_cast<const uint2*>(gv.aux_ref) : gv.aux;
+
+    // The two front ends share their launches: camera pack + preprocess, then -- behind the read-back, which each of them
+    // queues its own way -- the depth sort + scan.
+    const auto preprocess = [&]() -> int {
+        prof_begin(0, stream);
+        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, iv.ranges, (int)T, sw, stream);
+        SGR_STAGE("pack_camera");
+        sgr_launch_preprocess(P, D, M, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp,
+                              cam_slot(gv), gv, radii_ptr, prefiltered, sw.pre_stage(P), sw.rect_mode, stream);
+        SGR_STAGE("preprocess");
+        prof_end(stream);
+        return 0;
+    };
+    // Depth pre-sort of the P Gaussians, then K4: scan of tiles_touched in that order.  27 key bits: 3 passes of 9 bits while
+    // the launches are latency-bound, 4 of 7 bits -- longer store runs -- from 750 k Gaussians on (sgr_scan_sort.hip); 32 bits
+    // = 4 passes of 8 once a depth beyond 13 107 has been seen.  The ids are not materialised before the sort: its first pass
+    // takes the element index as the value, its last one carries every Gaussian's {tiles_touched, tile rect} into depth order
+    // (ONE fused 8-byte gather instead of three through `order`: 0.6 GB each at 5 M Gaussians, rocprofv3 FETCH_SIZE).  The
+    // scan's second sequence, in index order, gives every Gaussian's first partial-gradient row of the backward
+    // (SgrGeomView::u0); its last step -- the offsets of the individual Gaussians -- is done by the duplicate kernel.
+    // TILE_SORT (sgr_tile_sort.hip): no depth pre-sort -- the instances are emitted in index order and every tile's list is
+    // sorted by depth in LDS after the tile sort; both scan sequences are index order.
+    const auto depth_sort_scan = [&]() -> int {
+        prof_begin(1, stream);
+        order = nullptr;
+        const uint2* scanned = aux_emit;
+        if (!sw.tile_sort) {
+            const int dcur = sgr_launch_sort_pairs32(gv.dkeys, gv.dvals, (uint32_t)P, wide_depth ? 32 : SGR_DEPTH_KEY_BITS, gv.dhist,
+                                                     gv.scan_tmp, stream, true, aux_emit, gv.aux_sorted, P < depth9_max_p() ? 9 : 8, aux16);
+            order = gv.dvals[dcur];
+            scanned = gv.aux_sorted;
+        }
+        sgr_launch_scan_head(reinterpret_cast<const uint32_t*>(scanned), reinterpret_cast<const uint32_t*>(gv.aux), (size_t)P,
+                             aux16 ? 4 : 2, gv.scan_tmp, gv.sub_sums, stream, 2);
+        SGR_STAGE("depth_sort+scan");
+        prof_end(stream);
+        return 0;
+    };
 
     int R = 0;
     uint32_t cap = 0;  // lazy: slots of the instance list
     if (lazy) {
-        prof_begin(0, stream);
-        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, iv.ranges, (int)T, rmode, stream);
-        SGR_STAGE("pack_camera");
-        sgr_launch_preprocess(P, D, M, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp,
-                              cam_slot(gv), gv, radii_ptr, prefiltered, (switches() & 64) != 0 || P >= pre_stage_min_p(),
-                              rmode, stream);
-        SGR_STAGE("preprocess");
-        prof_end(stream);
+        if (const int rc = preprocess()) return rc;
         host_vals = pinned_pair(1);
         hipEvent_t landed = readback_event(1);
         if (!host_vals || !landed) return fail(SGR_E_HIP, "pinned readback slot / event creation failed");
@@ -506,122 +576,56 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
         t_lazy.landed = landed;
         t_lazy.wide = wide_depth;
         t_lazy.cap = 0x7fffffffu;  // (set below; until then "no overflow")
-        prof_begin(1, stream);
-        const int dcur = sgr_launch_sort_pairs32(gv.dkeys, gv.dvals, (uint32_t)P, wide_depth ? 32 : SGR_DEPTH_KEY_BITS, gv.dhist,
-                                                 gv.scan_tmp, stream, true, aux_emit, gv.aux_sorted, P < depth9_max_p() ? 9 : 8, aux16);
-        order = gv.dvals[dcur];
-        sgr_launch_scan_head(reinterpret_cast<const uint32_t*>(gv.aux_sorted), reinterpret_cast<const uint32_t*>(gv.aux), (size_t)P,
-                             aux16 ? 4 : 2, gv.scan_tmp, gv.sub_sums, stream, 2);
-        SGR_STAGE("depth_sort+scan");
-        prof_end(stream);
-        {   // capacity on the coarse ladder of the blocking path (consecutive calls ask for the same block size)
-            size_t hq = r_hint, step = 1;
-            while ((step << 1) <= hq) step <<= 1;
-            step = std::max<size_t>(step >> 4, 1024);
-            hq = (hq + step - 1) / step * step;
-            cap = (uint32_t)std::min<size_t>(hq, 0x7fffffffu);
-        }
+        if (const int rc = depth_sort_scan()) return rc;
+        cap = binning_ladder(r_hint);  // (consecutive calls ask for the same block size)
         bbase = binning_buffer(sgr_binning_bytes((int)cap), binning_user);
         if (!bbase) return fail(SGR_E_ALLOC, "binning buffer allocation failed");
         R = (int)cap;  // what the caller hands to sgr_backward: it sizes the same carving there
         t_lazy.cap = cap;
-    }
-    for (int attempt = 0; attempt < 2 && !lazy; attempt++) {
-        prof_begin(0, stream);
-        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, iv.ranges, (int)T, rmode, stream);
-        SGR_STAGE("pack_camera");
-
-        sgr_launch_preprocess(P, D, M, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp,
-                              cam_slot(gv), gv, radii_ptr, prefiltered,
-                              // SH rows staged through LDS (half a wave's rows at a time) or read per lane: bit-identical forms
-                              // (tests); the staged one wins once the launch is deep enough to be throughput-bound -- measured
-                              // 346 vs 360 us at 5 M Gaussians, 98.8 vs 90.2 us at 1 M -- so it is chosen by P (switch bit 6
-                              // forces it, SGR_PRE_STAGE_MIN_P moves the threshold)
-                              (switches() & 64) != 0 || P >= pre_stage_min_p(),
-                              // tile rects: the reference's 3-sigma squares cut down to the tiles the Gaussian can reach
-                              // alpha >= 1/255 in (sgr_preprocess.hip: 2 = bounding box + tile mask, 1 = bounding box only,
-                              // switch bit 11); switch bit 10 keeps the reference's rects
-                              rmode, stream);
-        SGR_STAGE("preprocess");
-        prof_end(stream);
-
-        // K5 first: num_rendered (header[4], summed by the preprocess kernel) and the prefilter flag (header[0]) go to
-        // pinned host memory in ONE 24-byte copy.  The host only waits for THAT copy (an event), after the depth sort and
-        // the scan have been queued behind it: while it wakes up, allocates the binning buffer and queues the dozen short
-        // binning kernels, the GPU is busy with the ~0.15 ms of sort + scan instead of idling (rocprofv3 kernel trace:
-        // ~0.2 ms of gaps per forward with the wait placed after the scan, as rasterizer_impl.cu:281 has it).
-        host_vals = pinned_pair();
-        hipEvent_t landed = readback_event();
-        if (!host_vals || !landed) return fail(SGR_E_HIP, "pinned readback slot / event creation failed");
-        // the words carry a value the device never writes, so that the host can see them arrive (wait_for_readback);
-        // header[2] = "a depth beyond the 27-bit sort keys" rides along
-        host_vals[0] = host_vals[2] = host_vals[4] = host_vals[5] = SGR_READBACK_PENDING;
-        SGR_HIP(hipMemcpyAsync(host_vals, gv.header, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        SGR_HIP(hipEventRecord(landed, stream));
-        // an error return between here and the wait must not leave this copy in flight: the next forward of this thread would
-        // take its late arrival for its own read-back
-        struct ReadbackDrain {
-            hipEvent_t ev;
-            ~ReadbackDrain() { if (ev) (void)hipEventSynchronize(ev); }
-        } drain{landed};
-
-        // Depth pre-sort of the P Gaussians (27 key bits: 3 x 9 or 4 x 7 bits over P elements; 32 bits = 4 passes of 8 when a
-        // depth beyond 13 107 has been seen), then K4: scan of tiles_touched in that order.
-        prof_begin(1, stream);
-        // (the ids are not materialised before the sort: its first pass takes the element index as the value; its last
-        // pass also carries every Gaussian's {tiles_touched, tile rect} into depth order -- ONE fused 8-byte gather instead
-        // of three per-stage gathers through `order`: at 5 M Gaussians those read 0.6 GB each, rocprofv3 FETCH_SIZE)
-        // (27 bits: 3 passes of 9 bits while the launches are latency-bound, 4 passes of 7 bits -- longer store runs -- from
-        // 750 k Gaussians on: sgr_scan_sort.hip)
-        if (tile_sort) {
-            // per-tile sort form (switch bit 12, sgr_tile_sort.hip): no depth pre-sort -- the instances are emitted in index
-            // order and every tile's list is sorted by depth in LDS after the tile sort; both scan sequences are index order
-            order = nullptr;
-            sgr_launch_scan_head(reinterpret_cast<const uint32_t*>(aux_emit), reinterpret_cast<const uint32_t*>(gv.aux), (size_t)P,
-                                 aux16 ? 4 : 2, gv.scan_tmp, gv.sub_sums, stream, 2);
-        } else {
-        const int dcur = sgr_launch_sort_pairs32(gv.dkeys, gv.dvals, (uint32_t)P, wide_depth ? 32 : SGR_DEPTH_KEY_BITS, gv.dhist,
-                                                 gv.scan_tmp, stream, true, aux_emit, gv.aux_sorted, P < depth9_max_p() ? 9 : 8, aux16);
-        order = gv.dvals[dcur];
-        // (second sequence of the same launches: the exclusive scan in index order = every Gaussian's first partial-gradient
-        // row of the backward, SgrGeomView::u0)
-        // (the scan's last step -- offsets of the individual Gaussians -- is done by the duplicate kernel, which needs them:
-        // round 4 ran a third launch that wrote them to an array)
-        sgr_launch_scan_head(reinterpret_cast<const uint32_t*>(gv.aux_sorted), reinterpret_cast<const uint32_t*>(gv.aux), (size_t)P,
-                             aux16 ? 4 : 2, gv.scan_tmp, gv.sub_sums, stream, 2);
-        }
-        SGR_STAGE("depth_sort+scan");
-        prof_end(stream);
-        // The window between "R is known" and "the GPU runs out of queued work" is only the ~0.12 ms of sort + scan
-        // above, and the allocation callback (a Python call into the torch allocator in the shipped binding) is the
-        // slowest thing in it.  So the binning buffer is requested BEFORE the wait, sized for the previous forward's R
-        // + 25 % (per host thread); only if that turns out too small is it requested again with the exact size.  The
-        // carving below depends on R alone, so a larger buffer is simply partly unused.
-        have_bytes = 0;
-        bbase = nullptr;
-        if (r_hint > 0) {
-            // the hint decays a little every call; request sizes on a coarse ladder (steps of 1/16 of the next lower power of
-            // two) so that consecutive calls ask the caller's caching allocator for the SAME block size instead of a new,
-            // slightly smaller one each time (every new size is a device allocation: tens of ms on some hosts)
-            size_t hq = r_hint;
-            {
-                size_t step = 1;
-                while ((step << 1) <= hq) step <<= 1;
-                step = std::max<size_t>(step >> 4, 1024);
-                hq = (hq + step - 1) / step * step;
+    } else {
+        size_t have_bytes = 0;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            if (const int rc = preprocess()) return rc;
+            // K5 first: num_rendered (header[4], summed by the preprocess kernel) and the prefilter flag (header[0]) go to
+            // pinned host memory in ONE 24-byte copy.  The host only waits for THAT copy (an event), after the depth sort and
+            // the scan have been queued behind it: while it wakes up, allocates the binning buffer and queues the dozen short
+            // binning kernels, the GPU is busy with the ~0.15 ms of sort + scan instead of idling (rocprofv3 kernel trace:
+            // ~0.2 ms of gaps per forward with the wait placed after the scan, as rasterizer_impl.cu:281 has it).
+            host_vals = pinned_pair();
+            hipEvent_t landed = readback_event();
+            if (!host_vals || !landed) return fail(SGR_E_HIP, "pinned readback slot / event creation failed");
+            // the words carry a value the device never writes, so that the host can see them arrive (wait_for_readback);
+            // header[2] = "a depth beyond the 27-bit sort keys" rides along
+            host_vals[0] = host_vals[2] = host_vals[4] = host_vals[5] = SGR_READBACK_PENDING;
+            SGR_HIP(hipMemcpyAsync(host_vals, gv.header, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            SGR_HIP(hipEventRecord(landed, stream));
+            // an error return between here and the wait must not leave this copy in flight: the next forward of this thread
+            // would take its late arrival for its own read-back
+            struct ReadbackDrain {
+                hipEvent_t ev;
+                ~ReadbackDrain() { if (ev) (void)hipEventSynchronize(ev); }
+            } drain{landed};
+            if (const int rc = depth_sort_scan()) return rc;
+            // The window between "R is known" and "the GPU runs out of queued work" is only the ~0.12 ms of sort + scan
+            // above, and the allocation callback (a Python call into the torch allocator in the shipped binding) is the
+            // slowest thing in it.  So the binning buffer is requested BEFORE the wait, sized for the previous forward's R
+            // + 25 % (per host thread; the hint decays a little every call); only if that turns out too small is it
+            // requested again with the exact size.  The carving below depends on R alone, so a larger buffer is simply
+            // partly unused.
+            have_bytes = 0;
+            bbase = nullptr;
+            if (r_hint > 0) {
+                have_bytes = sgr_binning_bytes((int)binning_ladder(r_hint));
+                bbase = binning_buffer(have_bytes, binning_user);
+                if (!bbase) return fail(SGR_E_ALLOC, "binning buffer allocation failed");
             }
-            have_bytes = sgr_binning_bytes((int)std::min<size_t>(hq, 0x7fffffffu));
-            bbase = binning_buffer(have_bytes, binning_user);
-            if (!bbase) return fail(SGR_E_ALLOC, "binning buffer allocation failed");
-        }
-        SGR_HIP(wait_for_readback(host_vals, landed));  // the one host wait of the forward
-        drain.ev = nullptr;
+            SGR_HIP(wait_for_readback(host_vals, landed));  // the one host wait of the forward
+            drain.ev = nullptr;
 
-        if (!(host_vals[2] & 1u) || wide_depth || tile_sort) break;  // (the per-tile sort reads the far-depth flag on the device)
-        wide_depth = true;
-        wide_left = 64;
-    }
-    if (!lazy) {
+            if (!(host_vals[2] & 1u) || wide_depth || sw.tile_sort) break;  // (the per-tile sort reads the far-depth flag on the device)
+            wide_depth = true;
+            wide_left = 64;
+        }
         if (host_vals[0] & 1u)
             return fail(SGR_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
         // (host_vals[5], what num_rendered would be with the reference's rects, is reporting only -- export 17, best effort: it
@@ -642,9 +646,9 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
     // (also with R == 0: the kernel finishes the index-order scan, SgrGeomView::u0, which the exports read)
     prof_begin(2, stream);
     SgrGeomView gv_dup = gv;
-    if (tile_sort) gv_dup.aux_sorted = const_cast<uint2*>(aux_emit);  // index-order emission: "depth order" is the identity
-    const int key16 = tile_key16(T);
-    sgr_launch_duplicate(P, gv_dup, order, gv.scan_tmp, gv.sub_sums, bv.keys[0], key16, bv.vals[0], gx, cap, rmode == 3 ? 1 : 0, stream);
+    if (sw.tile_sort) gv_dup.aux_sorted = const_cast<uint2*>(aux_emit);  // index-order emission: "depth order" is the identity
+    const int key16 = sw.key16(T);
+    sgr_launch_duplicate(P, gv_dup, order, gv.scan_tmp, gv.sub_sums, bv.keys[0], key16, bv.vals[0], gx, cap, aux16, stream);
     SGR_STAGE("duplicate");
     prof_end(stream);
     if (R > 0) {
@@ -662,26 +666,22 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
         prof_begin(4, stream);
         sgr_launch_tile_ranges(R, bv.keys[cur], key16, iv.ranges, bv.touched, lazy ? (uint32_t)T : 0xffffffffu, stream);
         SGR_STAGE("tile_ranges");
-        if (tile_sort) {
+        if (sw.tile_sort) {
             // every tile's list (ascending id so far) into (depth, id) order: a stable radix sort on the depth keys in LDS
             sgr_launch_tile_sort((int)T, iv.ranges, bv.vals[cur], bv.vals[cur ^ 1], gv.dkeys[0], gv.header, bv.keys[cur ^ 1], bv.tkeys, stream);
             SGR_STAGE("tile_sort");
         }
         prof_end(stream);
     }
-    const int lcur = tile_sort ? (cur ^ 1) : cur;  // which vals[] holds the final list (list_index())
+    const int lcur = sw.tile_sort ? (cur ^ 1) : cur;  // which vals[] holds the final list (list_index())
     prof_begin(5, stream);
-    const bool cull = !(switches() & 1);
-    // Tile order of the two blend launches: decided per frame on the device (sgr_tile_order_kernel: longest list first when
-    // the longest list is more than 2.5 x the mean, else the XCD-aware supertile order); switch bit 14 forces longest-first,
-    // bit 15 keeps the supertile order without looking (no extra launch: the round-5 behaviour)
-    const bool lpt = (switches() & 32768) == 0;
-    if (lpt) {
-        sgr_launch_tile_order(iv.ranges, (int)T, (switches() & 16384) ? 1 : 0, stream);
+    if (sw.lpt) {
+        sgr_launch_tile_order(iv.ranges, (int)T, sw.lpt_force ? 1 : 0, stream);
         SGR_STAGE("tile_order");
     }
-    sgr_launch_blend_fwd(cull, (switches() & 128) != 0, gx, lpt ? -gy : gy, iv.ranges, bv.vals[lcur], W, H, S, gv.rec, semantics,
-                         background, out_color, out_depth, out_alpha, out_semantic, iv.n_contrib, bv.hit4, hit_list_on() ? bv.hlist : nullptr, iv.n_contrib_k, stream);
+    sgr_launch_blend_fwd(sw.cull, sw.exact, gx, sw.lpt ? -gy : gy, iv.ranges, bv.vals[lcur], W, H, S, gv.rec, semantics,
+                         background, out_color, out_depth, out_alpha, out_semantic, iv.n_contrib, bv.hit4,
+                         sw.hit_list ? bv.hlist : nullptr, iv.n_contrib_k, stream);
     SGR_STAGE("blend_fwd");
     prof_end(stream);
     return R;
@@ -693,9 +693,9 @@ static int sorted_index(int width, int height) {
     const int end_bit = (int)getHigherMsb((uint32_t)(gx * gy));  // the tile sort only; depth order comes from the emission order
     return sgr_sort_pass_count(end_bit) & 1;
 }
-// ... and which vals[] holds the final instance list: the per-tile sort form (switch bit 12) writes it to the other one.
-// (A forward and the backward / exports over its buffers must run under the same switch, like every other switch.)
-static int list_index(int width, int height) { return sorted_index(width, height) ^ ((tile_sort_on() && !lazy_on()) ? 1 : 0); }
+// ... and which vals[] holds the final instance list: the per-tile sort form (TILE_SORT) writes it to the other one.
+// (A forward and the backward / exports over its buffers must run under the same switch, include/sgr.h.)
+static int list_index(int width, int height, const Switches& sw) { return sorted_index(width, height) ^ (sw.tile_sort ? 1 : 0); }
 
 int sgr_backward(int P, int D, int M, int R, int S, const float* background, int width, int height,
                  const float* means3D, const float* shs, const float* colors_precomp, const float* semantics,
@@ -724,6 +724,7 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
                     float* dL_dsemantic, sgr_alloc_fn scratch, void* scratch_user, int debug, void* stream_,
                     const sgr_backward_extras* extras) {
     hipStream_t stream = (hipStream_t)stream_;
+    const Switches sw = resolve_switches();
     SgrStatSink sink;
     if (extras && (extras->xyz_gradient_accum || extras->denom || extras->max_radii2D)) {
         if (!extras->xyz_gradient_accum || !extras->denom || !extras->max_radii2D)
@@ -782,13 +783,12 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
     const SgrImgView iv = sgr_img_carve(image_buffer, N, T);
     const int* radii_ptr = radii ? radii : gv.internal_radii;
     const int stride = sgr_partial_row_stride(S);
-    // Which blend backward runs.  Default: the LDS-staged kernel (sgr_blend_bwd.hip).  Switch bit 8 (SGR_SW=1) selects the
+    // Which blend backward runs.  Default: the LDS-staged kernel (sgr_blend_bwd.hip).  USE_SW (SGR_SW=1) selects the
     // scalar walk (sgr_blend_bwd_sw.hip; S = 0 with the hit record, cull, DPP reduction and deterministic combine on): it
     // writes FOUR rows per (tile, instance), one per quadrant.  A second design that was built, is parity-tested and
     // measured 11 % slower per step: both kernels sit at the VALU issue bound of the same per-visit
     // arithmetic, and the per-quadrant rows cost the row sum more than the barriers cost the LDS kernel.
-    const int sw_all = switches();
-    const bool quad = SGR_WITH_VARIANTS && S == 0 && R > 0 && (sw_all & 256) != 0 && (sw_all & (1 | 2 | 4 | 8 | 16)) == 0;
+    const bool quad = sw.quad && S == 0 && R > 0;
     // scratch = [P float4: conic + depth terms between the two per-Gaussian stages][R (or 4 R) partial rows]
     const size_t cd_bytes = sgr_align_up((size_t)P * sizeof(float4), 256);
     const size_t bytes = sgr_align_up((size_t)R * (quad ? 4u : 1u) * stride * sizeof(float), 256);
@@ -800,46 +800,45 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
     // by the forward's tile-ranges launch; the rows a backward writes are a function of the forward's hit record alone,
     // so repeated backwards over one forward re-mark the same bytes.  The A/B switches that change the visited set
     // (no cull / no hit record) clear it explicitly, before and after.
+    // (the scalar walk leaves quadrant MASKS in these bytes and the LDS kernel ones: a scalar-walk backward clears them
+    // before and after itself, so that the two kernels can follow each other over one forward)
+    const bool odd_set = !sw.cull || !sw.use_hits || quad;
     uint8_t* touched = nullptr;
     if (R > 0) {
         const SgrBinView bv = sgr_bin_carve(binning_buffer, (size_t)R);
         touched = bv.touched;
-        const int cur = list_index(W, H);
-        // (the scalar walk leaves quadrant MASKS in these bytes and the LDS kernel ones: a scalar-walk backward clears them
-        // before and after itself, so that the two kernels can follow each other over one forward)
-        const bool odd_set = (switches() & (1 | 8)) != 0 || quad;
+        const int cur = list_index(W, H, sw);
         prof_begin(6, stream);
         if (odd_set) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
         prof_end(stream);
         prof_begin(7, stream);
-        const int sw = switches();
-        const bool cull = !(sw & 1), dpp = !(sw & 2), det = !(sw & 4);
-        // the forward's record of which (quadrant, instance) pairs blended at all; switch 8: the kernel redoes the
+        // the forward's record of which (quadrant, instance) pairs blended at all; NO_HITS: the kernel redoes the
         // geometric cull instead (A/B and tests: the two walks must give bit-identical gradients)
-        const uint8_t* hits = (sw & 8) ? nullptr : bv.hit4;
+        const uint8_t* hits = sw.use_hits ? bv.hit4 : nullptr;
 #if SGR_WITH_VARIANTS
         if (quad)
-            sgr_launch_blend_bwd_sw((sw & 128) != 0, gx, gy, iv.ranges, bv.vals[cur], W, H, background, gv.rec, gv.u0, gv.tmask, alphas,
+            sgr_launch_blend_bwd_sw(sw.exact, gx, gy, iv.ranges, bv.vals[cur], W, H, background, gv.rec, gv.u0, gv.tmask, alphas,
                                     iv.n_contrib, bv.hit4, dL_dpix, dL_dpix_depth, dL_dalphas, partials, stride, touched, stream);
         else
 #endif
-            sgr_launch_blend_bwd(cull, dpp, det, (sw & 16) != 0, (sw & 128) != 0, gx, (sw & 32768) ? gy : -gy, iv.ranges, bv.vals[cur], W, H, S, background, gv.rec, gv.u0, gv.tmask, semantics,
+            // (-gy: the tiles in the frame's order, the flag word behind the ranges -- the order the forward's blend walked)
+            sgr_launch_blend_bwd(sw.cull, sw.dpp, sw.det, sw.v2, sw.exact, gx, -gy, iv.ranges, bv.vals[cur], W, H, S, background, gv.rec, gv.u0, gv.tmask, semantics,
                                  alphas, iv.n_contrib, hits, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_semantic, partials,
-                                 touched, (uint32_t)R, (SGR_HLIST && !(sw & 65536)) ? bv.hlist : nullptr, iv.n_contrib_k,
+                                 touched, (uint32_t)R, sw.hlist_walk ? bv.hlist : nullptr, iv.n_contrib_k,
                                  gv.header + 7, stream);
         SGR_STAGE("blend_bwd");
         prof_end(stream);
     }
     prof_begin(8, stream);
-    const int ev_failed = ((switches() & 128) ? sgr_launch_gauss_bwd_strict : sgr_launch_gauss_bwd)(
+    const int ev_failed = (sw.exact ? sgr_launch_gauss_bwd_strict : sgr_launch_gauss_bwd)(
         P, D, M, S, means3D, radii_ptr, shs, scales, rotations, cov3D_precomp, cam_slot(gv), gv, partials, stride, touched, cd,
         dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dsemantic, sink, quad ? 1 : 0,
-        (switches() & 128) ? 1 : 0, W, H, extras ? (hipEvent_t)extras->color_ready_event : nullptr, (switches() & 512) ? 1 : 0,
+        sw.exact ? 1 : 0, W, H, extras ? (hipEvent_t)extras->color_ready_event : nullptr, sw.rs_wave ? 1 : 0,
         (uint32_t)R, extras ? extras->masked_color_out : nullptr, skip_sh, stream);
     SGR_STAGE("gauss_bwd");
     prof_end(stream);
     if (ev_failed) return fail(SGR_E_HIP, "hipEventRecord(color_ready_event) failed: is it a valid event of this device?");
-    if (touched && ((switches() & (1 | 8)) != 0 || quad)) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
+    if (touched && odd_set) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
     return 0;
 }
 
@@ -906,11 +905,11 @@ int sgr_profile_host_wait_us(int reset) {
 int sgr_has_variants(void) { return SGR_WITH_VARIANTS ? 1 : 0; }
 
 int sgr_test_switches(int mask) {
-    const int prev = switches() | ((SGR_WITH_VARIANTS && sgr_sort_get_one_sweep()) ? 32 : 0);
+    const int prev = switches() | ((SGR_WITH_VARIANTS && sgr_sort_get_one_sweep()) ? SGR_SW_USE_ONESWEEP : 0);
     if (mask >= 0) {
         if (!SGR_WITH_VARIANTS) mask &= ~SGR_VARIANT_BITS;
-        g_switches.store(mask & ~32, std::memory_order_relaxed);
-        sgr_sort_set_one_sweep((mask >> 5) & 1);
+        g_switches.store(mask & ~SGR_SW_USE_ONESWEEP, std::memory_order_relaxed);
+        sgr_sort_set_one_sweep((mask & SGR_SW_USE_ONESWEEP) != 0);
     }
     return prev;
 }
@@ -1066,6 +1065,7 @@ __global__ void sgr_export_kernel(int which, int P, SgrGeomView gv, void* dst) {
 int sgr_export_internal(int which, int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
                         char* image_buffer, void* dst, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    const Switches sw = resolve_switches();
     const int debug = 1;
     const int gx = (width + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (height + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
     const size_t N = (size_t)width * height, T = (size_t)gx * gy;
@@ -1094,14 +1094,14 @@ int sgr_export_internal(int which, int P, int R, int width, int height, char* ge
         const SgrBinView bv = sgr_bin_carve(binning_buffer, (size_t)R);
         if (which == 19) { SGR_HIP(hipMemcpyAsync(dst, bv.hlist, (size_t)R * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
         if (which == 15) { SGR_HIP(hipMemcpyAsync(dst, bv.hit4, (size_t)R, hipMemcpyDeviceToDevice, stream)); return 0; }
-        const int cur = sorted_index(width, height), lcur = list_index(width, height);
+        const int cur = sorted_index(width, height), lcur = list_index(width, height, sw);
         if (which == 8) {
             SGR_HIP(hipMemcpyAsync(dst, bv.vals[lcur], (size_t)R * 4, hipMemcpyDeviceToDevice, stream));
             sgr_strip_dead_kernel<<<(R + 255) / 256, 256, 0, stream>>>((uint32_t*)dst, R);  // marked-list mode: bit 31 = cannot blend
             SGR_STAGE("export point_list");
         } else {
             const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
-            sgr_launch_compose_keys(R, bv.keys[cur], tile_key16(T), bv.vals[lcur], gv.rec, (uint64_t*)dst, stream);
+            sgr_launch_compose_keys(R, bv.keys[cur], sw.key16(T), bv.vals[lcur], gv.rec, (uint64_t*)dst, stream);
             SGR_STAGE("export keys");
         }
         return 0;

@@ -290,8 +290,8 @@ __device__ __forceinline__ bool sgr_xcd_tile(uint32_t b, uint32_t gx, uint32_t g
 
 // Tile of workgroup b.  gy >= 0: the XCD-aware supertile order above.  gy < 0: the grid is |gy| rows high and the frame's
 // tile-order block sits behind ranges[T] -- T tile ids sorted by descending list length, then ONE flag word: 1 = walk the
-// tiles in that LONGEST-FIRST order, 0 = the lists are even enough, use the supertile order (sgr_tile_order_kernel decides
-// per frame).  Heaviest tiles first shortens the ragged end of a launch whose tiles are very unequal -- a street scene: empty
+// tiles in that LONGEST-FIRST order, 0 = the lists are even enough, use the supertile order (sgr_pack_camera_kernel clears
+// it, sgr_tile_order_kernel decides per frame).  Heaviest tiles first shortens the ragged end of a launch whose tiles are very unequal -- a street scene: empty
 // sky next to actors, -10 % of the step -- at the price of the L2 locality of neighbouring tiles, which is what an even
 // scene lives on (+1 %): measured, DESIGN.md section 3.
 __device__ __forceinline__ bool sgr_wg_tile(uint32_t b, int gx, int gy, const uint2* __restrict__ ranges, uint32_t& tx, uint32_t& ty) {

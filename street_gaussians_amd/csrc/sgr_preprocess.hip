@@ -564,7 +564,7 @@ void sgr_launch_filter(int P, const float* means3D, const float* scales, const f
 }
 
 // bsum / sub: what sgr_launch_scan_head left for the two count sequences (aux_sorted in depth order, aux in index order)
-// key16: the tile keys are uint16_t (sgr_api.hip: tile_key16) -- `keys` points at the same buffer either way
+// key16: the tile keys are uint16_t (sgr_api.hip: Switches::key16) -- `keys` points at the same buffer either way
 void sgr_launch_duplicate(int P, const SgrGeomView& gv, const uint32_t* order, const uint32_t* bsum, const uint32_t* sub,
                           void* keys, int key16, uint32_t* vals, int gx, uint32_t cap, int marks, hipStream_t s) {
     if (P <= 0) return;

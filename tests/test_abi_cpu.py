@@ -90,3 +90,77 @@ def test_host_only_entry_points_answer_without_a_gpu(lib):
     assert b"lazy" in lib.sgr_last_error()
     lib.sgr_set_lazy(prev)
     assert lib.sgr_set_lazy(-1) == prev
+
+
+SW_ENUM = re.compile(r"^\s*SGR_SW_(\w+)\s*=\s*1\s*<<\s*(\d+)\s*,?", re.M)
+VARIANT_BITS = (1 << 4) | (1 << 5) | (1 << 8) | (1 << 9)  # USE_V2, USE_ONESWEEP, USE_SW, USE_RS_WAVE
+
+
+def _switch_enum():
+    return [(name, int(bit)) for name, bit in SW_ENUM.findall(open(os.path.join(ROOT, "include", "sgr.h")).read())]
+
+
+def test_switch_enum_covers_every_bit_and_the_binding_agrees():
+    """The SGR_SW_* enum of include/sgr.h names bits 0..18, one entry each, and street_gaussians_amd._C carries the same
+    names (without the prefix) with the same values -- bench.py, the tests and the tools use the Python names."""
+    from street_gaussians_amd import _C
+    enum = _switch_enum()
+    assert sorted(bit for _, bit in enum) == list(range(19)), enum
+    assert len({name for name, _ in enum}) == len(enum)
+    for name, bit in enum:
+        assert getattr(_C, name) == 1 << bit, name
+    # the names the callers use, every one of them in the enum
+    assert {name for name, _ in enum} == {"NO_CULL", "NO_DPP", "NO_DET", "NO_HITS", "USE_V2", "USE_ONESWEEP", "PRE_STAGE_SH",
+                                          "EXACT", "USE_SW", "USE_RS_WAVE", "REF_RECT", "NO_TILE_MASK", "TILE_SORT",
+                                          "REF_RECT_PLAIN", "LPT", "NO_LPT", "NO_HLIST", "HLIST_ALWAYS", "KEY32"}
+
+
+def test_test_switches_round_trips_every_bit(lib):
+    """sgr_test_switches sets and reports every bit; a library without the A/B variants drops their bits (4, 5, 8, 9).
+    Host state only: no HIP call is made."""
+    variants = lib.sgr_has_variants() != 0
+    prev = lib.sgr_test_switches(-1)
+    try:
+        for bit in range(19):
+            m = 1 << bit
+            lib.sgr_test_switches(m)
+            want = m if (variants or not m & VARIANT_BITS) else 0
+            assert lib.sgr_test_switches(-1) == want, bit
+        lib.sgr_test_switches(0)
+        assert lib.sgr_test_switches(-1) == 0
+        everything = (1 << 19) - 1
+        lib.sgr_test_switches(everything)
+        assert lib.sgr_test_switches(-1) == (everything if variants else everything & ~VARIANT_BITS)
+    finally:
+        lib.sgr_test_switches(prev)
+    assert lib.sgr_test_switches(-1) == prev
+
+
+# every environment name of the initial mask, aliases included (SGR_ONESWEEP is the radix sort's own flag: bit 5)
+SWITCH_ENV = {"SGR_NO_CULL": 0, "SGR_NO_DPP": 1, "SGR_NO_DET": 2, "SGR_NO_HITS": 3, "SGR_V2": 4, "SGR_ONESWEEP": 5,
+              "SGR_PRE_STAGE": 6, "SGR_EXACT": 7, "SGR_SW": 8, "SGR_SW8": 8, "SGR_RS_WAVE": 9, "SGR_SW9": 9,
+              "SGR_REF_RECT": 10, "SGR_NO_TILE_MASK": 11, "SGR_TILE_SORT": 12, "SGR_REF_RECT_PLAIN": 13, "SGR_LPT": 14,
+              "SGR_NO_LPT": 15, "SGR_NO_HLIST": 16, "SGR_HLIST_ALWAYS": 17, "SGR_KEY32": 18}
+
+
+def test_switch_environment_names_set_the_initial_mask(lib):
+    """A fresh process with exactly one of the names set (to 1) starts with exactly that bit -- or with none, for a variant bit
+    in a library without the variants; with none of them set the mask starts at 0 (`_C.test_switches(-1)`: host only)."""
+    import subprocess
+    import sys
+    from concurrent.futures import ThreadPoolExecutor
+    variants = lib.sgr_has_variants() != 0
+    base = {k: v for k, v in os.environ.items() if k not in SWITCH_ENV}
+    code = "from street_gaussians_amd import _C; print(_C.test_switches(-1))"
+
+    def initial_mask(name):
+        env = dict(base, **({name: "1"} if name else {}))
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (name, r.stderr[-2000:])
+        return int(r.stdout.split()[-1])
+
+    cases = [(None, 0)] + [(name, 1 << bit) for name, bit in SWITCH_ENV.items()]
+    with ThreadPoolExecutor(4) as pool:
+        got = list(pool.map(initial_mask, [name for name, _ in cases]))
+    for (name, m), g in zip(cases, got):
+        assert g == (m if (variants or not m & VARIANT_BITS) else 0), (name, g)

@@ -130,6 +130,74 @@ def test_longest_first_tile_order_changes_nothing(mode):
     assert (n == 0).sum() > 10 and n.max() > 4 * n.mean()  # empty sky tiles and tiles several times the mean
 
 
+def _forward_into_image_buffer(kw, img):
+    """sgr_forward through the ctypes binding with the CALLER's image buffer `img` (uint8, sgr_image_bytes): what
+    _C.rasterize_gaussians does, except that the image buffer callback hands out `img`."""
+    import ctypes as C
+    from street_gaussians_amd import _native
+    dev = torch.device("cuda")
+    t = {k: kw[k].to(dev).float().contiguous() for k in ("means3D", "shs", "semantics", "opacities", "scales", "rotations",
+                                                          "viewmatrix", "projmatrix", "campos", "bg")}
+    P, H, W = t["means3D"].shape[0], kw["image_height"], kw["image_width"]
+    S, M = t["semantics"].shape[1], t["shs"].shape[1]
+    out = dict(color=torch.empty(3, H, W, device=dev), depth=torch.empty(1, H, W, device=dev),
+               alpha=torch.empty(1, H, W, device=dev), semantic=torch.empty(S, H, W, device=dev),
+               radii=torch.empty(P, dtype=torch.int32, device=dev))
+    geom, binning = _C._Grow(dev), _C._Grow(dev)
+    img_cb = _native.ALLOC_FN(lambda nbytes, _user: img.data_ptr() if nbytes <= img.numel() else 0)
+    vp = lambda x: C.c_void_p(x.data_ptr())
+    R = _native.check(_native.lib().sgr_forward(
+        geom.cb, None, binning.cb, None, img_cb, None, P, kw["sh_degree"], M, S, vp(t["bg"]), W, H, vp(t["means3D"]),
+        vp(t["shs"]), None, vp(t["semantics"]), vp(t["opacities"]), vp(t["scales"]), 1.0, vp(t["rotations"]), None,
+        vp(t["viewmatrix"]), vp(t["projmatrix"]), vp(t["campos"]), kw["tanfovx"], kw["tanfovy"], 0, vp(out["color"]),
+        vp(out["depth"]), vp(out["alpha"]), vp(out["semantic"]), vp(out["radii"]), 1, _C._stream(dev)))
+    torch.cuda.synchronize()
+    return dict(out, R=R, geom=geom.tensor, binning=binning.tensor, img=img)
+
+
+def test_backward_walks_the_tiles_in_its_frames_order():
+    """Every forward leaves a valid tile-order flag in its image buffer (sgr_pack_camera_kernel clears it; the tile-order
+    launch sets it when it runs), and the backward follows that flag whatever the switches say by the time it runs.  The
+    image buffer is handed in holding a VALID longest-first block from an earlier frame (a permutation of the tile ids, flag
+    1); a forward under NO_LPT must leave the flag at 0, and a default-switch backward over that frame must give the
+    gradients of a NO_LPT forward + backward bit for bit."""
+    from street_gaussians_amd import _native
+    cam, sc, S = _scene("mid")
+    kw = oracle_kwargs(cam, sc, bg=torch.tensor([0.1, 0.3, 0.2]))
+    wts = syn.loss_weights(cam, S=S)
+    H, W = kw["image_height"], kw["image_width"]
+    N, T = H * W, ((W + 15) // 16) * ((H + 15) // 16)
+    prev = _C.binding()
+    _C.set_binding("ctypes")
+    try:
+        with switches(_C.NO_LPT):
+            ref, _ = raw_forward(kw)
+            g_ref = {k: npy(v).copy() for k, v in raw_backward(kw, ref, wts).items()}
+
+        # sgr_img_carve: n_contrib[N], then (256-byte aligned) the T ranges, the T tile ids of the order block, its flag word
+        img = torch.zeros((_native.lib().sgr_image_bytes(W, H) + 3) // 4 * 4, dtype=torch.uint8, device="cuda")
+        up = lambda a: (a + 255) // 256 * 256
+        ranges_w = (up(up(img.data_ptr()) + 4 * N) - img.data_ptr()) // 4
+        words = img.view(torch.int32)
+        words[ranges_w + 2 * T:ranges_w + 3 * T] = torch.randperm(T, generator=torch.Generator().manual_seed(5)).int().cuda()
+        words[ranges_w + 3 * T] = 1
+        with switches(_C.NO_LPT):
+            res = _forward_into_image_buffer(kw, img)
+        assert res["R"] == ref["R"]
+        ranges = _C.export_internal("ranges", kw["means3D"].shape[0], res["R"], H, W, res["geom"], res["binning"], img)
+        assert torch.equal(words[ranges_w:ranges_w + 2 * T], ranges.view(-1))  # the offsets above are the carve's
+        assert int(words[ranges_w + 3 * T]) == 0, "a NO_LPT forward left the previous frame's tile-order flag behind"
+        for k in ("color", "depth", "alpha", "semantic", "radii"):
+            assert torch.equal(res[k], ref[k]), k
+        with switches(0):
+            g = raw_backward(kw, res, wts)
+            torch.cuda.synchronize()
+        for k, v in g_ref.items():
+            assert np.array_equal(npy(g[k]), v), (k, int((npy(g[k]) != v).sum()))
+    finally:
+        _C.set_binding(prev)
+
+
 @pytest.mark.parametrize("mode", ["default", "strict"])
 def test_32_bit_tile_keys_give_the_same_lists_as_the_16_bit_default(mode):
     """The instance list's tile keys are 16-bit whenever the frame has fewer than 65535 tiles (the tile sort then moves 6
