@@ -29,7 +29,8 @@ SYMBOLS = [
     "sgr_lidar_work_bytes", "sgr_lidar_depth_forward", "sgr_lidar_depth_backward", "sgr_densify_work_bytes", "sgr_densify_plan",
     "sgr_densify_map", "sgr_densify_gather", "sgr_densify_split_children", "sgr_densify_prune_mask",
     "sgr_densify_compact", "sgr_reset_opacity", "sgr_texture_cube_workspace_bytes", "sgr_texture_cube_forward",
-    "sgr_texture_cube_backward", "sgr_adam_span_elems", "sgr_adam_step",
+    "sgr_texture_cube_backward", "sgr_adam_span_elems", "sgr_adam_step", "sgr_sky_workspace_bytes", "sgr_sky_forward",
+    "sgr_sky_backward", "sgr_sky_test_rays", "sgr_test_sort32_count",
 ]
 
 
@@ -137,6 +138,16 @@ def lib():
         L.sgr_texture_cube_forward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp]
         L.sgr_texture_cube_backward.restype = i
         L.sgr_texture_cube_backward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp, vp]
+        L.sgr_sky_workspace_bytes.restype = C.c_size_t
+        L.sgr_sky_workspace_bytes.argtypes = [i, i, i, i, i]
+        L.sgr_sky_forward.restype = i
+        L.sgr_sky_forward.argtypes = [i, i, i, i] + [vp] * 9 + [i, vp, vp, vp]
+        L.sgr_sky_backward.restype = i
+        L.sgr_sky_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
+        L.sgr_sky_test_rays.restype = i
+        L.sgr_sky_test_rays.argtypes = [i, i, vp, vp, vp, vp, i, vp, vp, vp]
+        L.sgr_test_sort32_count.restype = i
+        L.sgr_test_sort32_count.argtypes = [vp, vp, vp, vp, C.c_uint32, i, i, vp, vp, vp, vp]
         L.sgr_adam_span_elems.restype = i
         L.sgr_adam_span_elems.argtypes = []
         L.sgr_adam_step.restype = i

@@ -238,8 +238,10 @@ int sgr_launch_sort_pairs(uint64_t* const keys[2], uint32_t* const vals[2], uint
 // into sorted order, aux_out[sorted position] = aux_in[value]
 int sgr_launch_sort_pairs32(uint32_t* const keys[2], uint32_t* const vals[2], uint32_t n, int end_bit, uint32_t* hist,
                             uint32_t* scan_tmp, hipStream_t s, bool iota = false, const uint2* aux_in = nullptr,
-                            uint2* aux_out = nullptr, int max_bits = 8, int aux16 = 0);  // max_bits: digit width cap, 8 or 9;
-                            // aux16: the aux records are 16 bytes (uint4) instead of 8
+                            uint2* aux_out = nullptr, int max_bits = 8, int aux16 = 0,
+                            const uint32_t* dev_n = nullptr);  // max_bits: digit width cap, 8 or 9;
+                            // aux16: the aux records are 16 bytes (uint4) instead of 8; dev_n: sort only the first *dev_n
+                            // (<= n) pairs, a count read on the device (n still sizes the grids)
 int sgr_launch_sort_pairs16(uint16_t* const keys[2], uint32_t* const vals[2], uint32_t n, int end_bit, uint32_t* hist,
                             uint32_t* scan_tmp, hipStream_t s);
 int sgr_sort_pass_count(int end_bit);  // passes (= buffer flips) of a sort on key bits [0, end_bit)

@@ -133,7 +133,16 @@ void sgr_launch_scan_head(const uint32_t* in, const uint32_t* in2, size_t n, int
 template <typename K, int IPT>
 __global__ void __launch_bounds__(256)
 sgr_sort_hist_kernel(const K* __restrict__ keys, uint32_t n, int shift, uint32_t mask, uint32_t nblocks,
-                     uint32_t* __restrict__ hist) {
+                     uint32_t* __restrict__ hist, const uint32_t* __restrict__ dev_n) {
+    // dev_n: the element count lives on the device (at most n, the host bound the grid is sized by); a block past it
+    // contributes an empty histogram
+    if (dev_n) {
+        n = min(n, *dev_n);
+        if (blockIdx.x * (256u * IPT) >= n) {
+            for (uint32_t d = threadIdx.x; d <= mask; d += 256) hist[(size_t)d * nblocks + blockIdx.x] = 0u;
+            return;
+        }
+    }
     // one private histogram per wave (a quarter of the same-address LDS atomics), merged at the end
     __shared__ uint32_t h[4][512];  // up to 9-bit digits
 #pragma unroll
@@ -213,7 +222,8 @@ sgr_sort_scatter_kernel(const K* __restrict__ kin, const uint32_t* __restrict__ 
                         uint32_t* __restrict__ vout, uint32_t n, int shift, uint32_t nblocks,
                         const uint32_t* __restrict__ hist_scanned, const uint32_t* __restrict__ totals,
                         unsigned long long* __restrict__ status, uint32_t* __restrict__ ticket, uint32_t* __restrict__ err,
-                        uint32_t pass_tag, const uint2* __restrict__ aux_in, uint2* __restrict__ aux_out, int aux16) {
+                        uint32_t pass_tag, const uint2* __restrict__ aux_in, uint2* __restrict__ aux_out, int aux16,
+                        const uint32_t* __restrict__ dev_n) {
     constexpr int NB = 1 << BITS;
     constexpr int BPT = NB > 256 ? NB / 256 : 1;  // bins per thread in the prefix section (9-bit digits: 2)
     static_assert(!(ONE && NB > 256), "the one-sweep form has one status word per thread");
@@ -225,6 +235,10 @@ sgr_sort_scatter_kernel(const K* __restrict__ kin, const uint32_t* __restrict__ 
     __shared__ K sK[ITEMS];
     __shared__ uint32_t sV[ITEMS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!ONE && dev_n) {  // device-side count (three-launch form only): blocks past it have no keys and exit
+        n = min(n, *dev_n);
+        if (blockIdx.x * ITEMS >= n) return;
+    }
     if (ONE && tid == 0) lds4[0] = atomicAdd(ticket, 1u);  // block id in start order: every lower id is already running
     for (int b = tid; b < NB; b += 256) {
 #pragma unroll
@@ -500,14 +514,15 @@ int sgr_sort_pass_count(int end_bit) { return (end_bit + 7) / 8; }  // buffer fl
 
 template <typename K, int BITS, int IPT>
 static void sort_pass(const K* kin, const uint32_t* vin, K* kout, uint32_t* vout, uint32_t n, int shift, uint32_t* hist,
-                      const uint2* aux_in, uint2* aux_out, int aux16, hipStream_t s) {
+                      const uint2* aux_in, uint2* aux_out, int aux16, hipStream_t s, const uint32_t* dev_n) {
     const uint32_t nblocks = (n + 256u * IPT - 1) / (256u * IPT);
     constexpr int NB = 1 << BITS;
-    sgr_sort_hist_kernel<K, IPT><<<nblocks, 256, 0, s>>>(kin, n, shift, (uint32_t)(NB - 1), nblocks, hist);
+    sgr_sort_hist_kernel<K, IPT><<<nblocks, 256, 0, s>>>(kin, n, shift, (uint32_t)(NB - 1), nblocks, hist, dev_n);
     uint32_t* totals = hist + (size_t)NB * nblocks;
     sgr_sort_rowscan_kernel<<<NB, 256, 0, s>>>(hist, nblocks, totals);
     sgr_sort_scatter_kernel<K, BITS, IPT, false><<<nblocks, 256, 0, s>>>(kin, vin, kout, vout, n, shift, nblocks, hist, totals,
-                                                                         nullptr, nullptr, nullptr, 0u, aux_in, aux_out, aux16);
+                                                                         nullptr, nullptr, nullptr, 0u, aux_in, aux_out, aux16,
+                                                                         dev_n);
 }
 
 // Sorts n pairs on key bits [0, end_bit).  keys[0]/vals[0] hold the input; returns the index (0/1)
@@ -516,15 +531,17 @@ static void sort_pass(const K* kin, const uint32_t* vin, K* kout, uint32_t* vout
 // histogram depends on where the previous pass left the keys);
 // one sweep -- [control: 8 x 256 digit counts, 8 tickets, error flag | status table, 256 x 64 bit per block].
 // iota: vals[0] is not read, the value of input element i is i.  aux_in / aux_out: see the scatter kernel (last pass).
+// dev_n: only the first *dev_n (<= n) pairs are sorted, a count that lives on the device; n still sizes the grids and
+// picks the digit schedule, and nothing at or past the count is read or written.  Always the three-launch form.
 template <typename K>
 static int sort_pairs_impl(K* const keys[2], uint32_t* const vals[2], uint32_t n, int end_bit, uint32_t* hist,
                            uint32_t* scan_tmp, hipStream_t s, bool iota = false, const uint2* aux_in = nullptr,
-                           uint2* aux_out = nullptr, int max_bits = 8, int aux16 = 0) {
+                           uint2* aux_out = nullptr, int max_bits = 8, int aux16 = 0, const uint32_t* dev_n = nullptr) {
     if (n == 0) return 0;
     int npass = (end_bit + 7) / 8;
     int cur = 0;
 #if SGR_WITH_VARIANTS
-    if (sgr_sort_get_one_sweep() && npass <= SGR_SORT_MAX_PASS && !iota && !aux_in) {
+    if (sgr_sort_get_one_sweep() && npass <= SGR_SORT_MAX_PASS && !iota && !aux_in && !dev_n) {
         const uint32_t nblocks = (n + SGR_SORT_ITEMS - 1) / SGR_SORT_ITEMS;
         uint32_t* ghist = hist;
         uint32_t* tickets = hist + SGR_SORT_MAX_PASS * 256;
@@ -537,7 +554,7 @@ static int sort_pairs_impl(K* const keys[2], uint32_t* const vals[2], uint32_t n
         for (int p = 0; p < npass; p++) {
             sgr_sort_scatter_kernel<K, 8, SGR_SORT_IPT, true><<<nblocks, 256, 0, s>>>(
                 keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, 8 * p, nblocks, nullptr, ghist + p * 256, status,
-                tickets + p, err, (uint32_t)p + 1u, nullptr, nullptr, 0);
+                tickets + p, err, (uint32_t)p + 1u, nullptr, nullptr, 0, nullptr);
             cur ^= 1;
         }
         return cur;
@@ -552,7 +569,7 @@ static int sort_pairs_impl(K* const keys[2], uint32_t* const vals[2], uint32_t n
         const uint2* ai = last ? aux_in : nullptr;
         uint2* ao = last ? aux_out : nullptr;
         const int shift = bits * p;
-#define SGR_PASS(B, I) sort_pass<K, B, I>(keys[cur], vin, keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, ai, ao, aux16, s)
+#define SGR_PASS(B, I) sort_pass<K, B, I>(keys[cur], vin, keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, ai, ao, aux16, s, dev_n)
         if constexpr (sizeof(K) == 8) { SGR_PASS(8, 8); }
         else if (ipt == 16 && bits <= 8) {
             if (bits <= 5) SGR_PASS(5, 16); else if (bits == 6) SGR_PASS(6, 16); else if (bits == 7) SGR_PASS(7, 16); else SGR_PASS(8, 16);
@@ -570,8 +587,9 @@ int sgr_launch_sort_pairs(uint64_t* const keys[2], uint32_t* const vals[2], uint
     return sort_pairs_impl<uint64_t>(keys, vals, n, end_bit, hist, scan_tmp, s);
 }
 int sgr_launch_sort_pairs32(uint32_t* const keys[2], uint32_t* const vals[2], uint32_t n, int end_bit, uint32_t* hist,
-                            uint32_t* scan_tmp, hipStream_t s, bool iota, const uint2* aux_in, uint2* aux_out, int max_bits, int aux16) {
-    return sort_pairs_impl<uint32_t>(keys, vals, n, end_bit, hist, scan_tmp, s, iota, aux_in, aux_out, max_bits, aux16);
+                            uint32_t* scan_tmp, hipStream_t s, bool iota, const uint2* aux_in, uint2* aux_out, int max_bits, int aux16,
+                            const uint32_t* dev_n) {
+    return sort_pairs_impl<uint32_t>(keys, vals, n, end_bit, hist, scan_tmp, s, iota, aux_in, aux_out, max_bits, aux16, dev_n);
 }
 // 16-bit keys (the forward's tile sort when the frame has fewer than 65535 tiles): the same kernels on half the key bytes
 int sgr_launch_sort_pairs16(uint16_t* const keys[2], uint32_t* const vals[2], uint32_t n, int end_bit, uint32_t* hist,

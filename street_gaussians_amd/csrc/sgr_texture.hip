@@ -15,10 +15,13 @@
 //   5. gather  one lane per texel (per texel and channel for C != 3) walks the runs of the cells that have it as a tap:
 //              its four own cells and, on a face edge, the two border cells of each neighbouring face whose outside tap
 //              lands on it; a fixed order, so the sums are bit-reproducible.
+// With a device-side sample count (sgr_texture_cube_backward_impl, the fused sky composite's compacted sky pixels), the
+// key, sort, starts and record stages stop at that count; their grids stay sized by the host's upper bound.
 #include <string>
 
 #include "../../include/sgr_texture.h"
 #include "sgr_common.h"
+#include "sgr_cube.h"
 
 int sgr_set_error(int code, const std::string& msg);
 
@@ -28,124 +31,16 @@ int sgr_set_error(int code, const std::string& msg);
         if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
-// Edges of a face: 0 = column -1, 1 = column R, 2 = row -1, 3 = row R.  A tap at position k along edge e of face f is
-// texel (col, row) = (c0 (R-1) + c1 k, r0 (R-1) + r1 k) of face g; back = the edge of g that leads back to f.
-struct SgrCubeSeam {
-    int8_t g[6][4], c0[6][4], c1[6][4], r0[6][4], r1[6][4], back[6][4];
-};
-
-__device__ __forceinline__ float tx_su(int f) { return (f == 0 || f == 5) ? -1.f : 1.f; }  // SU = (-1, +1, +1, +1, +1, -1)
-__device__ __forceinline__ float tx_sv(int f) { return f == 2 ? 1.f : -1.f; }              // SV = (-1, -1, +1, -1, -1, -1)
-
-// Face and texel-space position (x, y) = (u R - 0.5, v R - 0.5) of direction d; false when (u, v) is not finite.
-__device__ __forceinline__ bool tx_coords(float dx, float dy, float dz, int R, int& face, float& x, float& y) {
-    const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
-    float c, s, t;
-    if (az > fmaxf(ax, ay)) { c = dz; s = dx; t = dy; face = 4 + (c < 0.f); }
-    else if (ay > ax) { c = dy; s = dx; t = dz; face = 2 + (c < 0.f); }
-    else { c = dx; s = dz; t = dy; face = 0 + (c < 0.f); }
-    const float m = 0.5f / fabsf(c);
-    float u = s * tx_su(face) * m + 0.5f, v = t * tx_sv(face) * m + 0.5f;
-    if (!isfinite(u) || !isfinite(v)) return false;
-    u = fminf(fmaxf(u, 0.f), 1.f);
-    v = fminf(fmaxf(v, 0.f), 1.f);
-    x = u * (float)R - 0.5f;
-    y = v * (float)R - 0.5f;
-    return true;
-}
-
-// Texel (within one batch's 6 R R texels) of footprint tap (col, row) of face f, or -1 when it lies outside two edges.
-__device__ __forceinline__ int64_t tx_tap(const SgrCubeSeam& sm, int R, int f, int col, int row) {
-    const bool ox = col < 0 || col >= R, oy = row < 0 || row >= R;
-    if (ox && oy) return -1;
-    if (ox || oy) {
-        const int e = ox ? (col < 0 ? 0 : 1) : (row < 0 ? 2 : 3);
-        const int k = ox ? row : col;
-        const int g = sm.g[f][e];
-        col = sm.c0[f][e] * (R - 1) + sm.c1[f][e] * k;
-        row = sm.r0[f][e] * (R - 1) + sm.r1[f][e] * k;
-        f = g;
-    }
-    return ((int64_t)f * R + row) * R + col;
-}
-
-// The four taps of cell (x0, y0) of face f in the order (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1); a missing corner
-// tap gets index -1.
-__device__ __forceinline__ int tx_cell_taps(const SgrCubeSeam& sm, int R, int f, int x0, int y0, int64_t idx[4]) {
-    int miss = -1;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        idx[k] = tx_tap(sm, R, f, x0 + (k & 1), y0 + (k >> 1));
-        if (idx[k] < 0) miss = k;
-    }
-    return miss;
-}
-
-__device__ __forceinline__ void tx_weights(float fx, float fy, float w[4]) {
-    w[0] = (1.f - fx) * (1.f - fy);
-    w[1] = fx * (1.f - fy);
-    w[2] = (1.f - fx) * fy;
-    w[3] = fx * fy;
-}
-
 // ---- forward --------------------------------------------------------------------------------------------------------
-// CT > 0: C = CT at compile time; CT = 0: C at run time.
 template <int CT>
 __global__ void __launch_bounds__(256)
 sgr_texture_cube_fwd_kernel(int Bt, int R, int Crt, int64_t n, int64_t total, const float* __restrict__ tex,
                             const float* __restrict__ uv, float* __restrict__ out, SgrCubeSeam sm) {
-    const int C = CT > 0 ? CT : Crt;
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= total) return;
     const int64_t b = s / n;
-    float* o = out + s * C;
-    int face;
-    float x, y;
-    if (!tx_coords(uv[3 * s], uv[3 * s + 1], uv[3 * s + 2], R, face, x, y)) {
-        for (int ch = 0; ch < C; ch++) o[ch] = 0.f;
-        return;
-    }
-    const float xf = floorf(x), yf = floorf(y);
-    const int x0 = (int)xf, y0 = (int)yf;
-    float w[4];
-    tx_weights(x - xf, y - yf, w);
-    const float* T = tex + (Bt == 1 ? 0 : b) * 6 * (int64_t)R * R * C;
-    int64_t idx[4];
-    if (x0 >= 0 && y0 >= 0 && x0 < R - 1 && y0 < R - 1) {
-        idx[0] = ((int64_t)face * R + y0) * R + x0;
-        idx[1] = idx[0] + 1;
-        idx[2] = idx[0] + R;
-        idx[3] = idx[2] + 1;
-    } else {
-        const int miss = tx_cell_taps(sm, R, face, x0, y0, idx);
-        if (miss >= 0) {  // the corner outside both edges: the mean of the other three texels
-            const float share = w[miss] * (1.f / 3.f);
-#pragma unroll
-            for (int k = 0; k < 4; k++) w[k] += share;
-            w[miss] = 0.f;
-            idx[miss] = idx[miss ^ 3];  // any valid texel: its weight is 0
-        }
-    }
-    if constexpr (CT > 0) {
-        float acc[CT];
-#pragma unroll
-        for (int ch = 0; ch < CT; ch++) acc[ch] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float* t = T + idx[k] * CT;
-#pragma unroll
-            for (int ch = 0; ch < CT; ch++) acc[ch] += w[k] * t[ch];
-        }
-#pragma unroll
-        for (int ch = 0; ch < CT; ch++) o[ch] = acc[ch];
-    } else {
-        for (int ch = 0; ch < C; ch++) {
-            float a = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) a += w[k] * T[idx[k] * C + ch];
-            o[ch] = a;
-        }
-    }
+    const float* T = tex + (Bt == 1 ? 0 : b) * 6 * (int64_t)R * R * (CT > 0 ? CT : Crt);
+    tx_lookup<CT>(T, R, Crt, sm, uv[3 * s], uv[3 * s + 1], uv[3 * s + 2], out + s * (CT > 0 ? CT : Crt));
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------
@@ -161,9 +56,10 @@ __device__ __forceinline__ uint32_t tx_cell_key(const TxGrid& g, int bt, int f, 
 }
 
 __global__ void __launch_bounds__(256)
-sgr_texture_cube_key_kernel(TxGrid g, const float* __restrict__ uv, uint32_t* __restrict__ keys) {
+sgr_texture_cube_key_kernel(TxGrid g, const float* __restrict__ uv, uint32_t* __restrict__ keys,
+                            const uint32_t* __restrict__ dev_n) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= g.total) return;
+    if (s >= g.total || (dev_n && s >= (int64_t)*dev_n)) return;
     int face;
     float x, y;
     uint32_t key = g.ncells;
@@ -174,9 +70,10 @@ sgr_texture_cube_key_kernel(TxGrid g, const float* __restrict__ uv, uint32_t* __
 
 __global__ void __launch_bounds__(256)
 sgr_texture_cube_starts_kernel(uint32_t ncells, uint32_t nsorted, const uint32_t* __restrict__ keys,
-                               uint32_t* __restrict__ starts) {
+                               uint32_t* __restrict__ starts, const uint32_t* __restrict__ dev_n) {
     const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (c > ncells) return;
+    if (dev_n) nsorted = min(nsorted, *dev_n);
     uint32_t lo = 0, hi = nsorted;  // first position with key >= c
     while (lo < hi) {
         const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -188,9 +85,9 @@ sgr_texture_cube_starts_kernel(uint32_t ncells, uint32_t nsorted, const uint32_t
 __global__ void __launch_bounds__(256)
 sgr_texture_cube_record_kernel(TxGrid g, int C, const float* __restrict__ uv, const float* __restrict__ dout,
                                const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
-                               float2* __restrict__ rec, float* __restrict__ gs) {
+                               float2* __restrict__ rec, float* __restrict__ gs, const uint32_t* __restrict__ dev_n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= g.total || keys[i] >= g.ncells) return;  // the sentinel run at the end is never read
+    if (i >= g.total || (dev_n && i >= (int64_t)*dev_n) || keys[i] >= g.ncells) return;  // the sentinel run at the end is never read
     const int64_t s = order[i];
     int face;
     float x, y;
@@ -354,11 +251,15 @@ bool derive_seam(SgrCubeSeam& sm) {
     return true;
 }
 
-const SgrCubeSeam* seam() {
+}  // namespace
+
+const SgrCubeSeam* sgr_cube_seam() {
     static SgrCubeSeam sm;
     static const bool ok = derive_seam(sm);
     return ok ? &sm : nullptr;
 }
+
+namespace {
 
 int check_args(int Bt, int B, int R, int C, int64_t n, TxGrid& g) {
     if (R < 1 || C < 1 || B < 1 || n < 0 || !(Bt == 1 || Bt == B))
@@ -368,7 +269,7 @@ int check_args(int Bt, int B, int R, int C, int64_t n, TxGrid& g) {
         return sgr_set_error(SGR_E_INVALID, "texture: Bt * 6 * (R + 1)^2 cell keys do not fit in 32 bits");
     if ((uint64_t)B * (uint64_t)n > 0x7fffffffull)
         return sgr_set_error(SGR_E_INVALID, "texture: more than 2^31 - 1 samples");
-    if (!seam()) return sgr_set_error(SGR_E_INVALID, "texture: the cube seam table could not be derived");
+    if (!sgr_cube_seam()) return sgr_set_error(SGR_E_INVALID, "texture: the cube seam table could not be derived");
     g.Bt = Bt;
     g.R = R;
     g.n = n;
@@ -417,33 +318,34 @@ int sgr_texture_cube_forward(int Bt, int B, int R, int C, int64_t n, const float
     if (!tex || !uv || !out) return sgr_set_error(SGR_E_INVALID, "texture: tex, uv and out are required");
     if (g.total == 0) return 0;
     hipStream_t s = (hipStream_t)stream_;
-    const SgrCubeSeam& sm = *seam();
+    const SgrCubeSeam& sm = *sgr_cube_seam();
     if (C == 3) sgr_texture_cube_fwd_kernel<3><<<blocks(g.total), 256, 0, s>>>(Bt, R, C, n, g.total, tex, uv, out, sm);
     else sgr_texture_cube_fwd_kernel<0><<<blocks(g.total), 256, 0, s>>>(Bt, R, C, n, g.total, tex, uv, out, sm);
     TX_HIP(hipGetLastError());
     return 0;
 }
 
-int sgr_texture_cube_backward(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
-                              float* dL_dtex, void* workspace, void* stream_) {
+int sgr_texture_cube_backward_impl(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
+                                   float* dL_dtex, void* workspace, const uint32_t* dev_n, hipStream_t s) {
     TxGrid g;
     if (const int rc = check_args(Bt, B, R, C, n, g)) return rc;
     if (!uv || !dL_dout || !dL_dtex || !workspace)
         return sgr_set_error(SGR_E_INVALID, "texture: uv, dL_dout, dL_dtex and workspace are required");
-    hipStream_t s = (hipStream_t)stream_;
-    const SgrCubeSeam& sm = *seam();
+    if (dev_n && (Bt != 1 || B != 1)) return sgr_set_error(SGR_E_INVALID, "texture: a device-side count needs Bt = B = 1");
+    const SgrCubeSeam& sm = *sgr_cube_seam();
     TxWork w = carve((char*)sgr_align_up((size_t)workspace, 256), g, C);
     int cur = 0;
     if (g.total) {
-        sgr_texture_cube_key_kernel<<<blocks(g.total), 256, 0, s>>>(g, uv, w.keys[0]);
+        sgr_texture_cube_key_kernel<<<blocks(g.total), 256, 0, s>>>(g, uv, w.keys[0], dev_n);
         int end_bit = 1;
         while (end_bit < 32 && (g.ncells >> end_bit)) end_bit++;  // the sentinel ncells is the largest key
-        cur = sgr_launch_sort_pairs32(w.keys, w.vals, (uint32_t)g.total, end_bit, w.hist, w.scan_tmp, s, true);
+        cur = sgr_launch_sort_pairs32(w.keys, w.vals, (uint32_t)g.total, end_bit, w.hist, w.scan_tmp, s, true, nullptr,
+                                      nullptr, 8, 0, dev_n);
         sgr_texture_cube_record_kernel<<<blocks(g.total), 256, 0, s>>>(g, C, uv, dL_dout, w.keys[cur], w.vals[cur], w.rec,
-                                                                       w.gs);
+                                                                       w.gs, dev_n);
     }
     sgr_texture_cube_starts_kernel<<<blocks((uint64_t)g.ncells + 1), 256, 0, s>>>(g.ncells, (uint32_t)g.total, w.keys[cur],
-                                                                                  w.starts);
+                                                                                  w.starts, dev_n);
     const uint64_t texels = (uint64_t)Bt * 6 * R * R;
     if (C == 3)
         sgr_texture_cube_gather_kernel<3><<<blocks(texels), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
@@ -451,4 +353,9 @@ int sgr_texture_cube_backward(int Bt, int B, int R, int C, int64_t n, const floa
         sgr_texture_cube_gather_kernel<0><<<blocks(texels * C), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
     TX_HIP(hipGetLastError());
     return 0;
+}
+
+int sgr_texture_cube_backward(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
+                              float* dL_dtex, void* workspace, void* stream_) {
+    return sgr_texture_cube_backward_impl(Bt, B, R, C, n, uv, dL_dout, dL_dtex, workspace, nullptr, (hipStream_t)stream_);
 }
