@@ -24,6 +24,7 @@ SYMBOLS = [
     "sgr_export_internal", "sgr_test_scan", "sgr_test_sort", "sgr_test_sort32", "sgr_test_sort_hist_words", "sgr_test_scan_tmp_words",
     "sgr_test_wave_sum", "sgr_test_exact_math", "sgr_test_lds_atomic_order", "sgr_test_switches", "sgr_has_variants", "sgr_set_lazy", "sgr_lazy_status", "sgr_profile_host_wait_us", "sgr_profile_enable", "sgr_profile_select", "sgr_profile_sample", "sgr_profile_read", "sgr_masked_color_grad",
     "sgr_sh_grad_from_views", "sgr_sh_grad_from_views_ex", "sgr_scene_compose_forward", "sgr_scene_compose_backward",
+    "sgr_scene_compose_forward_ex", "sgr_scene_compose_backward_ex",
     "sgr_scene_densification_stats", "sgr_ssim_workspace_floats", "sgr_ssim_forward", "sgr_ssim_backward",
     "sgr_l1_workspace_floats", "sgr_l1_forward", "sgr_l1_backward", "sgr_color_loss_backward", "sgr_bce_forward", "sgr_bce_backward",
     "sgr_lidar_work_bytes", "sgr_lidar_depth_forward", "sgr_lidar_depth_backward", "sgr_densify_work_bytes", "sgr_densify_plan",
@@ -91,6 +92,10 @@ def lib():
         L.sgr_scene_compose_forward.argtypes = [i, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
         L.sgr_scene_compose_backward.restype = i
         L.sgr_scene_compose_backward.argtypes = [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
+        L.sgr_scene_compose_forward_ex.restype = i
+        L.sgr_scene_compose_forward_ex.argtypes = [i, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
+        L.sgr_scene_compose_backward_ex.restype = i
+        L.sgr_scene_compose_backward_ex.argtypes = [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
         L.sgr_scene_densification_stats.restype = i
         L.sgr_scene_densification_stats.argtypes = [i, vp, vp, vp, ALLOC_FN, vp, vp]
         for n in ("sgr_ssim_workspace_floats", "sgr_l1_workspace_floats"):

@@ -24,7 +24,7 @@ SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_
 # and the tests of those paths run only against such a build.
 VARIANT_SOURCES = [os.path.join("variants", "sgr_blend_bwd_sw.hip")]
 HEADERS = ["sgr_common.h", "sgr_math.h", "sgr_reduce.h", "sgr_cube.h", os.path.join("..", "..", "include", "sgr.h"),
-           os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
+           os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 ops into v_pk_* and pays for it with v_mov

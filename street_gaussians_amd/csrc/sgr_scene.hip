@@ -10,12 +10,16 @@
 //         issue-bound on CDNA4: 64 cache lines per load instruction);
 //       * the pose gradient of an actor (rotation 4 + translation 3) is a reduction over its Gaussians: per-chunk
 //         partial sums in a fixed order, then one small kernel per actor sums its chunks in order -> deterministic.
+//     Per frame (include/sgr_scene_frame.h): the camera pose correction of the static segments, whose gradient is the
+//     same 16-sum reduction over the background (thousands of chunks: two fixed-order levels instead of one wave), and
+//     zero spans for the gradient blocks of the models absent from the frame.
 // n2  densification statistics scattered back per model in one pass (street_gaussian_model.py:551-571).
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/sgr_scene.h"
+#include "../../include/sgr_scene_frame.h"
 #include "sgr_common.h"
 
 int sgr_set_error(int code, const std::string& msg);
@@ -30,6 +34,7 @@ struct SgrSegDev {
     sgr_scene_segment s;
     sgr_scene_segment_grads g;
     int32_t first_chunk, nchunks;
+    int32_t corr_first;  // static segment under a correction: ordinal of its first chunk among the corrected chunks
 };
 
 // ---- quaternion helpers (real part first; general_utils.py:220-238) ----
@@ -62,11 +67,50 @@ __device__ __forceinline__ void qtomat(const Q4 q, float (&R)[9], Q4& qn, float&
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// ---- camera pose correction (include/sgr_scene_frame.h): the declared order, contraction off --------------------
+__device__ __forceinline__ float qlen_nc(const Q4 a) {
+#pragma clang fp contract(off)
+    return sqrtf(((a.w * a.w + a.x * a.x) + a.y * a.y) + a.z * a.z);
+}
+__device__ __forceinline__ Q4 qmul_nc(const Q4 a, const Q4 b) {
+#pragma clang fp contract(off)
+    return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+            a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
+}
+struct SgrCorr {
+    Q4 raw, qc, qq;     // c[0:4], F.normalize(c[0:4]), qc / |qc|
+    float nc, n2;       // max(|raw|, 1e-12), |qc|
+    float R[9], t[3];
+};
+__device__ __forceinline__ SgrCorr corr_load(const float* __restrict__ c) {
+#pragma clang fp contract(off)
+    SgrCorr k;
+    k.raw = {c[0], c[1], c[2], c[3]};
+    k.nc = fmaxf(qlen_nc(k.raw), 1e-12f);
+    k.qc = {k.raw.w / k.nc, k.raw.x / k.nc, k.raw.y / k.nc, k.raw.z / k.nc};
+    k.n2 = qlen_nc(k.qc);
+    k.qq = {k.qc.w / k.n2, k.qc.x / k.n2, k.qc.y / k.n2, k.qc.z / k.n2};
+    const float r = k.qq.w, x = k.qq.x, y = k.qq.y, z = k.qq.z;
+    k.R[0] = 1.f - 2.f * (y * y + z * z); k.R[1] = 2.f * (x * y - r * z); k.R[2] = 2.f * (x * z + r * y);
+    k.R[3] = 2.f * (x * y + r * z); k.R[4] = 1.f - 2.f * (x * x + z * z); k.R[5] = 2.f * (y * z - r * x);
+    k.R[6] = 2.f * (x * z - r * y); k.R[7] = 2.f * (y * z + r * x); k.R[8] = 1.f - 2.f * (x * x + y * y);
+    k.t[0] = c[4]; k.t[1] = c[5]; k.t[2] = c[6];
+    return k;
+}
+// x'_a = ((x_0 R_a0 + x_1 R_a1) + x_2 R_a2) + t_a
+__device__ __forceinline__ void corr_xyz(const SgrCorr& k, float (&x)[3]) {
+#pragma clang fp contract(off)
+    float y[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) y[a] = ((x[0] * k.R[3 * a] + x[1] * k.R[3 * a + 1]) + x[2] * k.R[3 * a + 2]) + k.t[a];
+    x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
+}
+
 // ---- forward: small attributes, one lane per Gaussian ---------------------------------------------------------
 __global__ void __launch_bounds__(SGR_SC_THREADS)
 sgr_scene_fwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __restrict__ segs, int S,
                      float* __restrict__ means3D, float* __restrict__ rotations, float* __restrict__ scales,
-                     float* __restrict__ opacities, float* __restrict__ semantics) {
+                     float* __restrict__ opacities, float* __restrict__ semantics, const float* __restrict__ corr) {
     const SgrChunk c = chunks[blockIdx.x];
     const sgr_scene_segment& sg = segs[c.seg].s;
     if ((int)threadIdx.x >= c.n) return;
@@ -90,6 +134,10 @@ sgr_scene_fwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
         x[0] = y0; x[1] = y1; x[2] = y2;
         float n2;
         q = qnormalize(qmul(po, q), n2);  // :328-329
+    } else if (corr) {  // camera pose correction (camera_pose.py:89-114, street_gaussian_model.py:311-312, 340-341)
+        const SgrCorr k = corr_load(corr);
+        corr_xyz(k, x);
+        q = qmul_nc(k.qc, q);
     }
     means3D[3 * o] = x[0]; means3D[3 * o + 1] = x[1]; means3D[3 * o + 2] = x[2];
     *reinterpret_cast<float4*>(rotations + 4 * o) = make_float4(q.w, q.x, q.y, q.z);
@@ -156,7 +204,8 @@ sgr_scene_sh_fwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __
 __global__ void __launch_bounds__(SGR_SC_THREADS)
 sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __restrict__ segs, int S,
                      const float* __restrict__ dmeans, const float* __restrict__ drot, const float* __restrict__ dscale,
-                     const float* __restrict__ dopac, const float* __restrict__ dsem, float* __restrict__ partials) {
+                     const float* __restrict__ dopac, const float* __restrict__ dsem, float* __restrict__ partials,
+                     const float* __restrict__ corr, float* __restrict__ cpart) {
     __shared__ float red[SGR_SC_THREADS / 64][SGR_SC_NPART];
     const SgrChunk c = chunks[blockIdx.x];
     const SgrSegDev& sd = segs[c.seg];
@@ -210,6 +259,22 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
             Q4 dql = qmul(qconj(po), du);          // d(a b)/db . dO = a* dO
             if (flip) dql = qmul(qconj(fq), dql);
             dq = dql;
+        } else if (corr) {  // x' = R x + t, rot' = qc (x) ql0: the same partials as an actor's, over the background
+            const SgrCorr k = corr_load(corr);
+            const float x[3] = {sg.xyz[3 * i], sg.xyz[3 * i + 1], sg.xyz[3 * i + 2]};
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+#pragma unroll
+                for (int b = 0; b < 3; b++) part[3 * a + b] = dx[a] * x[b];
+                part[9 + a] = dx[a];
+            }
+            const float dl[3] = {k.R[0] * dx[0] + k.R[3] * dx[1] + k.R[6] * dx[2],
+                                 k.R[1] * dx[0] + k.R[4] * dx[1] + k.R[7] * dx[2],
+                                 k.R[2] * dx[0] + k.R[5] * dx[1] + k.R[8] * dx[2]};
+            dx[0] = dl[0]; dx[1] = dl[1]; dx[2] = dl[2];
+            const Q4 dqc = qmul(dq, qconj(ql0));  // d(a b)/da . dO = dO b*
+            part[12] = dqc.w; part[13] = dqc.x; part[14] = dqc.y; part[15] = dqc.z;
+            dq = qmul(qconj(k.qc), dq);           // d(a b)/db . dO = a* dO
         }
         if (gr.xyz) { gr.xyz[3 * i] = dx[0]; gr.xyz[3 * i + 1] = dx[1]; gr.xyz[3 * i + 2] = dx[2]; }
         if (gr.rotation) {
@@ -247,7 +312,11 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
             }  // static logits: copied by the SH kernel, one lane per float
         }
     }
-    if (sg.kind != SGR_SEG_ACTOR || partials == nullptr) return;  // uniform per workgroup
+    // uniform per workgroup: an actor's chunk sums go to its slot of `partials`, a corrected static chunk's to `cpart`
+    float* dst = nullptr;
+    if (sg.kind == SGR_SEG_ACTOR) dst = partials ? partials + (size_t)blockIdx.x * SGR_SC_NPART : nullptr;
+    else if (corr && cpart) dst = cpart + (size_t)(sd.corr_first + (int)blockIdx.x - sd.first_chunk) * SGR_SC_NPART;
+    if (dst == nullptr) return;
     // chunk-wide sums in a fixed order: wave butterfly, then waves 0..3 in order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -260,7 +329,7 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
     __syncthreads();
     if (threadIdx.x < SGR_SC_NPART) {
         const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * SGR_SC_NPART + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+        dst[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
     }
 }
 
@@ -297,6 +366,97 @@ sgr_scene_pose_bwd_kernel(const SgrSegDev* __restrict__ segs, const float* __res
     sd.g.pose[4] = tot[9];
     sd.g.pose[5] = tot[10];
     sd.g.pose[6] = tot[11];
+}
+
+// dL/d(unit quaternion q) of x' = R(q) x from G[3a+b] = sum dx'_a x_b (general_utils.py:137-145)
+__device__ __forceinline__ Q4 dquat_of_R(const Q4 q, const float* G) {
+    const float r = q.w, x = q.x, y = q.y, z = q.z;
+    Q4 d;
+    d.w = 2.f * (-z * G[1] + y * G[2] + z * G[3] - x * G[5] - y * G[6] + x * G[7]);
+    d.x = 2.f * (y * G[1] + z * G[2] + y * G[3] - 2.f * x * G[4] - r * G[5] + z * G[6] + r * G[7] - 2.f * x * G[8]);
+    d.y = 2.f * (-2.f * y * G[0] + x * G[1] + r * G[2] + x * G[3] + z * G[5] - r * G[6] + z * G[7] - 2.f * y * G[8]);
+    d.z = 2.f * (-2.f * z * G[0] - r * G[1] + x * G[2] + r * G[3] - 2.f * z * G[4] + y * G[5] + x * G[6] + y * G[7]);
+    return d;
+}
+
+// the 16 sums of a workgroup's values in a fixed order: wave butterfly, then waves 0..3 in order (256 threads)
+__device__ __forceinline__ void sum16_fixed(float (&v)[SGR_SC_NPART], float (&red)[SGR_SC_THREADS / 64][SGR_SC_NPART]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < SGR_SC_NPART; k++) {
+        float a = v[k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m, 64);
+        if (lane == 0) red[wave][k] = a;
+    }
+    __syncthreads();
+}
+
+// correction, level 2: workgroup b sums the corrected chunks [256 b, 256 b + 256) (one per lane) in a fixed order
+__global__ void __launch_bounds__(SGR_SC_THREADS)
+sgr_scene_corr_sum_kernel(const float* __restrict__ cpart, int nc, float* __restrict__ gpart) {
+    __shared__ float red[SGR_SC_THREADS / 64][SGR_SC_NPART];
+    const int j = blockIdx.x * SGR_SC_THREADS + threadIdx.x;
+    float v[SGR_SC_NPART];
+#pragma unroll
+    for (int k = 0; k < SGR_SC_NPART; k += 4) {
+        const float4 t = j < nc ? *reinterpret_cast<const float4*>(cpart + (size_t)j * SGR_SC_NPART + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
+    }
+    sum16_fixed(v, red);
+    if (threadIdx.x < SGR_SC_NPART) {
+        const int k = threadIdx.x;
+        gpart[(size_t)blockIdx.x * SGR_SC_NPART + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    }
+}
+
+// correction, level 3: one workgroup sums the ng groups (lane l: groups l, l + 256, ... in order), then one lane chains
+// through R(qq), qq = qc / |qc| and qc = F.normalize(raw) into the 7 correction gradients
+__global__ void __launch_bounds__(SGR_SC_THREADS)
+sgr_scene_corr_final_kernel(const float* __restrict__ gpart, int ng, const float* __restrict__ corr, float* __restrict__ out) {
+    __shared__ float red[SGR_SC_THREADS / 64][SGR_SC_NPART];
+    float v[SGR_SC_NPART];
+#pragma unroll
+    for (int k = 0; k < SGR_SC_NPART; k++) v[k] = 0.f;
+    for (int j = threadIdx.x; j < ng; j += SGR_SC_THREADS) {
+#pragma unroll
+        for (int k = 0; k < SGR_SC_NPART; k++) v[k] += gpart[(size_t)j * SGR_SC_NPART + k];
+    }
+    sum16_fixed(v, red);
+    if (threadIdx.x != 0) return;
+    float tot[SGR_SC_NPART];
+#pragma unroll
+    for (int k = 0; k < SGR_SC_NPART; k++) tot[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    const SgrCorr c = corr_load(corr);
+    Q4 dqc = qnormalize_bwd(c.qq, c.n2, dquat_of_R(c.qq, tot), false);  // quaternion_to_matrix's own |q| (no eps)
+    dqc = {dqc.w + tot[12], dqc.x + tot[13], dqc.y + tot[14], dqc.z + tot[15]};
+    const Q4 d = qnormalize_bwd(c.qc, c.nc, dqc, qlen_nc(c.raw) < 1e-12f);  // F.normalize
+    out[0] = d.w; out[1] = d.x; out[2] = d.y; out[3] = d.z;
+    out[4] = tot[9]; out[5] = tot[10]; out[6] = tot[11];
+}
+
+// zero spans: workgroup b clears SGR_SC_ZSPAN floats of the span whose block range holds b (binary search)
+#define SGR_SC_ZSPAN 4096
+struct SgrZeroDev {
+    float* ptr;
+    size_t count;
+    uint32_t first_block;
+};
+__global__ void __launch_bounds__(SGR_SC_THREADS)
+sgr_scene_zero_kernel(const SgrZeroDev* __restrict__ spans, int n) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (spans[mid].first_block <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const SgrZeroDev s = spans[lo];
+    const size_t base = (size_t)(blockIdx.x - s.first_block) * SGR_SC_ZSPAN;
+#pragma unroll 4
+    for (int k = 0; k < SGR_SC_ZSPAN / SGR_SC_THREADS; k++) {
+        const size_t e = base + (size_t)k * SGR_SC_THREADS + threadIdx.x;
+        if (e < s.count) s.ptr[e] = 0.f;
+    }
 }
 
 // ---- backward: SH rows, one lane per float of each gradient array ----------------------------------------------
@@ -425,35 +585,53 @@ static int stage_get(size_t bytes, SgrPinnedStage** out) {
     return 0;
 }
 
-// uploads [segments | chunks] (+ room for partials) into scratch; returns device pointers
+// uploads [segments | chunks | zero spans] (+ room for partials) into scratch; returns device pointers
 template <typename SegDev>
 static int upload(const std::vector<SegDev>& sd, const std::vector<SgrChunk>& chunks, size_t extra_floats,
                   sgr_alloc_fn scratch, void* scratch_user, hipStream_t stream, SegDev** dsegs, SgrChunk** dchunks,
-                  float** dextra) {
+                  float** dextra, const std::vector<SgrZeroDev>* spans = nullptr, SgrZeroDev** dspans = nullptr) {
     const size_t b0 = sgr_align_up(sd.size() * sizeof(SegDev), 256), b1 = sgr_align_up(chunks.size() * sizeof(SgrChunk), 256);
-    char* base = scratch(b0 + b1 + extra_floats * sizeof(float) + 512, scratch_user);
+    const size_t b2 = spans ? sgr_align_up(spans->size() * sizeof(SgrZeroDev), 256) : 0;
+    char* base = scratch(b0 + b1 + b2 + extra_floats * sizeof(float) + 512, scratch_user);
     if (!base) return sgr_set_error(SGR_E_ALLOC, "scene scratch allocation failed");
     base = (char*)sgr_align_up((size_t)base, 256);
     SgrPinnedStage* st;
-    int rc = stage_get(b0 + b1, &st);
+    int rc = stage_get(b0 + b1 + b2, &st);
     if (rc) return rc;
     memcpy(st->p, sd.data(), sd.size() * sizeof(SegDev));
     memcpy(st->p + b0, chunks.data(), chunks.size() * sizeof(SgrChunk));
-    SC_HIP(hipMemcpyAsync(base, st->p, b0 + b1, hipMemcpyHostToDevice, stream));
+    if (spans) memcpy(st->p + b0 + b1, spans->data(), spans->size() * sizeof(SgrZeroDev));
+    SC_HIP(hipMemcpyAsync(base, st->p, b0 + b1 + b2, hipMemcpyHostToDevice, stream));
     SC_HIP(hipEventRecord(st->ev, stream));
     st->pending = true;
     *dsegs = (SegDev*)base;
     *dchunks = (SgrChunk*)(base + b0);
-    if (dextra) *dextra = (float*)(base + b0 + b1);
+    if (dspans) *dspans = (SgrZeroDev*)(base + b0 + b1);
+    if (dextra) *dextra = (float*)(base + b0 + b1 + b2);
     return 0;
 }
 
-extern "C" {
+// the frame's zero spans as the zero kernel's table (empty spans dropped); returns the number of workgroups
+static int zero_table(const sgr_scene_frame* frame, std::vector<SgrZeroDev>& spans, uint32_t* blocks) {
+    *blocks = 0;
+    if (!frame || frame->n_zero <= 0) return 0;
+    if (!frame->zero) return sgr_set_error(SGR_E_INVALID, "frame: n_zero > 0 without a span array");
+    size_t total = 0;
+    for (int k = 0; k < frame->n_zero; k++) {
+        const sgr_zero_span& z = frame->zero[k];
+        if (z.count == 0) continue;
+        if (!z.ptr) return sgr_set_error(SGR_E_INVALID, "frame: zero span without a pointer");
+        spans.push_back({z.ptr, z.count, (uint32_t)total});
+        total += (z.count + SGR_SC_ZSPAN - 1) / SGR_SC_ZSPAN;
+        if (total > 0x7fffffffu) return sgr_set_error(SGR_E_INVALID, "frame: zero spans too large");
+    }
+    *blocks = (uint32_t)total;
+    return 0;
+}
 
-int sgr_scene_compose_forward(int K, const sgr_scene_segment* segs, int M, int S, float* means3D, float* rotations,
-                              float* scales, float* opacities, float* shs, float* semantics, sgr_alloc_fn scratch,
-                              void* scratch_user, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+static int compose_forward(int K, const sgr_scene_segment* segs, int M, int S, float* means3D, float* rotations,
+                           float* scales, float* opacities, float* shs, float* semantics, const sgr_scene_frame* frame,
+                           sgr_alloc_fn scratch, void* scratch_user, hipStream_t stream) {
     int rc = check_segments(K, segs, M, S);
     if (rc) return rc;
     if (!scratch) return sgr_set_error(SGR_E_INVALID, "scratch callback is required");
@@ -464,42 +642,95 @@ int sgr_scene_compose_forward(int K, const sgr_scene_segment* segs, int M, int S
     if (!means3D || !rotations || !scales || !opacities || !shs || (S > 0 && !semantics))
         return sgr_set_error(SGR_E_INVALID, "all output arrays are required");
     std::vector<SgrSegDev> sd(K);
-    for (int k = 0; k < K; k++) { sd[k].s = segs[k]; sd[k].g = sgr_scene_segment_grads{}; sd[k].first_chunk = first[k]; sd[k].nchunks = count[k]; }
+    for (int k = 0; k < K; k++) { sd[k].s = segs[k]; sd[k].g = sgr_scene_segment_grads{}; sd[k].first_chunk = first[k]; sd[k].nchunks = count[k]; sd[k].corr_first = -1; }
     SgrSegDev* dsegs; SgrChunk* dchunks;
     if ((rc = upload(sd, chunks, 0, scratch, scratch_user, stream, &dsegs, &dchunks, nullptr))) return rc;
     const unsigned nb = (unsigned)chunks.size();
-    sgr_scene_fwd_kernel<<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, means3D, rotations, scales, opacities, semantics);
+    const float* corr = frame ? frame->correction : nullptr;
+    sgr_scene_fwd_kernel<<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, means3D, rotations, scales, opacities, semantics, corr);
     if (M == 16) sgr_scene_sh_fwd_kernel<16><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, shs, semantics);
     else sgr_scene_sh_fwd_kernel<0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, shs, semantics);
     SC_HIP(hipGetLastError());
     return 0;
 }
 
+static int compose_backward(int K, const sgr_scene_segment* segs, const sgr_scene_segment_grads* grads, int M, int S,
+                            const float* dL_dmeans3D, const float* dL_drotations, const float* dL_dscales,
+                            const float* dL_dopacities, const float* dL_dshs, const float* dL_dsemantics,
+                            const sgr_scene_frame* frame, sgr_alloc_fn scratch, void* scratch_user, hipStream_t stream) {
+    int rc = check_segments(K, segs, M, S);
+    if (rc) return rc;
+    if (!grads || !scratch) return sgr_set_error(SGR_E_INVALID, "grads and scratch are required");
+    std::vector<SgrZeroDev> spans;
+    uint32_t zblocks = 0;
+    if ((rc = zero_table(frame, spans, &zblocks))) return rc;
+    const float* corr = frame ? frame->correction : nullptr;
+    float* corr_grad = corr ? frame->correction_grad : nullptr;
+    std::vector<SgrChunk> chunks;
+    std::vector<int> first, count;
+    const size_t N = build_chunks(K, segs, chunks, first, count);
+    if (N == 0 && zblocks == 0 && !corr_grad) return 0;
+    std::vector<SgrSegDev> sd(K);
+    int nc = 0;  // corrected chunks
+    for (int k = 0; k < K; k++) {
+        sd[k].s = segs[k]; sd[k].g = grads[k]; sd[k].first_chunk = first[k]; sd[k].nchunks = count[k]; sd[k].corr_first = -1;
+        if (corr && segs[k].kind == SGR_SEG_STATIC) { sd[k].corr_first = nc; nc += count[k]; }
+    }
+    const int ng = (nc + SGR_SC_THREADS - 1) / SGR_SC_THREADS;  // groups of 256 corrected chunks
+    const size_t np = chunks.size() * SGR_SC_NPART, ncp = corr_grad ? (size_t)nc * SGR_SC_NPART : 0;
+    const size_t ngp = corr_grad ? (size_t)ng * SGR_SC_NPART : 0;
+    SgrSegDev* dsegs; SgrChunk* dchunks; float* partials; SgrZeroDev* dspans;
+    if ((rc = upload(sd, chunks, np + ncp + ngp, scratch, scratch_user, stream, &dsegs, &dchunks, &partials, &spans, &dspans)))
+        return rc;
+    float* cpart = corr_grad ? partials + np : nullptr;
+    float* gpart = corr_grad ? partials + np + ncp : nullptr;
+    if (zblocks) sgr_scene_zero_kernel<<<zblocks, SGR_SC_THREADS, 0, stream>>>(dspans, (int)spans.size());
+    const unsigned nb = (unsigned)chunks.size();
+    if (nb) {
+        sgr_scene_bwd_kernel<<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, dL_dmeans3D, dL_drotations, dL_dscales,
+                                                                dL_dopacities, dL_dsemantics, partials, corr, cpart);
+        sgr_scene_pose_bwd_kernel<<<(unsigned)K, 64, 0, stream>>>(dsegs, partials);
+        if (M == 16) sgr_scene_sh_bwd_kernel<16><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics);
+        else sgr_scene_sh_bwd_kernel<0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics);
+    }
+    if (corr_grad) {
+        if (ng) sgr_scene_corr_sum_kernel<<<(unsigned)ng, SGR_SC_THREADS, 0, stream>>>(cpart, nc, gpart);
+        sgr_scene_corr_final_kernel<<<1, SGR_SC_THREADS, 0, stream>>>(gpart, ng, corr, corr_grad);
+    }
+    SC_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+int sgr_scene_compose_forward(int K, const sgr_scene_segment* segs, int M, int S, float* means3D, float* rotations,
+                              float* scales, float* opacities, float* shs, float* semantics, sgr_alloc_fn scratch,
+                              void* scratch_user, void* stream_) {
+    return compose_forward(K, segs, M, S, means3D, rotations, scales, opacities, shs, semantics, nullptr, scratch,
+                           scratch_user, (hipStream_t)stream_);
+}
+
+int sgr_scene_compose_forward_ex(int K, const sgr_scene_segment* segs, int M, int S, float* means3D, float* rotations,
+                                 float* scales, float* opacities, float* shs, float* semantics,
+                                 const sgr_scene_frame* frame, sgr_alloc_fn scratch, void* scratch_user, void* stream_) {
+    return compose_forward(K, segs, M, S, means3D, rotations, scales, opacities, shs, semantics, frame, scratch,
+                           scratch_user, (hipStream_t)stream_);
+}
+
 int sgr_scene_compose_backward(int K, const sgr_scene_segment* segs, const sgr_scene_segment_grads* grads, int M, int S,
                                const float* dL_dmeans3D, const float* dL_drotations, const float* dL_dscales,
                                const float* dL_dopacities, const float* dL_dshs, const float* dL_dsemantics,
                                sgr_alloc_fn scratch, void* scratch_user, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_segments(K, segs, M, S);
-    if (rc) return rc;
-    if (!grads || !scratch) return sgr_set_error(SGR_E_INVALID, "grads and scratch are required");
-    std::vector<SgrChunk> chunks;
-    std::vector<int> first, count;
-    const size_t N = build_chunks(K, segs, chunks, first, count);
-    if (N == 0) return 0;
-    std::vector<SgrSegDev> sd(K);
-    for (int k = 0; k < K; k++) { sd[k].s = segs[k]; sd[k].g = grads[k]; sd[k].first_chunk = first[k]; sd[k].nchunks = count[k]; }
-    SgrSegDev* dsegs; SgrChunk* dchunks; float* partials;
-    if ((rc = upload(sd, chunks, chunks.size() * SGR_SC_NPART, scratch, scratch_user, stream, &dsegs, &dchunks, &partials)))
-        return rc;
-    const unsigned nb = (unsigned)chunks.size();
-    sgr_scene_bwd_kernel<<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, dL_dmeans3D, dL_drotations, dL_dscales,
-                                                            dL_dopacities, dL_dsemantics, partials);
-    sgr_scene_pose_bwd_kernel<<<(unsigned)K, 64, 0, stream>>>(dsegs, partials);
-    if (M == 16) sgr_scene_sh_bwd_kernel<16><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics);
-    else sgr_scene_sh_bwd_kernel<0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics);
-    SC_HIP(hipGetLastError());
-    return 0;
+    return compose_backward(K, segs, grads, M, S, dL_dmeans3D, dL_drotations, dL_dscales, dL_dopacities, dL_dshs,
+                            dL_dsemantics, nullptr, scratch, scratch_user, (hipStream_t)stream_);
+}
+
+int sgr_scene_compose_backward_ex(int K, const sgr_scene_segment* segs, const sgr_scene_segment_grads* grads, int M,
+                                  int S, const float* dL_dmeans3D, const float* dL_drotations, const float* dL_dscales,
+                                  const float* dL_dopacities, const float* dL_dshs, const float* dL_dsemantics,
+                                  const sgr_scene_frame* frame, sgr_alloc_fn scratch, void* scratch_user, void* stream_) {
+    return compose_backward(K, segs, grads, M, S, dL_dmeans3D, dL_drotations, dL_dscales, dL_dopacities, dL_dshs,
+                            dL_dsemantics, frame, scratch, scratch_user, (hipStream_t)stream_);
 }
 
 int sgr_scene_densification_stats(int K, const sgr_scene_stats_segment* segs, const float* dL_dmeans2D, const int* radii,

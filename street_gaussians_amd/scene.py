@@ -8,11 +8,17 @@ street_gaussian_model.py:287-449, gaussian_model.py:224-251, gaussian_model_acto
 every raw parameter and to each actor's pose.  ``densification_stats`` is the per-model scatter of
 ``add_densification_stats`` + ``set_max_radii2D`` (:551-571) in one pass.
 
+Per frame (include/sgr_scene_frame.h): ``correction`` is the camera pose correction the reference applies to the
+background with ``use_pose_correction`` (lib/models/camera_pose.py:89-114), and ``FlatScene.compose(segments=...)``
+renders the frame's subset of the persistent models (parse_camera, street_gaussian_model.py:230-250).
+
 There is no CPU implementation: tensors must live on the GPU and the HIP library must be built.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import operator
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -37,6 +43,34 @@ class _CSeg(C.Structure):
 class _CSegGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("xyz", "rotation", "scaling", "opacity", "features_dc", "features_rest",
                                          "semantic", "pose")]
+
+
+class _CZeroSpan(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("count", C.c_size_t)]
+
+
+class _CFrame(C.Structure):
+    _fields_ = [("correction", C.c_void_p), ("correction_grad", C.c_void_p), ("n_zero", C.c_int32), ("zero", C.c_void_p)]
+
+
+def _frame(correction, correction_grad=None, spans=()):
+    """sgr_scene_frame for one call (None when it would be empty), and the objects that must outlive the call."""
+    if correction is None and not spans:
+        return None, None
+    zero = (_CZeroSpan * len(spans))(*[_CZeroSpan(p, n) for p, n in spans]) if spans else None
+    fr = _CFrame(correction.data_ptr() if correction is not None else None,
+                 correction_grad.data_ptr() if correction_grad is not None else None, len(spans),
+                 C.cast(zero, C.c_void_p) if zero is not None else None)
+    return C.byref(fr), (fr, zero)
+
+
+def _correction(t):
+    """The [7] correction (pose_correction_rots[id] w, x, y, z, then pose_correction_trans[id]) as float32 on the GPU."""
+    if t is None:
+        return None
+    if t.numel() != 7:
+        raise ValueError(f"correction must hold 7 values (rotation w, x, y, z, translation), got shape {tuple(t.shape)}")
+    return _f32c(t.reshape(7), "correction")
 
 
 class _CStatSeg(C.Structure):
@@ -124,22 +158,25 @@ def _pack(segs: List[Segment], tensors: List[Optional[torch.Tensor]]):
 
 class _Compose(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, segs, M, S, *tensors):
+    def forward(ctx, segs, M, S, correction, *tensors):
         dev = tensors[0].device
+        corr = _correction(correction)
         arr, keep = _pack(segs, list(tensors))
         N = sum(int(c.count) for c in arr)
         f = dict(dtype=torch.float32, device=dev)
         outs = [torch.empty(N, 3, **f), torch.empty(N, 4, **f), torch.empty(N, 3, **f), torch.empty(N, 1, **f),
                 torch.empty(N, M, 3, **f), torch.empty(N, S, **f)]
         grow = _Grow(dev)
+        frame, fkeep = _frame(corr)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_forward(
-                len(segs), arr, int(M), int(S), *[_ptr(o) if o.numel() else None for o in outs], grow.cb, None,
+            check(_native.lib().sgr_scene_compose_forward_ex(
+                len(segs), arr, int(M), int(S), *[_ptr(o) if o.numel() else None for o in outs], frame, grow.cb, None,
                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         ctx.segs, ctx.M, ctx.S = segs, int(M), int(S)
         ctx.save_for_backward(*[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
-        ctx.packed = (arr, keep)  # same storages in backward (autograd forbids in-place changes of saved tensors)
+        ctx.packed = (arr, keep)
+        ctx.corr = (correction, corr)  # same storages in backward (autograd forbids in-place changes of saved tensors)
         return tuple(outs)
 
     @staticmethod
@@ -150,7 +187,7 @@ class _Compose(torch.autograd.Function):
         dev = tensors[0].device
         arr, keep = ctx.packed
         garr = (_CSegGrads * len(segs))()
-        need = ctx.needs_input_grad[3:]
+        need = ctx.needs_input_grad[4:]
         # one allocation for all gradients (16-byte aligned slices), carved into per-parameter views with ONE split
         # call + one view per parameter: this runs on the autograd thread and is pure host time next to ~0.4 ms of kernels
         want = [t is not None and need[i] for i, t in enumerate(tensors)]
@@ -169,26 +206,37 @@ class _Compose(torch.autograd.Function):
                     setattr(g, name, out.data_ptr())
         dz = lambda t: None if t is None else _f32c(t, "grad")
         ins = [dz(d_means), dz(d_rot), dz(d_scale), dz(d_opac), dz(d_shs), dz(d_sem) if S else None]
+        correction, corr = ctx.corr
+        dcorr = torch.empty(7, dtype=torch.float32, device=dev) if corr is not None and ctx.needs_input_grad[3] else None
+        frame, fkeep = _frame(corr, dcorr)
         grow = _Grow(dev)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_backward(
-                len(segs), arr, garr, M, S, *[_ptr(t) if t is not None and t.numel() else None for t in ins], grow.cb,
-                None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            check(_native.lib().sgr_scene_compose_backward_ex(
+                len(segs), arr, garr, M, S, *[_ptr(t) if t is not None and t.numel() else None for t in ins], frame,
+                grow.cb, None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         del keep
         # kernels work in float32; hand autograd the dtype of each input
         grads = [g if g is None or g.dtype == t.dtype else g.to(t.dtype) for g, t in zip(grads, tensors)]
-        return (None, None, None) + tuple(grads)
+        if dcorr is not None:
+            dcorr = dcorr.view(correction.shape).to(correction.dtype)
+        return (None, None, None, dcorr) + tuple(grads)
 
 
-def compose(segments: List[Segment], max_sh_coeffs: int, num_classes: int):
+def compose(segments: List[Segment], max_sh_coeffs: int, num_classes: int, correction: Optional[torch.Tensor] = None):
     """Returns (means3D [N,3], rotations [N,4], scales [N,3], opacities [N,1], shs [N,M,3], semantics [N,S]) for the
-    concatenation of ``segments`` (background first, then the visible actors, like ``parse_camera`` orders them)."""
+    concatenation of ``segments`` (background first, then the visible actors, like ``parse_camera`` orders them).
+
+    ``correction``: the camera pose correction of the rendered image, a [7] tensor -- typically
+    ``torch.cat([pc.pose_correction.pose_correction_rots[id], pc.pose_correction.pose_correction_trans[id]])``, whose
+    gradient flows back through that ``cat`` -- applied to the static segments as ``get_xyz`` / ``get_rotation`` do with
+    ``use_pose_correction`` (camera_pose.py:89-114).  Pass it only where the reference applies it
+    (``cfg.mode in ['train', 'evaluate']``)."""
     if not segments:
         raise ValueError("need at least one segment")
     flat = []
     for s in segments:
         flat += [getattr(s, n) for n in _TENSORS]
-    return _Compose.apply(list(segments), int(max_sh_coeffs), int(num_classes), *flat)
+    return _Compose.apply(list(segments), int(max_sh_coeffs), int(num_classes), correction, *flat)
 
 
 # ---- flat-parameter mode ---------------------------------------------------------------------------------------------
@@ -208,7 +256,8 @@ class FlatScene:
     wide per Gaussian and of semantic [S] for the background / [1] for an actor, so those two are flattened to 1-D); the
     result's ``xyz, rotation, scaling, opacity, features_dc, features_rest, semantic`` and ``poses`` [n_actors, 7] require
     grad and are what an optimiser holds; ``views()`` gives the per-model tensors (views: densification, I/O).
-    ``compose(M, S, flip_masks=None, idfts=None)`` is ``scene.compose`` for the current values."""
+    ``compose(M, S, flip_masks=None, poses=None, idfts=None, segments=None, correction=None)`` is ``scene.compose`` for
+    the current values of the frame's models ``segments`` (default: all)."""
 
     def __init__(self, meta, tensors, poses):
         self.meta = meta              # per segment: dict(count, kind, fourier_dim, sem_width, class_label, semantic_mode, flip_*)
@@ -240,7 +289,10 @@ class FlatScene:
                                          "xyz, rotation, scaling, opacity, features_dc and features_rest")
                     continue
                 t = t.detach().float()
-                parts[k].append(t.reshape(-1) if k in ("features_dc", "semantic") else t.reshape(n, -1))
+                if k in ("features_dc", "semantic"):
+                    parts[k].append(t.reshape(-1))
+                else:  # an empty model keeps its row width (reshape(0, -1) is ambiguous)
+                    parts[k].append(t.reshape(n, -1) if n else t.reshape(0, math.prod(t.shape[1:]) if t.dim() > 1 else 1))
             if s.pose is not None:
                 poses.append(s.pose.detach().float().reshape(7))
         tensors = {}
@@ -269,7 +321,7 @@ class FlatScene:
         for m, o in zip(self.meta, self._offsets()):
             n = m["count"]
             d = {k: self.tensors[k][o["row"]:o["row"] + n] for k in ("xyz", "rotation", "scaling", "opacity", "features_rest")}
-            d["features_rest"] = d["features_rest"].view(n, -1, 3)
+            d["features_rest"] = d["features_rest"].view(n, d["features_rest"].shape[1] // 3, 3)
             d["features_dc"] = self.tensors["features_dc"][o["dc"]:o["dc"] + n * m["fourier_dim"] * 3].view(n, m["fourier_dim"], 3)
             d["semantic"] = self.tensors["semantic"][o["sem"]:o["sem"] + n * m["sem_width"]].view(n, m["sem_width"])
             if m["kind"] == SEG_ACTOR:
@@ -279,74 +331,145 @@ class FlatScene:
         return out
 
     def compose(self, max_sh_coeffs: int, num_classes: int, flip_masks: Optional[Sequence] = None,
-                poses: Optional[torch.Tensor] = None, idfts: Optional[Sequence] = None):
+                poses: Optional[torch.Tensor] = None, idfts: Optional[Sequence] = None,
+                segments: Optional[Sequence[int]] = None, correction: Optional[torch.Tensor] = None):
         """Same result as ``scene.compose(segments, M, S)``; gradients arrive in the 7 flat leaves and in the poses.
 
-        Per frame (street_gaussian_model.py:230-330): ``poses`` [n_actors, 7] (obj_rot wxyz + obj_trans in world space) is
-        usually a NON-leaf the caller derives from its tracking-pose refinements and the ego pose -- pass it here and
-        the gradient flows on to those; default: the ``poses`` leaf held by this object.  ``idfts`` = one IDFT row
-        [fourier_dim] per segment (None for the background): it depends on the frame's timestamp
+        ``segments``: the indices (into the persistent models) this frame renders, in rasterization order, each at most
+        once -- ``parse_camera`` (street_gaussian_model.py:230-250) builds background + the actors present at the
+        frame; ``render_object`` passes the actors only, ``render_background`` the background only.  None = every
+        model, in order.  The outputs hold the present models' rows in that order; the flat gradients stay full-size,
+        0 in the blocks of the absent models (written by the same backward call).
+
+        Per frame (street_gaussian_model.py:230-330): ``poses`` [n_actors_in_frame, 7] (obj_rot wxyz + obj_trans in
+        world space, the frame's actors in frame order) is usually a NON-leaf the caller derives from its tracking-pose
+        refinements and the ego pose -- pass it here and the gradient flows on to those; default: the rows of those
+        actors in the ``poses`` leaf held by this object (its other rows get a zero gradient).  ``idfts`` = one IDFT row
+        [fourier_dim] per rendered segment (None for the background): it depends on the frame's timestamp
         (gaussian_model_actor.py:71-80); default: the rows the segments carried at construction.  ``flip_masks`` = one
-        bool [n] mask per segment or None (training-time symmetry flips, :270-283)."""
-        fm = list(flip_masks) if flip_masks is not None else [None] * len(self.meta)
-        P = self.poses if poses is None else poses
-        n_actors = sum(1 for m in self.meta if m["kind"] == SEG_ACTOR)
-        if n_actors and (P is None or P.shape[0] != n_actors):
-            raise ValueError(f"FlatScene.compose: {n_actors} actor segments need a [{n_actors}, 7] pose tensor")
+        bool [n] mask per rendered segment or None (training-time symmetry flips, :270-283).  ``correction``: the [7]
+        camera pose correction of the image, applied to the background (see ``scene.compose``)."""
+        K = len(self.meta)
+        if segments is None:
+            seg = list(range(K))
+        else:
+            seg = [operator.index(i) for i in segments]
+            bad = [i for i in seg if not 0 <= i < K]
+            if bad:
+                raise ValueError(f"FlatScene.compose: segment indices {bad} out of range for {K} models")
+            if len(set(seg)) != len(seg):
+                raise ValueError("FlatScene.compose: a model is rendered at most once per frame (repeated index in "
+                                 "`segments`)")
+        for name, v in (("flip_masks", flip_masks), ("idfts", idfts)):
+            if v is not None and len(v) != len(seg):
+                raise ValueError(f"FlatScene.compose: {name} has {len(v)} entries for {len(seg)} rendered segments")
+        fm = list(flip_masks) if flip_masks is not None else [None] * len(seg)
+        ordinal, a = {}, 0  # persistent model -> its row of the poses leaf
+        for i, m in enumerate(self.meta):
+            if m["kind"] == SEG_ACTOR:
+                ordinal[i] = a
+                a += 1
+        frame_actors = [i for i in seg if self.meta[i]["kind"] == SEG_ACTOR]
+        if poses is None:
+            P, rows = self.poses, [ordinal[i] for i in frame_actors]
+        else:
+            P, rows = poses, list(range(len(frame_actors)))
+            if P.dim() != 2 or P.shape[0] != len(frame_actors) or P.shape[1] != 7:
+                raise ValueError(f"FlatScene.compose: the frame renders {len(frame_actors)} actors and needs a "
+                                 f"[{len(frame_actors)}, 7] pose tensor, got {tuple(P.shape)}")
+        if frame_actors and P is None:
+            raise ValueError("FlatScene.compose: actor segments need poses")
         if P is not None and (P.dtype != torch.float32 or not P.is_contiguous()):
             P = P.float().contiguous()
         ids = None
         if idfts is not None:
             ids = [None if t is None else torch.as_tensor(t, dtype=torch.float32, device=self.xyz.device).contiguous() for t in idfts]
-        args = [self.tensors[k] for k in _FLAT] + [P]
-        return _ComposeFlat.apply(self, (fm, ids), int(max_sh_coeffs), int(num_classes), *args)
+        args = [self.tensors[k] for k in _FLAT] + [P, correction]
+        return _ComposeFlat.apply(self, (fm, ids, seg, rows), int(max_sh_coeffs), int(num_classes), *args)
+
+
+def _blocks(fs: FlatScene, rest_w: int):
+    """Per persistent model: {attribute: (element offset, element count)} of its block inside each flat tensor."""
+    out = []
+    for m, o in zip(fs.meta, fs._offsets()):
+        n = m["count"]
+        out.append({"xyz": (3 * o["row"], 3 * n), "rotation": (4 * o["row"], 4 * n), "scaling": (3 * o["row"], 3 * n),
+                    "opacity": (o["row"], n), "features_dc": (o["dc"], n * m["fourier_dim"] * 3),
+                    "features_rest": (o["row"] * rest_w, n * rest_w), "semantic": (o["sem"], n * m["sem_width"])})
+    return out
+
+
+def _zero_spans(fs: FlatScene, frame, grads):
+    """(address, count) of every gradient block the kernels do not write: the absent models' blocks of the flat
+    gradients and the pose rows of the absent actors; adjacent blocks merged."""
+    _, _, seg, rows = frame
+    present = set(seg)
+    rest_w = grads[5].shape[1] if grads[5] is not None and grads[5].dim() == 2 else 0
+    spans = []
+    for i, blk in enumerate(_blocks(fs, rest_w)):
+        if i in present:
+            continue
+        for k, g in zip(_FLAT, grads):
+            off, cnt = blk[k]
+            if g is not None and cnt:
+                assert off + cnt <= g.numel(), (i, k)
+                spans.append((g.data_ptr() + 4 * off, cnt))
+    gp = grads[7]
+    if gp is not None and gp.numel():
+        used = set(rows)
+        for r in range(gp.shape[0]):
+            if r not in used:
+                spans.append((gp.data_ptr() + 4 * 7 * r, 7))
+    spans.sort()
+    merged = []
+    for p, n in spans:
+        if merged and merged[-1][0] + 4 * merged[-1][1] == p:
+            merged[-1] = (merged[-1][0], merged[-1][1] + n)
+        else:
+            merged.append((p, n))
+    return merged
 
 
 def _pack_flat(fs: FlatScene, tensors, frame, grads=None):
-    """_CSeg array (and, with `grads`, the _CSegGrads array) whose pointers address the segments' blocks of the flat tensors.
-    frame = (flip masks, IDFT rows or None) of this call."""
-    flip_masks, idfts = frame
-    arr = (_CSeg * len(fs.meta))()
-    garr = (_CSegGrads * len(fs.meta))() if grads is not None else None
+    """_CSeg array (and, with `grads`, the _CSegGrads array) of the rendered segments, in frame order, whose pointers
+    address their blocks of the flat tensors.  frame = (flip masks, IDFT rows or None, persistent indices, pose rows)
+    of this call."""
+    flip_masks, idfts, seg, rows = frame
+    arr = (_CSeg * len(seg))()
+    garr = (_CSegGrads * len(seg))() if grads is not None else None
     keep = []
     base = {k: (t.data_ptr() if t is not None and t.numel() else 0) for k, t in zip(_FLAT + ("poses",), tensors)}
     gbase = None
     if grads is not None:
         gbase = {k: (t.data_ptr() if t is not None and t.numel() else 0) for k, t in zip(_FLAT + ("poses",), grads)}
-    width = {"xyz": 3, "rotation": 4, "scaling": 3, "opacity": 1}
     rest_w = tensors[5].shape[1] if tensors[5] is not None and tensors[5].dim() == 2 else 0
+    blocks = _blocks(fs, rest_w)
     a = 0
-    for i, (m, o) in enumerate(zip(fs.meta, fs._offsets())):
-        c = arr[i]
+    for j, i in enumerate(seg):
+        m, blk = fs.meta[i], blocks[i]
+        c = arr[j]
         c.count, c.kind, c.fourier_dim = m["count"], m["kind"], m["fourier_dim"]
         c.class_label, c.sem_mode, c.flip_axis = m["class_label"], _SEM[m["semantic_mode"]], m["flip_axis"]
         c.flip_quat = (C.c_float * 4)(*[float(v) for v in m["flip_quat"]])
 
         def addr(b, name):
-            if not b[name] or not m["count"]:
-                return None
-            if name in width:
-                return b[name] + 4 * o["row"] * width[name]
-            if name == "features_rest":
-                return b[name] + 4 * o["row"] * rest_w if rest_w else None
-            if name == "features_dc":
-                return b[name] + 4 * o["dc"]
-            return b[name] + 4 * o["sem"] if m["sem_width"] else None  # semantic
+            off, cnt = blk[name]
+            return b[name] + 4 * off if b[name] and cnt else None
         for name in _FLAT:
             setattr(c, name, addr(base, name))
             if garr is not None:
-                setattr(garr[i], name, addr(gbase, name))
+                setattr(garr[j], name, addr(gbase, name))
         if m["kind"] == SEG_ACTOR:
-            c.pose = base["poses"] + 4 * 7 * a
+            c.pose = base["poses"] + 4 * 7 * rows[a]
             if garr is not None and gbase["poses"]:
-                garr[i].pose = gbase["poses"] + 4 * 7 * a
+                garr[j].pose = gbase["poses"] + 4 * 7 * rows[a]
             a += 1
-        fmk = flip_masks[i]
+        fmk = flip_masks[j]
         if fmk is not None:
             fmk = fmk.view(torch.uint8) if fmk.dtype == torch.bool and fmk.is_contiguous() else fmk.to(torch.uint8).contiguous()
             keep.append(fmk)
             c.flip_mask = fmk.data_ptr() if fmk.numel() else None
-        idft = m["idft"] if idfts is None else idfts[i]
+        idft = m["idft"] if idfts is None else idfts[j]
         if idft is not None:
             keep.append(idft)
             c.idft = idft.data_ptr()
@@ -355,25 +478,29 @@ def _pack_flat(fs: FlatScene, tensors, frame, grads=None):
 
 class _ComposeFlat(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fs, flip_masks, M, S, *tensors):
+    def forward(ctx, fs, frame, M, S, *tensors):
         dev = tensors[0].device
+        *tensors, correction = tensors
         for t in tensors:
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
                 raise SgrError("flat scene parameters must be contiguous float32 HIP tensors")
-        arr, _, keep = _pack_flat(fs, tensors, flip_masks)
-        N = sum(m["count"] for m in fs.meta)
+        corr = _correction(correction)
+        arr, _, keep = _pack_flat(fs, tensors, frame)
+        N = sum(fs.meta[i]["count"] for i in frame[2])
         f = dict(dtype=torch.float32, device=dev)
         outs = [torch.empty(N, 3, **f), torch.empty(N, 4, **f), torch.empty(N, 3, **f), torch.empty(N, 1, **f),
                 torch.empty(N, M, 3, **f), torch.empty(N, S, **f)]
         grow = _Grow(dev)
+        cframe, fkeep = _frame(corr)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_forward(
-                len(fs.meta), arr, int(M), int(S), *[_ptr(o) if o.numel() else None for o in outs], grow.cb, None,
+            check(_native.lib().sgr_scene_compose_forward_ex(
+                len(arr), arr, int(M), int(S), *[_ptr(o) if o.numel() else None for o in outs], cframe, grow.cb, None,
                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        ctx.fs, ctx.flip_masks, ctx.M, ctx.S = fs, flip_masks, int(M), int(S)
+        ctx.fs, ctx.frame, ctx.M, ctx.S = fs, frame, int(M), int(S)
         ctx.save_for_backward(*[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
         ctx.keep = keep
+        ctx.corr = (correction, corr)
         return tuple(outs)
 
     @staticmethod
@@ -384,16 +511,22 @@ class _ComposeFlat(torch.autograd.Function):
         dev = tensors[0].device
         need = ctx.needs_input_grad[4:]
         grads = [torch.empty_like(t) if (t is not None and need[i]) else None for i, t in enumerate(tensors)]
-        arr, garr, keep = _pack_flat(fs, tensors, ctx.flip_masks, grads)
+        arr, garr, keep = _pack_flat(fs, tensors, ctx.frame, grads)
+        spans = _zero_spans(fs, ctx.frame, grads)
+        correction, corr = ctx.corr
+        dcorr = torch.empty(7, dtype=torch.float32, device=dev) if corr is not None and need[8] else None
+        cframe, fkeep = _frame(corr, dcorr, spans)
         dz = lambda t: None if t is None else _f32c(t, "grad")
         ins = [dz(d_means), dz(d_rot), dz(d_scale), dz(d_opac), dz(d_shs), dz(d_sem) if S else None]
         grow = _Grow(dev)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_backward(
-                len(fs.meta), arr, garr, M, S, *[_ptr(t) if t is not None and t.numel() else None for t in ins], grow.cb,
-                None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            check(_native.lib().sgr_scene_compose_backward_ex(
+                len(arr), arr, garr, M, S, *[_ptr(t) if t is not None and t.numel() else None for t in ins], cframe,
+                grow.cb, None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         del keep
-        return (None, None, None, None) + tuple(grads)
+        if dcorr is not None:
+            dcorr = dcorr.view(correction.shape).to(correction.dtype)
+        return (None, None, None, None) + tuple(grads) + (dcorr,)
 
 
 def densification_stats(models: Sequence[dict], dL_dmeans2D: torch.Tensor, radii: torch.Tensor) -> None:
