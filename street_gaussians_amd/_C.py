@@ -11,7 +11,10 @@ import torch
 
 from . import _native
 from . import _alloc
-from ._native import ALLOC_FN, SgrError, SgrLazyError, check
+from ._native import SgrError, SgrLazyError, check
+# _native.py's shared helpers under the names this module has exported all along: callers drive the ctypes path through
+# _C._Grow and _C._stream (tests/test_gpu_tile_sort.py)
+from ._native import Grow as _Grow, stream as _stream
 
 NUM_CHANNELS = 3  # config.h:15
 
@@ -95,35 +98,6 @@ def _fptr(t, name="tensor"):
         raise SgrError(f"{name} must be float32")
     t = t.contiguous()
     return t, C.c_void_p(t.data_ptr())
-
-
-class _Grow:
-    """Growable byte buffer handed to the C side (resizeFunctional, rasterize_points.cu:27-33).
-
-    The callback closes over a one-element holder, NOT over this object: a bound method (`ALLOC_FN(self._alloc)`) made
-    `_Grow -> callback -> method -> _Grow` a reference cycle, and the buffer -- hundreds of MB of backward scratch per
-    call -- stayed allocated until Python's cyclic collector ran (round 5, tools/densify_gc_trace.py: +1.25 GB per
-    iteration at 5 M Gaussians for ~10 iterations in a row; the densify loop's "device allocations in the region")."""
-
-    def __init__(self, device):
-        holder = [torch.empty(0, dtype=torch.uint8, device=device)]
-
-        def alloc(nbytes, _user, holder=holder, device=device):
-            # (a larger block than asked for is fine -- the native side carves what it needs -- and ladder sizes repeat
-            # when the number of Gaussians drifts: _alloc.py)
-            holder[0] = torch.empty(_alloc.ladder(int(nbytes)), dtype=torch.uint8, device=device)
-            return holder[0].data_ptr()
-
-        self._holder = holder
-        self.cb = ALLOC_FN(alloc)
-
-    @property
-    def tensor(self):
-        return self._holder[0]
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,

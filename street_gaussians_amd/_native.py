@@ -9,6 +9,10 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
+from . import _alloc
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SGR_LIB: another BUILD of the same library (tools/gpu_ab.sh variants built with other -D switches); never a fallback
 LIB_PATH = os.environ.get("SGR_LIB") or os.path.join(_HERE, "libsgr_hip.so")
@@ -17,22 +21,89 @@ ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
 
 _lib = None
 
-# every symbol include/sgr.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    "sgr_last_error", "sgr_version", "sgr_forward", "sgr_backward", "sgr_backward_ex", "sgr_mark_visible", "sgr_visible_filter",
-    "sgr_knn", "sgr_geometry_bytes", "sgr_binning_bytes", "sgr_image_bytes", "sgr_partial_row_floats",
-    "sgr_export_internal", "sgr_test_scan", "sgr_test_sort", "sgr_test_sort32", "sgr_test_sort_hist_words", "sgr_test_scan_tmp_words",
-    "sgr_test_wave_sum", "sgr_test_exact_math", "sgr_test_lds_atomic_order", "sgr_test_switches", "sgr_has_variants", "sgr_set_lazy", "sgr_lazy_status", "sgr_profile_host_wait_us", "sgr_profile_enable", "sgr_profile_select", "sgr_profile_sample", "sgr_profile_read", "sgr_masked_color_grad",
-    "sgr_sh_grad_from_views", "sgr_sh_grad_from_views_ex", "sgr_scene_compose_forward", "sgr_scene_compose_backward",
-    "sgr_scene_compose_forward_ex", "sgr_scene_compose_backward_ex",
-    "sgr_scene_densification_stats", "sgr_ssim_workspace_floats", "sgr_ssim_forward", "sgr_ssim_backward",
-    "sgr_l1_workspace_floats", "sgr_l1_forward", "sgr_l1_backward", "sgr_color_loss_backward", "sgr_bce_forward", "sgr_bce_backward",
-    "sgr_lidar_work_bytes", "sgr_lidar_depth_forward", "sgr_lidar_depth_backward", "sgr_densify_work_bytes", "sgr_densify_plan",
-    "sgr_densify_map", "sgr_densify_gather", "sgr_densify_split_children", "sgr_densify_prune_mask",
-    "sgr_densify_compact", "sgr_reset_opacity", "sgr_texture_cube_workspace_bytes", "sgr_texture_cube_forward",
-    "sgr_texture_cube_backward", "sgr_adam_span_elems", "sgr_adam_step", "sgr_sky_workspace_bytes", "sgr_sky_forward",
-    "sgr_sky_backward", "sgr_sky_test_rays", "sgr_test_sort32_count",
-]
+
+def _signatures():
+    vp, f, d, i, u32, i64, sz = C.c_void_p, C.c_float, C.c_double, C.c_int, C.c_uint32, C.c_int64, C.c_size_t
+    i64p = C.POINTER(C.c_int64)
+    bwd = [i, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp, vp, vp, vp,
+           vp, vp, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, i, vp]
+    return {
+        "sgr_last_error": (C.c_char_p, []),
+        "sgr_version": (i, []),
+        "sgr_forward": (i, [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, f, vp,
+                            vp, vp, vp, vp, f, f, i, vp, vp, vp, vp, vp, i, vp]),
+        "sgr_backward": (i, bwd),
+        "sgr_backward_ex": (i, bwd + [vp]),
+        "sgr_mark_visible": (i, [i, vp, vp, vp, vp, vp]),
+        "sgr_visible_filter": (i, [i, i, i, vp, vp, f, vp, vp, vp, vp, f, f, i, vp, vp, i, vp]),
+        "sgr_knn": (i, [i, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_geometry_bytes": (sz, [i]),
+        "sgr_binning_bytes": (sz, [i]),
+        "sgr_image_bytes": (sz, [i, i]),
+        "sgr_partial_row_floats": (i, [i]),
+        "sgr_export_internal": (i, [i, i, i, i, i, vp, vp, vp, vp, vp]),
+        "sgr_test_scan": (i, [vp, vp, sz, i, vp, vp]),
+        "sgr_test_sort": (i, [vp, vp, vp, vp, u32, i, vp, vp, vp]),
+        "sgr_test_sort32": (i, [vp, vp, vp, vp, u32, i, i, vp, vp, vp]),
+        "sgr_test_sort_hist_words": (sz, [u32]),
+        "sgr_test_scan_tmp_words": (sz, [sz]),
+        "sgr_test_wave_sum": (i, [vp, vp, vp, i, vp]),
+        "sgr_test_exact_math": (i, [i, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_test_lds_atomic_order": (i, [vp, vp, i, vp]),
+        "sgr_test_switches": (i, [i]),
+        "sgr_has_variants": (i, []),
+        "sgr_set_lazy": (i, [i]),
+        "sgr_lazy_status": (i, [vp, vp, vp]),
+        "sgr_profile_host_wait_us": (i, [i]),
+        "sgr_profile_enable": (i, [i]),
+        "sgr_profile_select": (i, [i]),
+        "sgr_profile_sample": (i, [i]),
+        "sgr_profile_read": (i, [vp, vp]),
+        "sgr_masked_color_grad": (i, [i, vp, vp, vp, vp]),
+        "sgr_sh_grad_from_views": (i, [i, i, i, i, vp, vp, vp, vp, vp]),
+        "sgr_sh_grad_from_views_ex": (i, [i, i, i, i, vp, sz, vp, sz, vp, sz, vp, vp]),
+        "sgr_scene_compose_forward": (i, [i, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_scene_compose_backward": (i, [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_scene_compose_forward_ex": (i, [i, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_scene_compose_backward_ex": (i, [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_scene_densification_stats": (i, [i, vp, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_ssim_workspace_floats": (sz, [i, i, i]),
+        "sgr_ssim_forward": (i, [i, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_ssim_backward": (i, [i, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_l1_workspace_floats": (sz, [i, i, i]),
+        "sgr_l1_forward": (i, [i, i, i, vp, vp, vp, vp, vp, vp]),
+        "sgr_l1_backward": (i, [i, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_color_loss_backward": (i, [i, i, i, vp, vp, vp, vp, vp, f, f, vp, vp, vp]),
+        "sgr_bce_forward": (i, [i, i, vp, vp, vp, vp, vp]),
+        "sgr_bce_backward": (i, [i, i, vp, vp, vp, vp, vp]),
+        "sgr_lidar_work_bytes": (sz, [i]),
+        "sgr_lidar_depth_forward": (i, [i, vp, vp, vp, vp, d, vp, vp, vp]),
+        "sgr_lidar_depth_backward": (i, [i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_densify_work_bytes": (sz, [i]),
+        "sgr_densify_plan": (i, [i, vp, vp, vp, vp, vp, vp, i64p, vp]),
+        "sgr_densify_map": (i, [i, vp, vp, vp, vp, vp, vp]),
+        "sgr_densify_gather": (i, [i, i, vp, vp, vp, i, vp, vp]),
+        "sgr_densify_split_children": (i, [i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_densify_prune_mask": (i, [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i64p, vp]),
+        "sgr_densify_compact": (i, [i, vp, vp, vp, i64p, vp]),
+        "sgr_reset_opacity": (i, [i, vp, vp, vp, vp]),
+        "sgr_texture_cube_workspace_bytes": (sz, [i, i, i, i, i64]),
+        "sgr_texture_cube_forward": (i, [i, i, i, i, i64, vp, vp, vp, vp]),
+        "sgr_texture_cube_backward": (i, [i, i, i, i, i64, vp, vp, vp, vp, vp]),
+        "sgr_adam_span_elems": (i, []),
+        "sgr_adam_step": (i, [vp, i, vp, i, i64, d, d, vp]),
+        "sgr_sky_workspace_bytes": (sz, [i, i, i, i, i]),
+        "sgr_sky_forward": (i, [i, i, i, i] + [vp] * 9 + [i, vp, vp, vp]),
+        "sgr_sky_backward": (i, [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_sky_test_rays": (i, [i, i, vp, vp, vp, vp, i, vp, vp, vp]),
+        "sgr_test_sort32_count": (i, [vp, vp, vp, vp, u32, i, i, vp, vp, vp, vp]),
+    }
+
+
+# name -> (restype, argtypes) of every function include/*.h declares; the tests check each against its prototype and that
+# the library exports all of them
+SIGNATURES = _signatures()
+SYMBOLS = list(SIGNATURES)
 
 
 class SgrError(RuntimeError):
@@ -57,134 +128,9 @@ def lib():
             raise SgrError(f"{LIB_PATH} not found: build it with `python -m street_gaussians_amd.build` "
                            "(there is no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        L.sgr_last_error.restype = C.c_char_p
-        L.sgr_version.restype = C.c_int
-        L.sgr_profile_host_wait_us.restype = C.c_int
-        L.sgr_profile_host_wait_us.argtypes = [C.c_int]
-        for n in ("sgr_geometry_bytes", "sgr_binning_bytes", "sgr_test_sort_hist_words", "sgr_test_scan_tmp_words"):
-            getattr(L, n).restype = C.c_size_t
-        L.sgr_geometry_bytes.argtypes = [C.c_int]
-        L.sgr_binning_bytes.argtypes = [C.c_int]
-        L.sgr_image_bytes.restype = C.c_size_t
-        L.sgr_image_bytes.argtypes = [C.c_int, C.c_int]
-        L.sgr_test_sort_hist_words.argtypes = [C.c_uint32]
-        L.sgr_test_scan_tmp_words.argtypes = [C.c_size_t]
-        vp, f, i = C.c_void_p, C.c_float, C.c_int
-        L.sgr_forward.restype = i
-        L.sgr_forward.argtypes = [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp,
-                                  f, vp, vp, vp, vp, vp, f, f, i, vp, vp, vp, vp, vp, i, vp]
-        L.sgr_backward.restype = i
-        L.sgr_backward.argtypes = [i, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, vp, vp,
-                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, i, vp]
-        L.sgr_backward_ex.restype = i
-        L.sgr_backward_ex.argtypes = L.sgr_backward.argtypes + [vp]
-        L.sgr_mark_visible.restype = i
-        L.sgr_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
-        L.sgr_visible_filter.restype = i
-        L.sgr_visible_filter.argtypes = [i, i, i, vp, vp, f, vp, vp, vp, vp, f, f, i, vp, vp, i, vp]
-        L.sgr_masked_color_grad.restype = i
-        L.sgr_masked_color_grad.argtypes = [i, vp, vp, vp, vp]
-        L.sgr_sh_grad_from_views.restype = i
-        L.sgr_sh_grad_from_views.argtypes = [i, i, i, i, vp, vp, vp, vp, vp]
-        L.sgr_sh_grad_from_views_ex.restype = i
-        L.sgr_sh_grad_from_views_ex.argtypes = [i, i, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
-        L.sgr_scene_compose_forward.restype = i
-        L.sgr_scene_compose_forward.argtypes = [i, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
-        L.sgr_scene_compose_backward.restype = i
-        L.sgr_scene_compose_backward.argtypes = [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
-        L.sgr_scene_compose_forward_ex.restype = i
-        L.sgr_scene_compose_forward_ex.argtypes = [i, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
-        L.sgr_scene_compose_backward_ex.restype = i
-        L.sgr_scene_compose_backward_ex.argtypes = [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]
-        L.sgr_scene_densification_stats.restype = i
-        L.sgr_scene_densification_stats.argtypes = [i, vp, vp, vp, ALLOC_FN, vp, vp]
-        for n in ("sgr_ssim_workspace_floats", "sgr_l1_workspace_floats"):
-            getattr(L, n).restype = C.c_size_t
-            getattr(L, n).argtypes = [i, i, i]
-        L.sgr_ssim_forward.restype = i
-        L.sgr_ssim_forward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_ssim_backward.restype = i
-        L.sgr_ssim_backward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_color_loss_backward.restype = i
-        L.sgr_color_loss_backward.argtypes = [i, i, i, vp, vp, vp, vp, vp, f, f, vp, vp, vp]
-        L.sgr_l1_forward.restype = i
-        L.sgr_l1_forward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp]
-        L.sgr_l1_backward.restype = i
-        L.sgr_l1_backward.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_bce_forward.restype = i
-        L.sgr_bce_forward.argtypes = [i, i, vp, vp, vp, vp, vp]
-        L.sgr_bce_backward.restype = i
-        L.sgr_bce_backward.argtypes = [i, i, vp, vp, vp, vp, vp]
-        L.sgr_lidar_work_bytes.restype = C.c_size_t
-        L.sgr_lidar_work_bytes.argtypes = [i]
-        L.sgr_lidar_depth_forward.restype = i
-        L.sgr_lidar_depth_forward.argtypes = [i, vp, vp, vp, vp, C.c_double, vp, vp, vp]
-        L.sgr_lidar_depth_backward.restype = i
-        L.sgr_lidar_depth_backward.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_densify_work_bytes.restype = C.c_size_t
-        L.sgr_densify_work_bytes.argtypes = [i]
-        L.sgr_densify_plan.restype = i
-        L.sgr_densify_plan.argtypes = [i, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp]
-        L.sgr_densify_map.restype = i
-        L.sgr_densify_map.argtypes = [i, vp, vp, vp, vp, vp, vp]
-        L.sgr_densify_gather.restype = i
-        L.sgr_densify_gather.argtypes = [i, i, vp, vp, vp, i, vp, vp]
-        L.sgr_densify_split_children.restype = i
-        L.sgr_densify_split_children.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_densify_prune_mask.restype = i
-        L.sgr_densify_prune_mask.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp]
-        L.sgr_densify_compact.restype = i
-        L.sgr_densify_compact.argtypes = [i, vp, vp, vp, C.POINTER(C.c_int64), vp]
-        L.sgr_reset_opacity.restype = i
-        L.sgr_reset_opacity.argtypes = [i, vp, vp, vp, vp]
-        L.sgr_texture_cube_workspace_bytes.restype = C.c_size_t
-        L.sgr_texture_cube_workspace_bytes.argtypes = [i, i, i, i, C.c_int64]
-        L.sgr_texture_cube_forward.restype = i
-        L.sgr_texture_cube_forward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp]
-        L.sgr_texture_cube_backward.restype = i
-        L.sgr_texture_cube_backward.argtypes = [i, i, i, i, C.c_int64, vp, vp, vp, vp, vp]
-        L.sgr_sky_workspace_bytes.restype = C.c_size_t
-        L.sgr_sky_workspace_bytes.argtypes = [i, i, i, i, i]
-        L.sgr_sky_forward.restype = i
-        L.sgr_sky_forward.argtypes = [i, i, i, i] + [vp] * 9 + [i, vp, vp, vp]
-        L.sgr_sky_backward.restype = i
-        L.sgr_sky_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_sky_test_rays.restype = i
-        L.sgr_sky_test_rays.argtypes = [i, i, vp, vp, vp, vp, i, vp, vp, vp]
-        L.sgr_test_sort32_count.restype = i
-        L.sgr_test_sort32_count.argtypes = [vp, vp, vp, vp, C.c_uint32, i, i, vp, vp, vp, vp]
-        L.sgr_adam_span_elems.restype = i
-        L.sgr_adam_span_elems.argtypes = []
-        L.sgr_adam_step.restype = i
-        L.sgr_adam_step.argtypes = [vp, i, vp, i, C.c_int64, C.c_double, C.c_double, vp]
-        L.sgr_knn.restype = i
-        L.sgr_knn.argtypes = [i, vp, vp, ALLOC_FN, vp, vp]
-        L.sgr_export_internal.restype = i
-        L.sgr_export_internal.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp]
-        L.sgr_test_scan.restype = i
-        L.sgr_test_scan.argtypes = [vp, vp, C.c_size_t, i, vp, vp]
-        L.sgr_test_sort.restype = i
-        L.sgr_test_sort.argtypes = [vp, vp, vp, vp, C.c_uint32, i, vp, vp, vp]
-        L.sgr_test_sort32.restype = i
-        L.sgr_test_sort32.argtypes = [vp, vp, vp, vp, C.c_uint32, i, i, vp, vp, vp]
-        L.sgr_test_wave_sum.restype = i
-        L.sgr_test_wave_sum.argtypes = [vp, vp, vp, i, vp]
-        L.sgr_test_lds_atomic_order.restype = i
-        L.sgr_test_lds_atomic_order.argtypes = [vp, vp, i, vp]
-        L.sgr_test_exact_math.restype = i
-        L.sgr_test_exact_math.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.sgr_test_switches.restype = i
-        L.sgr_test_switches.argtypes = [i]
-        L.sgr_profile_enable.restype = i
-        L.sgr_profile_enable.argtypes = [i]
-        L.sgr_profile_select.restype = i
-        L.sgr_profile_select.argtypes = [i]
-        L.sgr_profile_sample.restype = i
-        L.sgr_profile_sample.argtypes = [i]
-        L.sgr_profile_read.restype = i
-        L.sgr_profile_read.argtypes = [vp, vp]
-        L.sgr_partial_row_floats.restype = i
-        L.sgr_partial_row_floats.argtypes = [i]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -193,3 +139,38 @@ def check(rc: int) -> int:
     if rc < 0:
         raise (SgrLazyError if rc == -SGR_E_LAZY else SgrError)(lib().sgr_last_error().decode())
     return rc
+
+
+def stream(device) -> C.c_void_p:
+    """The current HIP stream of ``device``, as the C ABI takes it."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    """Device address of tensor ``t`` as the C ABI takes it; None (NULL) for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class Grow:
+    """Growable byte buffer handed to the C side (resizeFunctional, rasterize_points.cu:27-33).
+
+    The callback closes over a one-element holder, NOT over this object: a bound method (`ALLOC_FN(self._alloc)`) made
+    `Grow -> callback -> method -> Grow` a reference cycle, and the buffer -- hundreds of MB of backward scratch per
+    call -- stayed allocated until Python's cyclic collector ran (round 5, tools/densify_gc_trace.py: +1.25 GB per
+    iteration at 5 M Gaussians for ~10 iterations in a row; the densify loop's "device allocations in the region")."""
+
+    def __init__(self, device):
+        holder = [torch.empty(0, dtype=torch.uint8, device=device)]
+
+        def alloc(nbytes, _user, holder=holder, device=device):
+            # (a larger block than asked for is fine -- the native side carves what it needs -- and ladder sizes repeat
+            # when the number of Gaussians drifts: _alloc.py)
+            holder[0] = torch.empty(_alloc.ladder(int(nbytes)), dtype=torch.uint8, device=device)
+            return holder[0].data_ptr()
+
+        self._holder = holder
+        self.cb = ALLOC_FN(alloc)
+
+    @property
+    def tensor(self):
+        return self._holder[0]

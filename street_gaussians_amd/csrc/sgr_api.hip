@@ -150,13 +150,6 @@ static int fail(int code, const std::string& msg) {
 }
 int sgr_set_error(int code, const std::string& msg) { return fail(code, msg); }  // for the other translation units
 
-#define SGR_HIP(call)                                                                            \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess)                                                                   \
-            return fail(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__));          \
-    } while (0)
-
 // reference CHECK_CUDA (auxiliary.h:166-173): with debug, synchronise after the stage and report
 #define SGR_STAGE(name)                                                                                   \
     do {                                                                                                  \

@@ -1174,10 +1174,7 @@ static void launch_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, unsig
 // floats per partial row for S semantic channels: the kernel's SMAX bucket writes ceil((11+SMAX)/4) float4
 // = NVAL of the instantiation that serves S (12 floats = 48 bytes at S = 0: the rows are only 16-byte aligned; padding
 // them to 64 bytes cost 25 % more row traffic in this kernel's stores and in the per-Gaussian row sum's loads)
-int sgr_partial_row_stride(int S) {
-    const int smax = S == 0 ? 0 : (S <= 4 ? 4 : (S <= 8 ? 8 : (S <= 12 ? 12 : (S <= 16 ? 16 : (S <= 20 ? 20 : (S <= 24 ? 24 : 32))))));
-    return (SGR_ROW_BASE + smax + 3) / 4 * 4;
-}
+int sgr_partial_row_stride(int S) { return (SGR_ROW_BASE + sgr_smax(S) + 3) / 4 * 4; }
 
 void sgr_launch_blend_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W,
                           int H, int S, const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* semantics, const float* alphas, const uint32_t* n_contrib,
@@ -1187,15 +1184,8 @@ void sgr_launch_blend_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, in
     if (gx <= 0 || gy == 0) return;
     const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
     const int stride = sgr_partial_row_stride(S);
-#define SGR_BWD(N) launch_bwd<N>(cull, dpp, det, v2, exact, tiles, s, ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, \
-                                 n_contrib, hit4, dL_dpix, dL_ddepth, dL_dalpha, dL_dsem, partials, stride, touched, row_limit, hlist, n_contrib_k, hl_flag)
-    if (S == 0) SGR_BWD(0);
-    else if (S <= 4) SGR_BWD(4);
-    else if (S <= 8) SGR_BWD(8);
-    else if (S <= 12) SGR_BWD(12);
-    else if (S <= 16) SGR_BWD(16);
-    else if (S <= 20) SGR_BWD(20);
-    else if (S <= 24) SGR_BWD(24);
-    else SGR_BWD(32);
-#undef SGR_BWD
+    sgr_with_smax(S, [&](auto N) {
+        launch_bwd<N>(cull, dpp, det, v2, exact, tiles, s, ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas,
+                      n_contrib, hit4, dL_dpix, dL_ddepth, dL_dalpha, dL_dsem, partials, stride, touched, row_limit, hlist, n_contrib_k, hl_flag);
+    });
 }

@@ -343,15 +343,8 @@ void sgr_launch_blend_fwd(bool cull, bool exact, int gx, int gy, const uint2* ra
                           uint32_t* n_contrib, uint8_t* hit4, uint32_t* hlist, uint32_t* n_contrib_k, hipStream_t s) {
     if (gx <= 0 || gy == 0) return;
     const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
-#define SGR_FWD(N) launch_fwd<N>(cull, exact, tiles, s, ranges, point_list, W, H, S, gx, gy, rec, semantics, bg, \
-                                 out_color, out_depth, out_alpha, out_semantic, n_contrib, hit4, hlist, n_contrib_k)
-    if (S == 0) SGR_FWD(0);
-    else if (S <= 4) SGR_FWD(4);
-    else if (S <= 8) SGR_FWD(8);
-    else if (S <= 12) SGR_FWD(12);
-    else if (S <= 16) SGR_FWD(16);
-    else if (S <= 20) SGR_FWD(20);
-    else if (S <= 24) SGR_FWD(24);
-    else SGR_FWD(32);
-#undef SGR_FWD
+    sgr_with_smax(S, [&](auto N) {
+        launch_fwd<N>(cull, exact, tiles, s, ranges, point_list, W, H, S, gx, gy, rec, semantics, bg, out_color, out_depth, out_alpha,
+                      out_semantic, n_contrib, hit4, hlist, n_contrib_k);
+    });
 }

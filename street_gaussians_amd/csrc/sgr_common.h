@@ -206,6 +206,29 @@ static inline size_t sgr_required(F carve) {
 
 #ifdef __HIPCC__
 #include <mutex>
+#include <string>
+#include <type_traits>
+
+// The kernel instantiation that serves S semantic channels: its SMAX bucket (0, 4, 8, ..., 24, 32).  The blend kernels,
+// the per-Gaussian row sums and the partial-row stride (sgr_partial_row_stride) all pick it here: the rows are written
+// and read with one layout.
+constexpr int sgr_smax(int S) { return S == 0 ? 0 : S <= 4 ? 4 : S <= 24 ? (S + 3) / 4 * 4 : SGR_SEM_MAX; }
+// f(std::integral_constant<int, sgr_smax(S)>{}); the walk visits the buckets in order, so exactly those are instantiated
+template <int N = 0, typename F>
+static inline void sgr_with_smax(int S, F&& f) {
+    if (sgr_smax(S) == N) f(std::integral_constant<int, N>{});
+    else if constexpr (N < SGR_SEM_MAX) sgr_with_smax<sgr_smax(N + 1)>(S, f);
+}
+
+// Records msg as the calling thread's sgr_last_error() and returns -code (sgr_api.hip).
+int sgr_set_error(int code, const std::string& msg);
+// A failed HIP runtime call returns -SGR_E_HIP from the calling function, with "<call>: <hipGetErrorString>".
+#define SGR_HIP(call)                                                                                                \
+    do {                                                                                                             \
+        hipError_t e__ = (call);                                                                                     \
+        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+
 // process-wide 256-byte device block of the current device, held (mutex) until the struct is destroyed (sgr_api.hip)
 struct SgrFlagBlock {
     uint32_t* ptr = nullptr;

@@ -17,14 +17,6 @@
 #include "../../include/sgr_densify.h"
 #include "sgr_common.h"
 
-int sgr_set_error(int code, const std::string& msg);
-
-#define DN_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 struct DnWork {
     uint32_t *flags, *offA, *offB, *offS, *offC, *tmp, *totals;  // totals: nA nB nS nC nClone nPrunedCand
 };
@@ -296,12 +288,12 @@ int sgr_densify_prune_mask(int n, const sgr_densify_params* p, int variant, cons
     SgrFlagBlock fb = sgr_acquire_flag_block();
     if (!fb.ptr) return sgr_set_error(SGR_E_HIP, "counter block allocation failed");
     uint32_t* cnt = fb.ptr + 16;  // words 16..19: the first words belong to sgr_visible_filter's flag
-    DN_HIP(hipMemsetAsync(cnt, 0, 16, stream));
+    SGR_HIP(hipMemsetAsync(cnt, 0, 16, stream));
     sgr_densify_prune_kernel<<<std::min((n + 255) / 256, 2048), 256, 0, stream>>>(n, *p, variant, xyz, scaling, rotation, opacity, sph, bx,
                                                                  box_normals, prune, cnt);
     uint32_t h[4];
-    DN_HIP(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, stream));
-    DN_HIP(hipStreamSynchronize(stream));
+    SGR_HIP(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, stream));
+    SGR_HIP(hipStreamSynchronize(stream));
     for (int k = 0; k < 4; k++) counts[k] = h[k];
     return 0;
 }
@@ -317,8 +309,8 @@ int sgr_densify_compact(int n, const uint8_t* prune, char* work, int32_t* sel, i
     sgr_launch_scan(w.offA, w.offA, (size_t)n, w.tmp, false, stream, w.totals + 0);
     sgr_densify_compact_kernel<<<(n + 255) / 256, 256, 0, stream>>>(n, prune, w.offA, sel);
     uint32_t t = 0;
-    DN_HIP(hipMemcpyAsync(&t, w.totals, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    DN_HIP(hipStreamSynchronize(stream));
+    SGR_HIP(hipMemcpyAsync(&t, w.totals, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SGR_HIP(hipStreamSynchronize(stream));
     *n_out = t;
     return 0;
 }
@@ -328,7 +320,7 @@ int sgr_reset_opacity(int N, float* opacity, float* exp_avg, float* exp_avg_sq, 
     if (N <= 0) return 0;
     if (!opacity) return sgr_set_error(SGR_E_INVALID, "opacity is required");
     sgr_reset_opacity_kernel<<<(N + 255) / 256, 256, 0, stream>>>(N, opacity, exp_avg, exp_avg_sq);
-    DN_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -353,11 +345,11 @@ int sgr_densify_plan(int N, const sgr_densify_params* p, const float* xyz_gradie
     sgr_launch_scan(w.offB, w.offB, (size_t)N, w.tmp, false, stream, w.totals + 1);
     sgr_launch_scan(w.offS, w.offS, (size_t)N, w.tmp, false, stream, w.totals + 2);
     sgr_launch_scan(w.offC, w.offC, (size_t)N, w.tmp, false, stream, w.totals + 3);
-    DN_HIP(hipMemsetAsync(w.totals + 4, 0, sizeof(uint32_t), stream));
+    SGR_HIP(hipMemsetAsync(w.totals + 4, 0, sizeof(uint32_t), stream));
     sgr_densify_count_kernel<<<std::min((N + 255) / 256, 1024), 256, 0, stream>>>(N, w);
     uint32_t t[8];
-    DN_HIP(hipMemcpyAsync(t, w.totals, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    DN_HIP(hipStreamSynchronize(stream));
+    SGR_HIP(hipMemcpyAsync(t, w.totals, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SGR_HIP(hipStreamSynchronize(stream));
     const int64_t nA = t[0], nB = t[1], nS = t[2], nC = t[3], nClone = t[4];
     const int64_t n_out = nA + nB + (int64_t)p->n_split * nC;
     const int64_t candidates = ((int64_t)N - nS) + nClone + (int64_t)p->n_split * nS;  // the set prune_mask is evaluated on
@@ -374,7 +366,7 @@ int sgr_densify_map(int N, const sgr_densify_params* p, const char* work, int32_
     if (!p || !work || !src || !kind || !sample_row) return sgr_set_error(SGR_E_INVALID, "p, work, src, kind and sample_row are required");
     const DnWork w = dn_carve((char*)sgr_align_up((size_t)work, 256), (size_t)N);
     sgr_densify_map_kernel<<<(N + 255) / 256, 256, 0, stream>>>(N, p->n_split, w, src, kind, sample_row);
-    DN_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -405,7 +397,7 @@ int sgr_densify_gather(int n_out, int width, const float* in, const int32_t* src
         default: DN_G(0); break;
     }
 #undef DN_G
-    DN_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -419,7 +411,7 @@ int sgr_densify_split_children(int n_out, int n_split, const int32_t* src, const
     sgr_densify_children_kernel<<<(n_out + 255) / 256, 256, 0, stream>>>(n_out, n_split, src, kind, sample_row, xyz_in,
                                                                         scaling_in, rotation_in, normals, xyz_out,
                                                                         scaling_out);
-    DN_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 

@@ -538,10 +538,6 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
     const float kx = (0.5f * (float)W) / lsc, ky = (0.5f * (float)H) / lsc;
     const unsigned nb = (P + SGR_GB_THREADS - 1) / SGR_GB_THREADS;
     const unsigned nb4 = (unsigned)(((size_t)P * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
-#define SGR_RS(N)                                                                                                    \
-    sgr_row_sum_kernel<N, false><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D, \
-                                                               dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink, kx, ky, exact, row_limit, \
-                                                               masked_color_out)
     // switch bit 9 / SGR_RS_WAVE=1: the wave-cooperative row sum instead of the four-lanes-per-Gaussian one (A/B: measured SLOWER on MI355X --
     // per-Gaussian backward stage 0.258 vs 0.213 ms at 1 M Gaussians, 1.14 vs 0.76 ms at 5 M, 0.83 vs 0.57 ms at 2 M + 19
     // channels: its segmented scan is 13 ds_bpermute per step and row chunk, more than the gather chains it removes)
@@ -549,35 +545,23 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
 #if SGR_WITH_VARIANTS
     const bool quads = !rs_wave;  // (sgr_test_switches bit 9)
     const unsigned nbw = (unsigned)((P + 64 * SGR_RSW_WAVES - 1) / (64 * SGR_RSW_WAVES));
-#define SGR_RSW(N)                                                                                                   \
-    sgr_row_sum_wave_kernel<N><<<nbw, 64 * SGR_RSW_WAVES, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D, \
-                                                                 dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink)
     if (quad) {  // the scalar-walk blend backward's rows (S = 0 only)
         sgr_row_sum_kernel<0, true><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
                                                                   dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink, kx, ky, exact, 0xffffffffu, masked_color_out);
     } else if (!quads) {
-        if (S == 0) SGR_RSW(0);
-        else if (S <= 4) SGR_RSW(4);
-        else if (S <= 8) SGR_RSW(8);
-        else if (S <= 12) SGR_RSW(12);
-        else if (S <= 16) SGR_RSW(16);
-        else if (S <= 20) SGR_RSW(20);
-        else if (S <= 24) SGR_RSW(24);
-        else SGR_RSW(32);
+        sgr_with_smax(S, [&](auto N) {
+            sgr_row_sum_wave_kernel<N><<<nbw, 64 * SGR_RSW_WAVES, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
+                                                                         dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink);
+        });
     } else
-#undef SGR_RSW
 #else
     (void)quad; (void)rs_wave;
 #endif
-    if (S == 0) SGR_RS(0);
-    else if (S <= 4) SGR_RS(4);
-    else if (S <= 8) SGR_RS(8);
-    else if (S <= 12) SGR_RS(12);
-    else if (S <= 16) SGR_RS(16);
-    else if (S <= 20) SGR_RS(20);
-    else if (S <= 24) SGR_RS(24);
-    else SGR_RS(32);
-#undef SGR_RS
+    sgr_with_smax(S, [&](auto N) {
+        sgr_row_sum_kernel<N, false><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
+                                                                   dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink, kx, ky, exact,
+                                                                   row_limit, masked_color_out);
+    });
     // dL/dmean2D, dL/dopacity, dL/dcolour are final from here on.  A failed record must not pass silently: the reducer's side
     // stream would wait on a stale record and read the colour gradient unsynchronised -- the error is picked up by the
     // failure is returned to sgr_backward_ex, which reports SGR_E_HIP

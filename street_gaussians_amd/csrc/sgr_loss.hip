@@ -13,8 +13,6 @@
 #include "../../include/sgr_loss.h"
 #include "sgr_common.h"
 
-int sgr_set_error(int code, const std::string& msg);
-
 #define SGR_LS_T 16           // output tile edge
 #define SGR_LS_R 5            // window radius (window_size 11)
 #define SGR_LS_IN (SGR_LS_T + 2 * SGR_LS_R)  // 26
@@ -370,12 +368,6 @@ sgr_lidar_bwd_kernel(int n, const float* __restrict__ depth, const float* __rest
     dacc[i] = ga;
 }
 
-#define LS_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 static inline dim3 tile_grid(int C, int H, int W) {
     return dim3((W + SGR_LS_T - 1) / SGR_LS_T, (H + SGR_LS_T - 1) / SGR_LS_T, C);
 }
@@ -399,7 +391,7 @@ int sgr_ssim_forward(int C, int H, int W, const float* img1, const float* img2, 
     else sgr_ssim_fwd_kernel<false><<<grid, 256, 0, stream>>>(H, W, img1, img2, mask, g, nullptr, workspace);
     sgr_final_sum_kernel<<<1, 256, 0, stream>>>(workspace, (size_t)grid.x * grid.y * grid.z,
                                                 1.0f / ((float)C * (float)H * (float)W), nullptr, out_ssim, 0);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -412,7 +404,7 @@ int sgr_ssim_backward(int C, int H, int W, const float* img1, const float* img2,
     static const SgrGauss11 g = make_window();
     sgr_ssim_bwd_kernel<<<tile_grid(C, H, W), 256, 0, stream>>>(H, W, C, img1, img2, mask, g, partials, upstream, dL_dimg1,
                                                                 1.0f, 0.0f, nullptr);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -426,7 +418,7 @@ int sgr_color_loss_backward(int C, int H, int W, const float* img1, const float*
     static const SgrGauss11 g = make_window();
     sgr_ssim_bwd_kernel<<<tile_grid(C, H, W), 256, 0, stream>>>(H, W, C, img1, img2, mask, g, partials, upstream, dL_dimg1,
                                                                 w_ssim, w_l1, l1_out);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -443,7 +435,7 @@ int sgr_l1_forward(int C, int H, int W, const float* a, const float* b, const ui
     const size_t plane = (size_t)H * W;
     sgr_l1_fwd_kernel<<<SGR_L1_BLOCKS, 256, 0, stream>>>(C, plane, a, b, mask, workspace, workspace + SGR_L1_BLOCKS);
     sgr_final_sum_kernel<<<1, 256, 0, stream>>>(workspace, SGR_L1_BLOCKS, 1.0f, workspace + SGR_L1_BLOCKS, out, 1);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -454,7 +446,7 @@ int sgr_l1_backward(int C, int H, int W, const float* a, const float* b, const u
     if (!a || !b || !out || !upstream || !dL_da) return sgr_set_error(SGR_E_INVALID, "a, b, out, upstream and dL_da are required");
     const size_t n = (size_t)C * H * W;
     sgr_l1_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(C, (size_t)H * W, a, b, mask, out, upstream, dL_da);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -464,7 +456,7 @@ int sgr_bce_forward(int n, int mode, const float* acc, const uint8_t* mask, floa
     if (!acc || !out || !workspace) return sgr_set_error(SGR_E_INVALID, "acc, out and workspace are required");
     sgr_bce_fwd_kernel<<<SGR_L1_BLOCKS, 256, 0, stream>>>(n, mode, acc, mask, workspace);
     sgr_final_sum_kernel<<<1, 256, 0, stream>>>(workspace, SGR_L1_BLOCKS, 1.0f / (float)n, nullptr, out, 0);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -474,7 +466,7 @@ int sgr_bce_backward(int n, int mode, const float* acc, const uint8_t* mask, con
     if (n <= 0 || (mode != SGR_BCE_SKY && mode != SGR_BCE_OBJECT)) return sgr_set_error(SGR_E_INVALID, "n > 0 and a valid mode are required");
     if (!acc || !upstream || !dL_dacc) return sgr_set_error(SGR_E_INVALID, "acc, upstream and dL_dacc are required");
     sgr_bce_bwd_kernel<<<(n + 255) / 256, 256, 0, stream>>>(n, mode, acc, mask, upstream, dL_dacc);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -490,8 +482,8 @@ int sgr_lidar_depth_forward(int n, const float* depth, const float* acc, const f
     if (n <= 0) return sgr_set_error(SGR_E_INVALID, "n must be positive");
     if (!depth || !acc || !lidar_depth || !out || !work) return sgr_set_error(SGR_E_INVALID, "depth, acc, lidar_depth, out and work are required");
     const LdWork w = ld_carve((char*)sgr_align_up((size_t)work, 256), (size_t)n);
-    LS_HIP(hipMemsetAsync(w.hist, 0, 4 * 256 * sizeof(uint32_t), stream));
-    LS_HIP(hipMemsetAsync(w.state, 0, 16 * sizeof(uint32_t), stream));
+    SGR_HIP(hipMemsetAsync(w.hist, 0, 4 * 256 * sizeof(uint32_t), stream));
+    SGR_HIP(hipMemsetAsync(w.state, 0, 16 * sizeof(uint32_t), stream));
     sgr_lidar_err_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, depth, acc, lidar_depth, mask, w);
     sgr_lidar_k_kernel<<<1, 1, 0, stream>>>(w, keep);
     for (int pass = 3; pass >= 0; pass--) {
@@ -500,7 +492,7 @@ int sgr_lidar_depth_forward(int n, const float* depth, const float* acc, const f
     }
     sgr_lidar_sum_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, w);
     sgr_lidar_final_kernel<<<1, 256, 0, stream>>>(w, out);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -512,7 +504,7 @@ int sgr_lidar_depth_backward(int n, const float* depth, const float* acc, const 
         return sgr_set_error(SGR_E_INVALID, "all arrays are required");
     const LdWork w = ld_carve((char*)sgr_align_up((size_t)const_cast<char*>(work), 256), (size_t)n);
     sgr_lidar_bwd_kernel<<<(n + 255) / 256, 256, 0, stream>>>(n, depth, acc, lidar_depth, out, w, upstream, dL_ddepth, dL_dacc);
-    LS_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 

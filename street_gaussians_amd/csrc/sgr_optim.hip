@@ -18,14 +18,6 @@
 
 #pragma clang fp contract(off)
 
-int sgr_set_error(int code, const std::string& msg);
-
-#define OP_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 static constexpr int SGR_ADAM_THREADS = 256;
 static constexpr int SGR_ADAM_VEC = 4;                                       // float4 per lane per span
 static constexpr int64_t SGR_ADAM_SPAN = SGR_ADAM_THREADS * SGR_ADAM_VEC * 4; // 4096 elements
@@ -146,6 +138,6 @@ int sgr_adam_step(const sgr_adam_chunk* chunks, int n_chunks, const sgr_adam_rec
     const unsigned grid = (unsigned)(n_spans < cap ? n_spans : cap);
     sgr_adam_step_kernel<<<grid, SGR_ADAM_THREADS, (size_t)n_records * sizeof(int32_t), (hipStream_t)stream_>>>(
         chunks, records, n_chunks, n_records, n_spans, k);
-    OP_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }

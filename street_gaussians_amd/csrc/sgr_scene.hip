@@ -22,8 +22,6 @@
 #include "../../include/sgr_scene_frame.h"
 #include "sgr_common.h"
 
-int sgr_set_error(int code, const std::string& msg);
-
 #define SGR_SC_THREADS 256
 #define SGR_SC_NPART 16  // per-chunk partials of an actor: G[9] (sum dx' x^T), T[3] (sum dx'), Q[4] (rotation path)
 
@@ -547,12 +545,6 @@ static int check_segments(int K, const sgr_scene_segment* segs, int M, int S) {
     return 0;
 }
 
-#define SC_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 // Host tables travel through a per-thread, grow-only PINNED staging buffer so that the copy is really asynchronous
 // (a pageable source makes hipMemcpyAsync stage or block); an event guards the buffer against reuse while the previous
 // call's copy is still in flight.
@@ -565,11 +557,11 @@ struct SgrPinnedStage {
 static int stage_get(size_t bytes, SgrPinnedStage** out) {
     static thread_local SgrPinnedStage stages[64];  // the guarding event belongs to a device: one stage per (thread, device)
     int dev = 0;
-    SC_HIP(hipGetDevice(&dev));
+    SGR_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return sgr_set_error(SGR_E_INVALID, "device index out of range");
     SgrPinnedStage& st = stages[dev];
     if (st.pending) {
-        SC_HIP(hipEventSynchronize(st.ev));
+        SGR_HIP(hipEventSynchronize(st.ev));
         st.pending = false;
     }
     if (bytes > st.cap) {
@@ -577,10 +569,10 @@ static int stage_get(size_t bytes, SgrPinnedStage** out) {
         st.p = nullptr;
         st.cap = 0;
         const size_t want = sgr_align_up(bytes + bytes / 2 + 4096, 4096);
-        SC_HIP(hipHostMalloc((void**)&st.p, want, hipHostMallocPortable));
+        SGR_HIP(hipHostMalloc((void**)&st.p, want, hipHostMallocPortable));
         st.cap = want;
     }
-    if (!st.ev) SC_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    if (!st.ev) SGR_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
     *out = &st;
     return 0;
 }
@@ -601,8 +593,8 @@ static int upload(const std::vector<SegDev>& sd, const std::vector<SgrChunk>& ch
     memcpy(st->p, sd.data(), sd.size() * sizeof(SegDev));
     memcpy(st->p + b0, chunks.data(), chunks.size() * sizeof(SgrChunk));
     if (spans) memcpy(st->p + b0 + b1, spans->data(), spans->size() * sizeof(SgrZeroDev));
-    SC_HIP(hipMemcpyAsync(base, st->p, b0 + b1 + b2, hipMemcpyHostToDevice, stream));
-    SC_HIP(hipEventRecord(st->ev, stream));
+    SGR_HIP(hipMemcpyAsync(base, st->p, b0 + b1 + b2, hipMemcpyHostToDevice, stream));
+    SGR_HIP(hipEventRecord(st->ev, stream));
     st->pending = true;
     *dsegs = (SegDev*)base;
     *dchunks = (SgrChunk*)(base + b0);
@@ -650,7 +642,7 @@ static int compose_forward(int K, const sgr_scene_segment* segs, int M, int S, f
     sgr_scene_fwd_kernel<<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, means3D, rotations, scales, opacities, semantics, corr);
     if (M == 16) sgr_scene_sh_fwd_kernel<16><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, shs, semantics);
     else sgr_scene_sh_fwd_kernel<0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, shs, semantics);
-    SC_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -697,7 +689,7 @@ static int compose_backward(int K, const sgr_scene_segment* segs, const sgr_scen
         if (ng) sgr_scene_corr_sum_kernel<<<(unsigned)ng, SGR_SC_THREADS, 0, stream>>>(cpart, nc, gpart);
         sgr_scene_corr_final_kernel<<<1, SGR_SC_THREADS, 0, stream>>>(gpart, ng, corr, corr_grad);
     }
-    SC_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -750,7 +742,7 @@ int sgr_scene_densification_stats(int K, const sgr_scene_stats_segment* segs, co
     int rc = upload(sd, chunks, 0, scratch, scratch_user, stream, &dsegs, &dchunks, nullptr);
     if (rc) return rc;
     sgr_scene_stats_kernel<<<(unsigned)chunks.size(), SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, dL_dmeans2D, radii);
-    SC_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 

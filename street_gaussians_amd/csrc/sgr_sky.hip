@@ -24,14 +24,6 @@
 #include "sgr_common.h"
 #include "sgr_cube.h"
 
-int sgr_set_error(int code, const std::string& msg);
-
-#define SKY_HIP(call)                                                                                      \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 namespace {
 
 // the camera of the ray contract: K^-1 (closed form in double, rounded once), R, T, and the origin o = -R^T T
@@ -339,7 +331,7 @@ int sgr_sky_forward(int H, int W, int R, int C, const float* rgb, const float* a
     sgr_sky_flag_kernel<<<blocks(HW), kBlock, 0, s>>>(a, v.flag);
     sgr_launch_scan(v.flag, v.flag, (size_t)HW, v.scan_tmp, true, s, v.count, nullptr, 1, nullptr, nullptr);
     sgr_sky_fwd_kernel<<<blocks(HW), kBlock, 0, s>>>(a, *sgr_cube_seam(), v.flag, v.rays, v.sky, out);
-    SKY_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -361,7 +353,7 @@ int sgr_sky_backward(int H, int W, int R, int C, const float* dL_dout, const flo
     } else {
         sgr_sky_bwd_kernel<false><<<nb, kBlock, 0, s>>>(a, dL_dout, v.flag, v.sky, dL_drgb, dL_dacc, w.up, w.part);
     }
-    SKY_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return sgr_texture_cube_backward_impl(1, 1, R, 3, HW, v.rays, w.up, dL_dcube, w.tex_work, v.count, s);
 }
 
@@ -373,7 +365,7 @@ int sgr_sky_test_rays(int H, int W, const float* K, const float* w2c, const floa
     const int64_t HW = (int64_t)H * W;
     const SkyArgs a{H, W, 1, HW, flags, nullptr, nullptr, nullptr, K, w2c, perturb_x, perturb_y, nullptr, nullptr};
     sgr_sky_rays_kernel<<<blocks(HW), kBlock, 0, (hipStream_t)stream_>>>(a, rays, kinv);
-    SKY_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -385,6 +377,6 @@ int sgr_test_sort32_count(uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, uin
     uint32_t* vals[2] = {vals0, vals1};
     const int cur = sgr_launch_sort_pairs32(keys, vals, n, end_bit, hist, scan_tmp, (hipStream_t)stream_, false, nullptr,
                                             nullptr, max_bits, 0, dev_n);
-    SKY_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return cur;
 }

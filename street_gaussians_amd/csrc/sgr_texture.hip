@@ -23,14 +23,6 @@
 #include "sgr_common.h"
 #include "sgr_cube.h"
 
-int sgr_set_error(int code, const std::string& msg);
-
-#define TX_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return sgr_set_error(SGR_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 // ---- forward --------------------------------------------------------------------------------------------------------
 template <int CT>
 __global__ void __launch_bounds__(256)
@@ -321,7 +313,7 @@ int sgr_texture_cube_forward(int Bt, int B, int R, int C, int64_t n, const float
     const SgrCubeSeam& sm = *sgr_cube_seam();
     if (C == 3) sgr_texture_cube_fwd_kernel<3><<<blocks(g.total), 256, 0, s>>>(Bt, R, C, n, g.total, tex, uv, out, sm);
     else sgr_texture_cube_fwd_kernel<0><<<blocks(g.total), 256, 0, s>>>(Bt, R, C, n, g.total, tex, uv, out, sm);
-    TX_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -351,7 +343,7 @@ int sgr_texture_cube_backward_impl(int Bt, int B, int R, int C, int64_t n, const
         sgr_texture_cube_gather_kernel<3><<<blocks(texels), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
     else
         sgr_texture_cube_gather_kernel<0><<<blocks(texels * C), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
-    TX_HIP(hipGetLastError());
+    SGR_HIP(hipGetLastError());
     return 0;
 }
 

@@ -24,7 +24,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _alloc, _native
-from ._native import SgrError, check
+from ._native import SgrError, check, ptr
 
 PARAMS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "semantic")  # optimiser group names (:409-412)
 
@@ -36,10 +36,6 @@ class _CParams(C.Structure):
 
 
 _VARIANTS = {None: 0, "base": 0, "bkgd": 1, "actor": 2}
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 # ---- memory for a loop that re-sizes under load ------------------------------------------------------------------------
@@ -123,21 +119,21 @@ def densify_and_prune(params: Dict[str, torch.Tensor], xyz_gradient_accum: torch
                   int(bool(prune_big)), int(grad_column), int(n_split), 0)
     counts = (C.c_int64 * 6)()
     work = torch.empty(L.sgr_densify_work_bytes(N), dtype=torch.uint8, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _native.stream(dev)
     acc, den, sc, op = f32(xyz_gradient_accum), f32(denom), f32(params["scaling"]), f32(params["opacity"])
     with torch.cuda.device(dev):
-        check(L.sgr_densify_plan(N, C.byref(cp), _p(acc), _p(den), _p(sc), _p(op), _p(work), counts, stream))
+        check(L.sgr_densify_plan(N, C.byref(cp), ptr(acc), ptr(den), ptr(sc), ptr(op), ptr(work), counts, stream))
         n_out, n_norm = int(counts[4]), int(counts[5])
         src = torch.empty(n_out, dtype=torch.int32, device=dev)
         kind = torch.empty(n_out, dtype=torch.uint8, device=dev)
         srow = torch.empty(n_out, dtype=torch.int32, device=dev)
-        check(L.sgr_densify_map(N, C.byref(cp), _p(work), _p(src), _p(kind), _p(srow), stream))
+        check(L.sgr_densify_map(N, C.byref(cp), ptr(work), ptr(src), ptr(kind), ptr(srow), stream))
 
         def gather(t, zero_new):
             t = f32(t)
             width = t[0].numel() if N else 0
             out = _alloc.empty((n_out,) + tuple(t.shape[1:]), torch.float32, dev)  # ladder-sized backing: see _alloc.py
-            check(L.sgr_densify_gather(n_out, width, _p(t), _p(src), _p(kind), int(zero_new), _p(out), stream))
+            check(L.sgr_densify_gather(n_out, width, ptr(t), ptr(src), ptr(kind), int(zero_new), ptr(out), stream))
             return out
 
         new_params = {k: gather(params[k], False) for k in PARAMS if k in params}
@@ -146,9 +142,9 @@ def densify_and_prune(params: Dict[str, torch.Tensor], xyz_gradient_accum: torch
                 normals = normal_source(n_norm, dev) if normal_source is not None else torch.randn(n_norm, 3, device=dev)
             if tuple(normals.shape) != (n_norm, 3):
                 raise RuntimeError(f"normals must have dimensions ({n_norm}, 3)")
-            check(L.sgr_densify_split_children(n_out, int(n_split), _p(src), _p(kind), _p(srow), _p(f32(params["xyz"])),
-                                               _p(sc), _p(f32(params["rotation"])), _p(f32(normals)), _p(new_params["xyz"]),
-                                               _p(new_params["scaling"]), stream))
+            check(L.sgr_densify_split_children(n_out, int(n_split), ptr(src), ptr(kind), ptr(srow), ptr(f32(params["xyz"])),
+                                               ptr(sc), ptr(f32(params["rotation"])), ptr(f32(normals)), ptr(new_params["xyz"]),
+                                               ptr(new_params["scaling"]), stream))
         new_states = None
         if states is not None:
             new_states = {k: (gather(a, True), gather(b, True)) for k, (a, b) in states.items()}
@@ -161,7 +157,7 @@ def _gather(L, t, src, kind, n_out, zero_new, stream, N):
     t = t.detach().to(torch.float32).contiguous()
     width = t[0].numel() if N else 0
     out = _alloc.empty((n_out,) + tuple(t.shape[1:]), torch.float32, t.device)
-    check(L.sgr_densify_gather(n_out, width, _p(t), _p(src), _p(kind), int(zero_new), _p(out), stream))
+    check(L.sgr_densify_gather(n_out, width, ptr(t), ptr(src), ptr(kind), int(zero_new), ptr(out), stream))
     return out
 
 
@@ -177,16 +173,16 @@ def _densify_two_step(params, xyz_gradient_accum, denom, *, max_grad, min_opacit
     cp = _CParams(float(max_grad), float(min_opacity), float(extent), float(percent_dense), float(percent_big_ws),
                   int(bool(prune_big)), int(grad_column), int(n_split), 1)
     counts = (C.c_int64 * 6)()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _native.stream(dev)
     acc, den, sc, op = f32(xyz_gradient_accum), f32(denom), f32(params["scaling"]), f32(params["opacity"])
     with torch.cuda.device(dev):
         work = torch.empty(L.sgr_densify_work_bytes(N), dtype=torch.uint8, device=dev)
-        check(L.sgr_densify_plan(N, C.byref(cp), _p(acc), _p(den), _p(sc), _p(op), _p(work), counts, stream))
+        check(L.sgr_densify_plan(N, C.byref(cp), ptr(acc), ptr(den), ptr(sc), ptr(op), ptr(work), counts, stream))
         n_cand, n_norm = int(counts[4]), int(counts[5])
         src = torch.empty(n_cand, dtype=torch.int32, device=dev)
         kind = torch.empty(n_cand, dtype=torch.uint8, device=dev)
         srow = torch.empty(n_cand, dtype=torch.int32, device=dev)
-        check(L.sgr_densify_map(N, C.byref(cp), _p(work), _p(src), _p(kind), _p(srow), stream))
+        check(L.sgr_densify_map(N, C.byref(cp), ptr(work), ptr(src), ptr(kind), ptr(srow), stream))
         # the candidates' geometry: gathered rows, split children computed
         cand = {k: _gather(L, params[k], src, kind, n_cand, False, stream, N) for k in ("xyz", "scaling", "rotation", "opacity")}
         if n_norm:
@@ -194,9 +190,9 @@ def _densify_two_step(params, xyz_gradient_accum, denom, *, max_grad, min_opacit
                 normals = normal_source(n_norm, dev) if normal_source is not None else torch.randn(n_norm, 3, device=dev)
             if tuple(normals.shape) != (n_norm, 3):
                 raise RuntimeError(f"normals must have dimensions ({n_norm}, 3)")
-            check(L.sgr_densify_split_children(n_cand, int(n_split), _p(src), _p(kind), _p(srow), _p(f32(params["xyz"])),
-                                               _p(sc), _p(f32(params["rotation"])), _p(f32(normals)), _p(cand["xyz"]),
-                                               _p(cand["scaling"]), stream))
+            check(L.sgr_densify_split_children(n_cand, int(n_split), ptr(src), ptr(kind), ptr(srow), ptr(f32(params["xyz"])),
+                                               ptr(sc), ptr(f32(params["rotation"])), ptr(f32(normals)), ptr(cand["xyz"]),
+                                               ptr(cand["scaling"]), stream))
         sphere = box = None
         if variant == "bkgd":
             if sphere_center is None or sphere_radius is None:
@@ -217,13 +213,13 @@ def _densify_two_step(params, xyz_gradient_accum, denom, *, max_grad, min_opacit
             box_normals = f32(box_normals)
         prune = torch.empty(n_cand, dtype=torch.uint8, device=dev)
         pc = (C.c_int64 * 4)()
-        check(L.sgr_densify_prune_mask(n_cand, C.byref(cp), _VARIANTS[variant], _p(cand["xyz"]), _p(cand["scaling"]),
-                                       _p(cand["rotation"]), _p(cand["opacity"]), sphere, box,
-                                       _p(box_normals) if box is not None else None, _p(prune), pc, stream))
+        check(L.sgr_densify_prune_mask(n_cand, C.byref(cp), _VARIANTS[variant], ptr(cand["xyz"]), ptr(cand["scaling"]),
+                                       ptr(cand["rotation"]), ptr(cand["opacity"]), sphere, box,
+                                       ptr(box_normals) if box is not None else None, ptr(prune), pc, stream))
         sel = torch.empty(n_cand, dtype=torch.int32, device=dev)
         n_out = C.c_int64(0)
         work2 = torch.empty(L.sgr_densify_work_bytes(n_cand), dtype=torch.uint8, device=dev)
-        check(L.sgr_densify_compact(n_cand, _p(prune), _p(work2), _p(sel), C.byref(n_out), stream))
+        check(L.sgr_densify_compact(n_cand, ptr(prune), ptr(work2), ptr(sel), C.byref(n_out), stream))
         n_out = int(n_out.value)
         sel = sel[:n_out]
         sel64 = sel.long()
@@ -266,6 +262,6 @@ def reset_opacity(opacity: torch.Tensor, state: Optional[Tuple[torch.Tensor, tor
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != out.numel():
                 raise SgrError("the Adam moments must be contiguous float32 tensors shaped like opacity")
     with torch.cuda.device(dev):
-        check(_native.lib().sgr_reset_opacity(out.numel(), _p(out), _p(a), _p(b),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        check(_native.lib().sgr_reset_opacity(out.numel(), ptr(out), ptr(a), ptr(b),
+                                              _native.stream(dev)))
     return out

@@ -7,21 +7,12 @@ of ~30 MIOpen / elementwise launches.  `train.py:100-104` keeps its two lines; o
 Tensors must live on the GPU; there is no CPU implementation in the product."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 
 from . import _native
-from ._native import SgrError, check
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._native import SgrError, check, ptr, stream
 
 
 def _prep(img, name):
@@ -54,7 +45,7 @@ class _SSIM(torch.autograd.Function):
         ws = torch.empty(L.sgr_ssim_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
         partials = torch.empty(3 * Cc * H * W, dtype=torch.float32, device=dev) if need else None
         with torch.cuda.device(dev):
-            check(L.sgr_ssim_forward(Cc, H, W, _p(img1), _p(img2), _p(mask), _p(out), _p(partials), _p(ws), _stream(dev)))
+            check(L.sgr_ssim_forward(Cc, H, W, ptr(img1), ptr(img2), ptr(mask), ptr(out), ptr(partials), ptr(ws), stream(dev)))
         ctx.save_for_backward(img1, img2, mask if mask is not None else torch.empty(0, device=dev), partials
                               if partials is not None else torch.empty(0, device=dev))
         ctx.has_mask = mask is not None
@@ -70,8 +61,8 @@ class _SSIM(torch.autograd.Function):
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(img1)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_ssim_backward(Cc, H, W, _p(img1), _p(img2), _p(mask) if ctx.has_mask else None,
-                                                  _p(partials), _p(up), _p(grad), _stream(dev)))
+            check(_native.lib().sgr_ssim_backward(Cc, H, W, ptr(img1), ptr(img2), ptr(mask) if ctx.has_mask else None,
+                                                  ptr(partials), ptr(up), ptr(grad), stream(dev)))
         return grad, None, None
 
 
@@ -84,7 +75,7 @@ class _L1(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=dev)
         ws = torch.empty(L.sgr_l1_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(L.sgr_l1_forward(Cc, H, W, _p(a), _p(b), _p(mask), _p(out), _p(ws), _stream(dev)))
+            check(L.sgr_l1_forward(Cc, H, W, ptr(a), ptr(b), ptr(mask), ptr(out), ptr(ws), stream(dev)))
         ctx.save_for_backward(a, b, mask if mask is not None else torch.empty(0, device=dev), out)
         ctx.has_mask = mask is not None
         return out[0]
@@ -97,8 +88,8 @@ class _L1(torch.autograd.Function):
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(a)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_l1_backward(Cc, H, W, _p(a), _p(b), _p(mask) if ctx.has_mask else None, _p(out),
-                                                _p(up), _p(grad), _stream(dev)))
+            check(_native.lib().sgr_l1_backward(Cc, H, W, ptr(a), ptr(b), ptr(mask) if ctx.has_mask else None, ptr(out),
+                                                ptr(up), ptr(grad), stream(dev)))
         return grad, None, None
 
 
@@ -110,7 +101,7 @@ class _BCE(torch.autograd.Function):
         out = torch.empty(1, dtype=torch.float32, device=dev)
         ws = torch.empty(L.sgr_l1_workspace_floats(1, 1, 1), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(L.sgr_bce_forward(n, mode, _p(acc), _p(mask), _p(out), _p(ws), _stream(dev)))
+            check(L.sgr_bce_forward(n, mode, ptr(acc), ptr(mask), ptr(out), ptr(ws), stream(dev)))
         ctx.save_for_backward(acc, mask)
         ctx.mode = mode
         return out[0]
@@ -122,7 +113,7 @@ class _BCE(torch.autograd.Function):
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(acc)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_bce_backward(acc.numel(), ctx.mode, _p(acc), _p(mask), _p(up), _p(grad), _stream(dev)))
+            check(_native.lib().sgr_bce_backward(acc.numel(), ctx.mode, ptr(acc), ptr(mask), ptr(up), ptr(grad), stream(dev)))
         return grad, None, None
 
 
@@ -134,8 +125,8 @@ class _Lidar(torch.autograd.Function):
         out = torch.empty(4, dtype=torch.float32, device=dev)
         work = torch.empty(L.sgr_lidar_work_bytes(n), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            check(L.sgr_lidar_depth_forward(n, _p(depth), _p(acc), _p(lidar), _p(mask), float(keep), _p(out), _p(work),
-                                            _stream(dev)))
+            check(L.sgr_lidar_depth_forward(n, ptr(depth), ptr(acc), ptr(lidar), ptr(mask), float(keep), ptr(out), ptr(work),
+                                            stream(dev)))
         ctx.save_for_backward(depth, acc, lidar, out, work)
         return out[0]
 
@@ -146,8 +137,8 @@ class _Lidar(torch.autograd.Function):
         up = upstream.reshape(1).to(torch.float32).contiguous()
         gd, ga = torch.empty_like(depth), torch.empty_like(acc)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_lidar_depth_backward(depth.numel(), _p(depth), _p(acc), _p(lidar), _p(out), _p(work),
-                                                         _p(up), _p(gd), _p(ga), _stream(dev)))
+            check(_native.lib().sgr_lidar_depth_backward(depth.numel(), ptr(depth), ptr(acc), ptr(lidar), ptr(out), ptr(work),
+                                                         ptr(up), ptr(gd), ptr(ga), stream(dev)))
         return gd, ga, None, None, None
 
 
@@ -203,8 +194,8 @@ class _ColorLoss(torch.autograd.Function):
                          dtype=torch.float32, device=dev)
         partials = torch.empty(3 * Cc * H * W, dtype=torch.float32, device=dev) if img.requires_grad else None
         with torch.cuda.device(dev):
-            check(L.sgr_l1_forward(Cc, H, W, _p(img), _p(gt), _p(mask), _p(out_l), _p(ws), _stream(dev)))
-            check(L.sgr_ssim_forward(Cc, H, W, _p(img), _p(gt), _p(mask), _p(out_s), _p(partials), _p(ws), _stream(dev)))
+            check(L.sgr_l1_forward(Cc, H, W, ptr(img), ptr(gt), ptr(mask), ptr(out_l), ptr(ws), stream(dev)))
+            check(L.sgr_ssim_forward(Cc, H, W, ptr(img), ptr(gt), ptr(mask), ptr(out_s), ptr(partials), ptr(ws), stream(dev)))
         ctx.save_for_backward(img, gt, mask if mask is not None else torch.empty(0, device=dev),
                               partials if partials is not None else torch.empty(0, device=dev), out_l)
         ctx.has_mask = mask is not None
@@ -223,9 +214,9 @@ class _ColorLoss(torch.autograd.Function):
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(img)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_color_loss_backward(Cc, H, W, _p(img), _p(gt), _p(mask) if ctx.has_mask else None,
-                                                        _p(partials), _p(out_l), ctx.w_l1, ctx.w_ssim, _p(up), _p(grad),
-                                                        _stream(dev)))
+            check(_native.lib().sgr_color_loss_backward(Cc, H, W, ptr(img), ptr(gt), ptr(mask) if ctx.has_mask else None,
+                                                        ptr(partials), ptr(out_l), ctx.w_l1, ctx.w_ssim, ptr(up), ptr(grad),
+                                                        stream(dev)))
         return grad, None, None, None, None
 
 

@@ -13,7 +13,6 @@ Its state reads and writes as ``torch.optim.Adam.state_dict()`` per model, and a
 ``densify.densify_and_prune(states=...)`` takes.  There is no CPU implementation: tensors must live on the GPU."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -289,10 +288,8 @@ class SegmentedAdam:
         with torch.cuda.device(dev):
             chunks = self._chunk_table()
             recs = _pinned_to(rec, dev)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            check(_native.lib().sgr_adam_step(C.c_void_p(chunks.data_ptr()), len(self.layout) * len(GROUPS),
-                                              C.c_void_p(recs.data_ptr()), len(rec), n_spans, self.betas[0],
-                                              self.betas[1], stream))
+            check(_native.lib().sgr_adam_step(_native.ptr(chunks), len(self.layout) * len(GROUPS), _native.ptr(recs), len(rec),
+                                              n_spans, self.betas[0], self.betas[1], _native.stream(dev)))
         # the contiguous copies of strided gradients and the tables are freed on this stream: reused only after the launch
 
     # ---- state ---------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _native
-from ._native import ALLOC_FN, SgrError, check
+from ._native import Grow, SgrError, check, ptr, stream
 
 SEG_STATIC, SEG_ACTOR = 0, 1
 SEM_LOGITS, SEM_PROBABILITIES = 0, 1
@@ -104,21 +104,6 @@ class Segment:
         return SEG_ACTOR if self.pose is not None else SEG_STATIC
 
 
-class _Grow:
-    def __init__(self, device):
-        self.device = device
-        self.tensor = None
-        self.cb = ALLOC_FN(self._alloc)
-
-    def _alloc(self, nbytes, _user):
-        self.tensor = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        return self.tensor.data_ptr()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _f32c(t, name):
     if t is None:
         return None
@@ -166,12 +151,12 @@ class _Compose(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=dev)
         outs = [torch.empty(N, 3, **f), torch.empty(N, 4, **f), torch.empty(N, 3, **f), torch.empty(N, 1, **f),
                 torch.empty(N, M, 3, **f), torch.empty(N, S, **f)]
-        grow = _Grow(dev)
+        grow = Grow(dev)
         frame, fkeep = _frame(corr)
         with torch.cuda.device(dev):
             check(_native.lib().sgr_scene_compose_forward_ex(
-                len(segs), arr, int(M), int(S), *[_ptr(o) if o.numel() else None for o in outs], frame, grow.cb, None,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                len(segs), arr, int(M), int(S), *[ptr(o) if o.numel() else None for o in outs], frame, grow.cb, None,
+                stream(dev)))
         ctx.segs, ctx.M, ctx.S = segs, int(M), int(S)
         ctx.save_for_backward(*[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
@@ -209,11 +194,11 @@ class _Compose(torch.autograd.Function):
         correction, corr = ctx.corr
         dcorr = torch.empty(7, dtype=torch.float32, device=dev) if corr is not None and ctx.needs_input_grad[3] else None
         frame, fkeep = _frame(corr, dcorr)
-        grow = _Grow(dev)
+        grow = Grow(dev)
         with torch.cuda.device(dev):
             check(_native.lib().sgr_scene_compose_backward_ex(
-                len(segs), arr, garr, M, S, *[_ptr(t) if t is not None and t.numel() else None for t in ins], frame,
-                grow.cb, None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                len(segs), arr, garr, M, S, *[ptr(t) if t is not None and t.numel() else None for t in ins], frame,
+                grow.cb, None, stream(dev)))
         del keep
         # kernels work in float32; hand autograd the dtype of each input
         grads = [g if g is None or g.dtype == t.dtype else g.to(t.dtype) for g, t in zip(grads, tensors)]
@@ -490,12 +475,12 @@ class _ComposeFlat(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=dev)
         outs = [torch.empty(N, 3, **f), torch.empty(N, 4, **f), torch.empty(N, 3, **f), torch.empty(N, 1, **f),
                 torch.empty(N, M, 3, **f), torch.empty(N, S, **f)]
-        grow = _Grow(dev)
+        grow = Grow(dev)
         cframe, fkeep = _frame(corr)
         with torch.cuda.device(dev):
             check(_native.lib().sgr_scene_compose_forward_ex(
-                len(arr), arr, int(M), int(S), *[_ptr(o) if o.numel() else None for o in outs], cframe, grow.cb, None,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                len(arr), arr, int(M), int(S), *[ptr(o) if o.numel() else None for o in outs], cframe, grow.cb, None,
+                stream(dev)))
         ctx.fs, ctx.frame, ctx.M, ctx.S = fs, frame, int(M), int(S)
         ctx.save_for_backward(*[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
@@ -518,11 +503,11 @@ class _ComposeFlat(torch.autograd.Function):
         cframe, fkeep = _frame(corr, dcorr, spans)
         dz = lambda t: None if t is None else _f32c(t, "grad")
         ins = [dz(d_means), dz(d_rot), dz(d_scale), dz(d_opac), dz(d_shs), dz(d_sem) if S else None]
-        grow = _Grow(dev)
+        grow = Grow(dev)
         with torch.cuda.device(dev):
             check(_native.lib().sgr_scene_compose_backward_ex(
-                len(arr), arr, garr, M, S, *[_ptr(t) if t is not None and t.numel() else None for t in ins], cframe,
-                grow.cb, None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                len(arr), arr, garr, M, S, *[ptr(t) if t is not None and t.numel() else None for t in ins], cframe,
+                grow.cb, None, stream(dev)))
         del keep
         if dcorr is not None:
             dcorr = dcorr.view(correction.shape).to(correction.dtype)
@@ -547,10 +532,10 @@ def densification_stats(models: Sequence[dict], dL_dmeans2D: torch.Tensor, radii
                                                         m["max_radii2D"].data_ptr())
     g = dL_dmeans2D.detach().to(torch.float32).contiguous()
     r = radii.to(torch.int32).contiguous()
-    grow = _Grow(dev)
+    grow = Grow(dev)
     with torch.cuda.device(dev):
-        check(_native.lib().sgr_scene_densification_stats(len(models), arr, _ptr(g), _ptr(r), grow.cb, None,
-                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        check(_native.lib().sgr_scene_densification_stats(len(models), arr, ptr(g), ptr(r), grow.cb, None,
+                                                          stream(dev)))
 
 
 class FlatStats:

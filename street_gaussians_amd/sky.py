@@ -7,23 +7,13 @@ with an autograd backward.  Nothing in the forward or the backward waits on the 
 Tensors must live on the GPU; there is no CPU implementation in the product."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _native
-from ._native import SgrError, check
+from ._native import SgrError, check, ptr, stream
 
 TRAIN, WHITE, CLAMP = 1, 2, 4  # include/sgr_sky.h SGR_SKY_*
 SAVED, SCRATCH = 0, 1
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class _SkyComposite(torch.autograd.Function):
@@ -36,8 +26,8 @@ class _SkyComposite(torch.autograd.Function):
         out = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         saved = torch.empty(L.sgr_sky_workspace_bytes(H, W, R, 3, SAVED), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            check(L.sgr_sky_forward(H, W, R, 3, _p(rgb), _p(acc), _p(cube), _p(K), _p(w2c), _p(mask), _p(px), _p(py),
-                                    _p(affine), flags, _p(out), _p(saved), _stream(dev)))
+            check(L.sgr_sky_forward(H, W, R, 3, ptr(rgb), ptr(acc), ptr(cube), ptr(K), ptr(w2c), ptr(mask), ptr(px), ptr(py),
+                                    ptr(affine), flags, ptr(out), ptr(saved), stream(dev)))
         ctx.save_for_backward(rgb, acc, affine)
         ctx.saved_state = saved
         ctx.flags = flags
@@ -58,8 +48,8 @@ class _SkyComposite(torch.autograd.Function):
         daff = torch.empty(3, 4, dtype=torch.float32, device=dev) if affine is not None else None
         scratch = torch.empty(L.sgr_sky_workspace_bytes(H, W, R, 3, SCRATCH), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            check(L.sgr_sky_backward(H, W, R, 3, _p(g), _p(rgb), _p(acc), _p(affine), ctx.flags, _p(ctx.saved_state),
-                                     _p(drgb), _p(dacc), _p(dcube), _p(daff), _p(scratch), _stream(dev)))
+            check(L.sgr_sky_backward(H, W, R, 3, ptr(g), ptr(rgb), ptr(acc), ptr(affine), ctx.flags, ptr(ctx.saved_state),
+                                     ptr(drgb), ptr(dacc), ptr(dcube), ptr(daff), ptr(scratch), stream(dev)))
         return drgb, dacc, dcube, daff, None, None, None, None, None, None
 
 

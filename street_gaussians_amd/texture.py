@@ -7,20 +7,10 @@ here through the ``nvdiffrast`` drop-in package.
 Tensors must live on the GPU; there is no CPU implementation in the product."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _native
-from ._native import SgrError, check
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
+from ._native import SgrError, check, ptr, stream
 
 
 class _TextureCube(torch.autograd.Function):
@@ -31,7 +21,7 @@ class _TextureCube(torch.autograd.Function):
         dev = tex.device
         out = torch.empty(B, H, W, Cc, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(_native.lib().sgr_texture_cube_forward(Bt, B, R, Cc, H * W, _p(tex), _p(uv), _p(out), _stream(dev)))
+            check(_native.lib().sgr_texture_cube_forward(Bt, B, R, Cc, H * W, ptr(tex), ptr(uv), ptr(out), stream(dev)))
         ctx.save_for_backward(uv)
         ctx.tex_shape = tex.shape
         return out
@@ -47,7 +37,7 @@ class _TextureCube(torch.autograd.Function):
         grad = torch.empty(ctx.tex_shape, dtype=torch.float32, device=dev)
         work = torch.empty(L.sgr_texture_cube_workspace_bytes(Bt, B, R, Cc, H * W), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            check(L.sgr_texture_cube_backward(Bt, B, R, Cc, H * W, _p(uv), _p(up), _p(grad), _p(work), _stream(dev)))
+            check(L.sgr_texture_cube_backward(Bt, B, R, Cc, H * W, ptr(uv), ptr(up), ptr(grad), ptr(work), stream(dev)))
         return grad, None
 
 

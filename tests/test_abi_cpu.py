@@ -28,6 +28,42 @@ def _declared():
     return names
 
 
+PROTO = re.compile(r"^(int|size_t|const char\s*\*)\s*(sgr_\w+)\s*\(([^)]*)\)", re.M)
+C_KINDS = {"int": "int", "int32_t": "int", "uint32_t": "int", "int64_t": "int64", "size_t": "size_t", "float": "float",
+           "double": "double"}
+C_RESTYPES = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+
+
+def _c_kind(param):
+    """pointer (arrays such as `int64_t counts[6]` included), callback (sgr_alloc_fn) or the scalar's kind"""
+    if param.split()[0] == "sgr_alloc_fn":
+        return "callback"
+    if "*" in param or "[" in param:
+        return "pointer"
+    return C_KINDS[" ".join(param.split()[:-1])]  # the type without the parameter's name
+
+
+def _prototypes():
+    """name -> (return type, parameter kinds) of every function include/*.h declares"""
+    protos = {}
+    for h in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(h).read(), flags=re.S)
+        for ret, name, params in PROTO.findall(text):
+            params = [p for p in params.split(",") if p.strip() not in ("", "void")]
+            protos[name] = (" ".join(ret.replace("*", "* ").split()), [_c_kind(p) for p in params])
+    return protos
+
+
+def _py_kind(t):
+    from street_gaussians_amd._native import ALLOC_FN
+    if t is ALLOC_FN:
+        return "callback"
+    if t is C.c_void_p or issubclass(t, C._Pointer):
+        return "pointer"
+    return {C.c_int: "int", C.c_uint32: "int", C.c_int64: "int64", C.c_size_t: "size_t", C.c_float: "float",
+            C.c_double: "double"}[t]
+
+
 def test_library_exports_every_declared_entry_point(lib):
     declared = _declared()
     assert {"sgr_forward", "sgr_backward", "sgr_mark_visible", "sgr_visible_filter", "sgr_knn", "sgr_last_error",
@@ -43,6 +79,12 @@ def test_python_binding_and_headers_agree(lib):
     assert not unknown, f"bound but not declared in include/*.h: {unknown}"
     for n in _native.SYMBOLS:
         assert hasattr(lib, n), n
+    # the binding's table and the prototypes agree: return type, parameter count and the kind of every parameter
+    protos = _prototypes()
+    for n, (restype, argtypes) in _native.SIGNATURES.items():
+        ret, kinds = protos[n]
+        assert restype is C_RESTYPES[ret], (n, ret)
+        assert [_py_kind(t) for t in argtypes] == kinds, n
 
 
 def test_headers_cite_the_reference_interfaces():
