@@ -188,7 +188,7 @@ int sgr_profile_select(int stage_mask);
 int sgr_profile_sample(int every);
 
 /* ---- introspection for parity tests: copies one internal array, densely packed, to dst (device). -------------
- * which: 0 depths f32[P] | 1 clamped u8[3P] | 2 means2D f32[2P] | 3 cov3D f32[6P] | 4 conic_opacity f32[4P]
+ * which: 0 depths f32[P] | 1 clamped u8[3P] | 2 means2D f32[2P] | 3 cov3D f32[6P] (sgr_export_cov3d) | 4 conic_opacity f32[4P]
  *        5 rgb f32[3P] | 6 tiles_touched u32[P] | 7 point_offsets u32[P] | 8 point_list u32[R]
  *        9 sorted keys u64[R] | 12 ranges u32[2T] | 13 n_contrib u32[H*W] | 14 extents f32[2P]
  *        15 hit record u8[R] (bit q: the forward blended the instance into quadrant q of its tile; entries behind the
@@ -206,6 +206,10 @@ int sgr_profile_sample(int every);
  *        20 u32[H*W]: n_contrib counted in entries of 19 (a pixel's last contributor's index in its tile's list + 1) */
 int sgr_export_internal(int which, int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
                         char* image_buffer, void* dst, void* stream);
+/* Array 3 is the one the buffers do not hold (sgr_export_internal refuses it): the preprocess and the per-Gaussian backward
+ * each recompute cov3D from scales, scale_modifier and rotations.  This writes f32[6P] by the same device function on the
+ * same operands (device arrays; rotations as handed to sgr_forward, not normalised). */
+int sgr_export_cov3d(int P, const float* scales, float scale_modifier, const float* rotations, float* dst, void* stream);
 
 /* ---- A/B switches (tests, tools/gpu_ab.sh), one bit each; the environment names in parentheses set the initial mask */
 enum {

@@ -329,7 +329,7 @@ def distCUDA2(points):
 
 
 _EXPORT = {"depths": (0, torch.float32, lambda P, R, N, T: (P,)), "clamped": (1, torch.uint8, lambda P, R, N, T: (P, 3)),
-           "means2D": (2, torch.float32, lambda P, R, N, T: (P, 2)),
+           "means2D": (2, torch.float32, lambda P, R, N, T: (P, 2)), "cov3D": (3, torch.float32, lambda P, R, N, T: (P, 6)),
            "conic_opacity": (4, torch.float32, lambda P, R, N, T: (P, 4)), "rgb": (5, torch.float32, lambda P, R, N, T: (P, 3)),
            "tiles_touched": (6, torch.int32, lambda P, R, N, T: (P,)), "point_offsets": (7, torch.int32, lambda P, R, N, T: (P,)),
            "point_list": (8, torch.int32, lambda P, R, N, T: (R,)), "keys": (9, torch.int64, lambda P, R, N, T: (R,)),
@@ -428,14 +428,28 @@ def test_switches(mask: int = -1) -> int:
     return int(_native.lib().sgr_test_switches(int(mask)))
 
 
-def export_internal(name, P, R, image_height, image_width, geomBuffer, binningBuffer, imageBuffer):
-    """Parity-test introspection (sgr_export_internal): dense copy of one internal array."""
+def export_internal(name, P, R, image_height, image_width, geomBuffer, binningBuffer, imageBuffer, scales=None,
+                    rotations=None, scale_modifier=1.0):
+    """Parity-test introspection (sgr_export_internal): dense copy of one internal array.  "cov3D" is the one array the
+    buffers do not hold; it is recomputed from ``scales`` / ``rotations`` / ``scale_modifier`` (sgr_export_cov3d)."""
     which, dtype, shp = _EXPORT[name]
     H, W = int(image_height), int(image_width)
     T = ((W + 15) // 16) * ((H + 15) // 16)
     dev = geomBuffer.device
     out = torch.zeros(shp(P, R, H * W, T), dtype=dtype, device=dev)
     vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    if name == "cov3D":
+        if scales is None or rotations is None:
+            raise SgrError("cov3D is not kept in the buffers: pass the forward's scales and rotations")
+        _dev_check(scales, "scales")
+        _dev_check(rotations, "rotations")
+        sc, rot = scales.detach().float().contiguous(), rotations.detach().float().contiguous()
+        if sc.shape != (P, 3) or rot.shape != (P, 4):
+            raise RuntimeError("scales must have dimensions (num_points, 3), rotations (num_points, 4)")
+        with torch.cuda.device(dev):
+            check(_native.lib().sgr_export_cov3d(int(P), vp(sc), float(scale_modifier), vp(rot), vp(out), _stream(dev)))
+            torch.cuda.current_stream(dev).synchronize()
+        return out
     with torch.cuda.device(dev):
         check(_native.lib().sgr_export_internal(which, P, R, W, H, vp(geomBuffer), vp(binningBuffer), vp(imageBuffer),
                                                 vp(out), _stream(dev)))

@@ -42,6 +42,7 @@ def _signatures():
         "sgr_image_bytes": (sz, [i, i]),
         "sgr_partial_row_floats": (i, [i]),
         "sgr_export_internal": (i, [i, i, i, i, i, vp, vp, vp, vp, vp]),
+        "sgr_export_cov3d": (i, [i, vp, f, vp, vp, vp]),
         "sgr_test_scan": (i, [vp, vp, sz, i, vp, vp]),
         "sgr_test_sort": (i, [vp, vp, vp, vp, u32, i, vp, vp, vp]),
         "sgr_test_sort32": (i, [vp, vp, vp, vp, u32, i, i, vp, vp, vp]),

@@ -1066,7 +1066,7 @@ int sgr_export_internal(int which, int P, int R, int width, int height, char* ge
         if (P <= 0) return 0;
         const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
         if (which == 17) { SGR_HIP(hipMemcpyAsync(dst, gv.header + 5, 4, hipMemcpyDeviceToDevice, stream)); return 0; }
-        if (which == 3) return fail(SGR_E_INVALID, "cov3D is not materialised (the backward recomputes it)");
+        if (which == 3) return fail(SGR_E_INVALID, "cov3D is not materialised (the backward recomputes it): sgr_export_cov3d");
         if (which == 7) {
             uint32_t mode = 0;
             SGR_HIP(hipMemcpyAsync(&mode, gv.header + 6, 4, hipMemcpyDeviceToHost, stream));
@@ -1104,6 +1104,30 @@ int sgr_export_internal(int which, int P, int R, int width, int height, char* ge
     if (which == 13) { SGR_HIP(hipMemcpyAsync(dst, iv.n_contrib, N * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
     if (which == 20) { SGR_HIP(hipMemcpyAsync(dst, iv.n_contrib_k, N * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
     return fail(SGR_E_INVALID, "unknown internal array");
+}
+
+// cov3D is not kept in the geometry buffer: the preprocess and the per-Gaussian backward both call sgr_cov3d on the inputs.
+// The export does the same -- the same function on the same operands, one Gaussian per thread.
+__global__ void sgr_export_cov3d_kernel(int P, const float* __restrict__ scales, float mod, const float* __restrict__ rotations,
+                                        float* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const float sc[3] = {scales[3 * (size_t)i], scales[3 * (size_t)i + 1], scales[3 * (size_t)i + 2]};
+    const float rot[4] = {rotations[4 * (size_t)i], rotations[4 * (size_t)i + 1], rotations[4 * (size_t)i + 2],
+                          rotations[4 * (size_t)i + 3]};
+    float cov3D[6];
+    sgr_cov3d(sc, mod, rot, cov3D);
+#pragma unroll
+    for (int k = 0; k < 6; k++) dst[6 * (size_t)i + k] = cov3D[k];
+}
+int sgr_export_cov3d(int P, const float* scales, float scale_modifier, const float* rotations, float* dst, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 1;
+    if (P <= 0) return 0;
+    if (!scales || !rotations || !dst) return fail(SGR_E_INVALID, "sgr_export_cov3d needs scales, rotations and a destination");
+    sgr_export_cov3d_kernel<<<(P + 255) / 256, 256, 0, stream>>>(P, scales, scale_modifier, rotations, dst);
+    SGR_STAGE("export cov3D");
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

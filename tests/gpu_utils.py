@@ -61,7 +61,10 @@ def raw_forward(kw):
     res = dict(R=R, color=color, depth=depth, alpha=alpha, semantic=semantic, radii=radii, geom=gb, binning=bb, img=ib)
 
     def internal(name):
-        return _C.export_internal(name, P, R, kw["image_height"], kw["image_width"], gb, bb, ib)
+        # (cov3D is the one array the buffers do not hold: the library recomputes it from the call's scales / rotations)
+        extra = dict(scales=dev(kw.get("scales")), rotations=dev(kw.get("rotations")),
+                     scale_modifier=kw.get("scale_modifier", 1.0)) if name == "cov3D" else {}
+        return _C.export_internal(name, P, R, kw["image_height"], kw["image_width"], gb, bb, ib, **extra)
     return res, internal
 
 
@@ -252,6 +255,208 @@ def exact_mode_against_reference_kernels(kw, wts, S, label, rf=None, gref=None, 
     if own:
         rf.free()
     return res, g
+
+
+# Backward on identical inputs (oracle_backward_same_state): |a-b| <= 1e-4*max(|a|,|b|) + 2e-6*max|b|.  The few
+# elements outside are single (pixel, Gaussian) alpha-threshold flips (v_exp_f32 vs expf); measured on MI355X
+# (profiles/r2/parity_measured.jsonl) and gated just above.
+# Measured maxima over the whole suite: 2.7e-3 of a tensor's elements outside (7 of 2554), worst error 3.2e-4 of the
+# tensor's scale.
+SAME_STATE_GATE = dict(rel=1e-4, abs_frac=2e-6, max_outlier_frac=4e-3, cap=1e-3)
+
+
+def tile_tops(n_contrib, H, W):
+    """Per tile, the largest n_contrib of its pixels: how far into its list the tile's forward got, [gy, gx]."""
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    pad = np.zeros((gy * 16, gx * 16), np.int64)
+    pad[:H, :W] = np.asarray(n_contrib).reshape(H, W)
+    return pad.reshape(gy, 16, gx, 16).max(axis=(1, 3))
+
+
+def check_hit_list(arr, H, W, label=""):
+    """The compact hit list (include/sgr.h exports 19 / 20) against its definition from the hit record (15) and n_contrib
+    (13), entry for entry: per tile, from its range's start, the ascending positions of the non-zero hit bytes; per pixel,
+    n_contrib recounted in those entries; every pixel's last contributor is in the list.  Both arrays are undefined behind
+    what a tile processed (the record behind its last batch, the list behind its count), so a tile is checked over
+    [0, largest n_contrib of its pixels).  arr: numpy arrays ranges, n_contrib, hits, hit_list, n_contrib_k.
+    -> the number of tiles that had anything to check."""
+    ranges = np.asarray(arr["ranges"]).view(np.uint32).reshape(-1, 2).astype(np.int64)
+    nc = np.asarray(arr["n_contrib"]).view(np.uint32).reshape(H, W).astype(np.int64)
+    nk = np.asarray(arr["n_contrib_k"]).view(np.uint32).reshape(H, W).astype(np.int64)
+    hits = np.asarray(arr["hits"])
+    hl = np.asarray(arr["hit_list"]).view(np.uint32).astype(np.int64)
+    gx = (W + 15) // 16
+    checked = 0
+    for t, (a, b) in enumerate(ranges):
+        ty, tx = divmod(t, gx)
+        blk_c = nc[ty * 16:(ty + 1) * 16, tx * 16:(tx + 1) * 16]
+        blk_k = nk[ty * 16:(ty + 1) * 16, tx * 16:(tx + 1) * 16]
+        top = int(blk_c.max()) if blk_c.size else 0
+        if top == 0:
+            assert int(blk_k.max(initial=0)) == 0, (label, t)
+            continue
+        assert top <= b - a, (label, t)
+        pos = np.nonzero(hits[a:a + top])[0]  # the record is defined for the batches the tile processed: covers [0, top)
+        assert np.array_equal(hl[a:a + len(pos)], pos), (label, t)
+        # per pixel: entries of the list in front of its last contributor + 1 ... and the last contributor is in the list
+        want = np.searchsorted(pos, blk_c, side="left")  # = #{entries with position < n_contrib}
+        assert np.array_equal(blk_k, want), (label, t)
+        lastpos = blk_c[blk_c > 0] - 1
+        assert np.all(hits[a + lastpos] != 0), (label, t)
+        checked += 1
+    return checked
+
+
+def check_dead_marks(arr, point_list, rect, tmask, H, W, label=""):
+    """"Marked dead" in the strict mode: a list position whose tile lies outside its Gaussian's cut-down rect / tile mask
+    (exports 16 / 18 of a forward under the default rects) was blended nowhere -- its hit byte is 0.  Checked over the part
+    of each tile's record that is defined, [0, largest n_contrib of the tile's pixels).  -> (dead positions checked, all)."""
+    gx = (W + 15) // 16
+    ranges = np.asarray(arr["ranges"]).view(np.uint32).reshape(-1, 2).astype(np.int64)
+    pl = np.asarray(point_list).astype(np.int64).reshape(-1)
+    n = ranges[:, 1] - ranges[:, 0]
+    assert int(n.sum()) == pl.size, label
+    tile_of = np.repeat(np.arange(ranges.shape[0], dtype=np.int64), n)
+    rel = np.arange(pl.size, dtype=np.int64) - ranges[tile_of, 0]
+    assert (rel >= 0).all(), label
+    tx, ty = tile_of % gx, tile_of // gx
+    r = np.asarray(rect).astype(np.int64)[pl]
+    inside = (tx >= r[:, 0]) & (tx < r[:, 2]) & (ty >= r[:, 1]) & (ty < r[:, 3])
+    mk = np.asarray(tmask).view(np.uint64).reshape(-1)[pl]
+    j = np.clip((ty - r[:, 1]) * (r[:, 2] - r[:, 0]) + (tx - r[:, 0]), 0, 63).astype(np.uint64)
+    inside &= (mk == 0) | (((mk >> j) & np.uint64(1)) == 1)
+    defined = rel < tile_tops(np.asarray(arr["n_contrib"]).view(np.uint32), H, W).reshape(-1)[tile_of]
+    dead = defined & ~inside
+    hits = np.asarray(arr["hits"])
+    assert not hits[dead].any(), f"{label}: {int((hits[dead] != 0).sum())} instances outside their cut-down rect were blended"
+    return int(dead.sum()), int(pl.size)
+
+
+def _strict_mask():
+    return _C.test_switches(-1) | _C.EXACT | _C.REF_RECT
+
+
+def _reference_arrays(rf):
+    """-> (kind, get): the reference's forward state behind one accessor that returns numpy arrays.  kind "golden": a dict
+    of committed arrays (tests/golden/*.npz); "kernels": oracle/_ref's build of the reference's kernels (device tensors);
+    "oracle": the C oracle's ForwardResult."""
+    u = {"tiles_touched": np.uint32, "point_offsets": np.uint32, "point_list": np.uint32, "keys": np.uint64, "ranges": np.uint32,
+         "n_contrib": np.uint32}
+    if isinstance(rf, dict):
+        def get(k):
+            if k == "point_offsets":  # not in the files: the reference's inclusive scan of its tiles_touched
+                return np.cumsum(np.asarray(rf["tiles_touched"]).astype(np.uint32), dtype=np.uint32)
+            if k == "num_rendered":
+                return int(rf["num_rendered"])
+            return np.asarray(rf[k]).view(u[k]) if k in u else np.asarray(rf[k])
+        return "golden", get
+    if hasattr(rf, "internal"):
+        def get(k):
+            if k == "num_rendered":
+                return int(rf.num_rendered)
+            return npy(rf.internal(k)).view(u[k]) if k in u else npy(getattr(rf, k))
+        return "kernels", get
+
+    def get(k):
+        if k == "num_rendered":
+            return int(rf.num_rendered)
+        return np.asarray(getattr(rf, k))
+    return "oracle", get
+
+
+def strict_mode_against_reference(kw, wts, S, label, rf=None, gref=None, allow=None):
+    """The library in its STRICTLY CONFORMING configuration -- parity arithmetic on the reference's own tile rects,
+    `_C.EXACT | _C.REF_RECT` (SGR_EXACT=1 SGR_REF_RECT=1), the one bench.py reports -- against a reference, end to end,
+    with nothing of the library's own between the two sides: the binning arrays are compared with the reference's ENTRY FOR
+    ENTRY (no filtering through exported rects or masks).
+
+    `rf` / `gref`: the reference's forward state and gradients --
+      * None: oracle/_ref's strict build of the reference's kernels is run here (and re-run, for its own spread);
+      * a RefForward with its gradient dict, or a dict of golden arrays (forward arrays by name, gradients as "g_" + name;
+        a file without `keys` skips that one array);
+      * the C oracle's ForwardResult (`gref` unused): the leg that runs where oracle/_ref is absent.
+
+    Asserted against the reference's kernels / a golden file: num_rendered, radii, tiles_touched, point_offsets, point_list,
+    keys, ranges, n_contrib identical; alpha / depth / semantic bit-identical; colour within rel 1e-4 without an outlier;
+    every gradient tensor inside strict_gate (rel 1e-4 + 2e-6 of the scale) with the allowance
+    exact_mode_against_reference_kernels uses (`allow`: {tensor: count}, the documented exceptions of a case, in elements
+    outside the gate of whichever reference is compared).  Against the C oracle: the integer arrays identical all the same; images and
+    n_contrib within the image_close / flip bound of test_forward_matches_oracle and gradients through
+    oracle_backward_same_state with SAME_STATE_GATE -- the C oracle evaluates exp() with the host's libm expf, which differs
+    from the device's in rare last bits, so bit identity of what passes through exp() is NOT promised against it.
+
+    Whatever the reference: a second backward over the same forward state is bit-identical; the compact hit list and
+    n_contrib_k are what check_hit_list defines; every list position outside its Gaussian's cut-down rect has a zero hit
+    byte (check_dead_marks).  Returns (res, g, internal)."""
+    own = rf is None
+    rerun = {}
+    if own:
+        from oracle import ref
+        rf = ref.forward(**kw)
+        gref = ref.backward(rf, wts["color"], wts["depth"], wts["alpha"], wts["semantic"] if S else None)
+        gref_b = ref.backward(rf, wts["color"], wts["depth"], wts["alpha"], wts["semantic"] if S else None)
+        for k in GRAD_NAMES:
+            if k == "semantics" and not S:
+                continue
+            rerun[k] = count_outside(npy(gref_b[k]).reshape(-1), npy(gref[k]).reshape(-1))
+        _log(dict(kind="ref_rerun", name=f"strict {label}", outside=rerun))
+    kind, get = _reference_arrays(rf)
+    H, W = int(kw["image_height"]), int(kw["image_width"])
+    with switches(_strict_mask()):
+        res, internal = raw_forward(kw)
+        g = raw_backward(kw, res, wts)
+        g2 = raw_backward(kw, res, wts)
+        torch.cuda.synchronize()
+        arr = {k: npy(internal(k)).copy() for k in ["ranges", "n_contrib", "hits", "hit_list", "n_contrib_k"]}
+        lists = {k: npy(internal(k)).view(dt).copy() for k, dt in [("tiles_touched", np.uint32), ("point_offsets", np.uint32),
+                                                                   ("point_list", np.uint32), ("keys", np.uint64)]}
+        R_ref = int(internal("num_rendered_reference")[0])
+    # ---- the lists, verbatim
+    R = get("num_rendered")
+    assert res["R"] == R == R_ref, (label, res["R"], R, R_ref)
+    assert np.array_equal(npy(res["radii"]).reshape(-1), get("radii").reshape(-1)), f"{label}: radii"
+    for k in ["tiles_touched", "point_offsets", "point_list", "keys"]:
+        if kind == "golden" and k == "keys" and "keys" not in rf:
+            continue
+        assert np.array_equal(lists[k].reshape(-1), get(k).reshape(-1)), f"{label}: {k} differs from the reference's"
+    assert np.array_equal(arr["ranges"].view(np.uint32).reshape(-1), get("ranges").reshape(-1)), f"{label}: ranges"
+    nc = arr["n_contrib"].view(np.uint32).reshape(-1)
+    # ---- images, n_contrib, gradients
+    if kind == "oracle":
+        for k in ["color", "depth", "alpha"] + (["semantic"] if S else []):
+            image_close(npy(res[k]), get(k), name=f"strict {label}: {k}")
+        assert (nc != get("n_contrib").reshape(-1)).mean() <= 1e-3, f"{label}: n_contrib differs beyond exp-ulp flips"
+        from oracle import oracle
+        same = oracle_backward_same_state(oracle, rf, res, wts, S)
+        for k in GRAD_NAMES:
+            gate = dict(SAME_STATE_GATE)
+            if (allow or {}).get(k):  # a documented per-case, per-tensor exception: that many elements, the cap unchanged
+                gate["max_outlier_frac"] = max(gate["max_outlier_frac"], (allow[k] + 0.5) / max(same[k].size, 1))
+            grad_close(npy(g[k]).reshape(same[k].shape), same[k], name=f"strict same-state {label}:{k}", **gate)
+    else:
+        assert np.array_equal(nc, get("n_contrib").reshape(-1)), f"{label}: n_contrib differs from the reference's"
+        for k in ["alpha", "depth"] + (["semantic"] if S else []):
+            assert np.array_equal(npy(res[k]).reshape(-1), get(k).reshape(-1)), f"{label}: {k} image not bit-identical"
+        image_close(npy(res["color"]).reshape(-1), get("color").reshape(-1), rel=1e-4, name=f"strict {label}: color", max_outliers=0)
+        for k in GRAD_NAMES:
+            if k == "semantics" and not S:
+                continue
+            want = np.asarray(gref["g_" + k]) if kind == "golden" else npy(gref[k])
+            strict_gate(npy(g[k]).reshape(-1), want.reshape(-1), name=f"strict {label}: {k}",
+                        allow=max((allow or {}).get(k, 0), conditioned_allowance(k, want.size, rerun.get(k, 0))))
+    # ---- strict is as deterministic as the other modes
+    for k in g:
+        assert torch.equal(g[k], g2[k]), f"{label}: strict mode: {k} not deterministic"
+    # ---- the compact hit list is what it says, and "marked dead" means never blended
+    checked = check_hit_list(arr, H, W, label)
+    with switches(_C.test_switches(-1) & ~(_C.REF_RECT | _C.REF_RECT_PLAIN)):
+        _, int_d = raw_forward(kw)
+        rect, tmask = npy(int_d("tile_rect")), npy(int_d("tile_mask"))
+    ndead, nall = check_dead_marks(arr, lists["point_list"], rect, tmask, H, W, label)
+    _log(dict(kind="strict_lists", name=label, R=R, tiles_checked=checked, dead_checked=ndead, reference=kind))
+    if own:
+        rf.free()
+    return res, g, internal
 
 
 def restrict_binning(internal, point_list, ranges, W, H, keys=None, n_contrib=None):

@@ -206,3 +206,16 @@ def test_switch_environment_names_set_the_initial_mask(lib):
         got = list(pool.map(initial_mask, [name for name, _ in cases]))
     for (name, m), g in zip(cases, got):
         assert g == (m if (variants or not m & VARIANT_BITS) else 0), (name, g)
+
+
+def test_export_table_lists_every_array_the_header_names():
+    """`_C._EXPORT` (the names tests read internal arrays by) against the `which` numbers of sgr_export_internal's comment in
+    include/sgr.h: every array the header names has a row, cov3D (3, the one sgr_export_cov3d recomputes) included."""
+    import re
+    from street_gaussians_amd import _C
+    text = open(os.path.join(ROOT, "include", "sgr.h")).read()
+    block = text[text.index("* which: 0 depths"):text.index("int sgr_export_internal(")]
+    named = {int(m) for m in re.findall(r"(?:which: |\| |\* {8})(\d+) (?=[a-z])", block)}
+    assert named == {v[0] for v in _C._EXPORT.values()}, sorted(named)
+    which, dtype, shape = _C._EXPORT["cov3D"]
+    assert which == 3 and shape(7, 0, 0, 0) == (7, 6) and "sgr_export_cov3d" in block

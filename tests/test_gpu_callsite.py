@@ -3,7 +3,10 @@ StreetGaussianRenderer.render_kernel (/root/reference/lib/models/street_gaussian
 script/test_gaussian_rasterization.py by executing those sources with a recording rasterizer
 (tests/golden/make_callsite_fixture.py, pinned by tests/test_callsite_cpu.py) -- go through the drop-in
 GaussianRasterizationSettings / GaussianRasterizer exactly as captured (keyword call, None where the reference passes None,
-means2D a [P,3] tensor that requires grad) and are compared with the C oracle on the same inputs."""
+means2D a [P,3] tensor that requires grad) and are compared with the C oracle on the same inputs.
+
+Strict leg (test_replay_reference_call_site_strict): the same replay under EXACT | REF_RECT (SGR_EXACT=1 SGR_REF_RECT=1), where
+the drop-in's num_rendered is the oracle's exactly; images, viewspace_points.grad and leaf gradients under the same gates."""
 import glob
 import os
 
@@ -12,8 +15,9 @@ import pytest
 import torch
 
 from golden import make_callsite_fixture as mk
-from gpu_utils import grad_close, image_close, npy
+from gpu_utils import grad_close, image_close, npy, switches
 from oracle import oracle
+from street_gaussians_amd import _C
 from street_gaussians_amd import rasterizer as rast_mod
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +27,19 @@ FIX = sorted(glob.glob(os.path.join(HERE, "golden", "callsite", "*.npz")))
 
 @pytest.mark.parametrize("path", FIX, ids=[os.path.basename(p)[:-4] for p in FIX])
 def test_replay_reference_call_site(path):
+    _replay(path, strict=False)
+
+
+@pytest.mark.parametrize("path", FIX, ids=[os.path.basename(p)[:-4] for p in FIX])
+def test_replay_reference_call_site_strict(path):
+    """The same five call sites under EXACT | REF_RECT, the configuration bench.py reports: the drop-in then renders the
+    reference's whole list, so its num_rendered is the oracle's exactly."""
+    with switches(_C.test_switches(-1) | _C.EXACT | _C.REF_RECT):
+        _replay(path, strict=True)
+        torch.cuda.synchronize()
+
+
+def _replay(path, strict):
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
     st, kw, meta = mk.load(path)
     cu = lambda t: None if t is None else t.cuda()
@@ -49,7 +66,10 @@ def test_replay_reference_call_site(path):
                         sh_degree=st["sh_degree"], scale_modifier=st["scale_modifier"], shs=kw["shs"],
                         colors_precomp=kw["colors_precomp"], scales=kw["scales"], rotations=kw["rotations"],
                         cov3D_precomp=kw["cov3D_precomp"], semantics=kw["semantics"])
-    assert 0 < rast_mod.last_num_rendered() <= fw.num_rendered  # (tile rects cut down to where alpha >= 1/255 is possible)
+    if strict:
+        assert rast_mod.last_num_rendered() == fw.num_rendered
+    else:
+        assert 0 < rast_mod.last_num_rendered() <= fw.num_rendered  # (tile rects cut down to where alpha >= 1/255 is possible)
     assert (npy(radii) == fw.radii).all()
     S = 0 if kw["semantics"] is None else kw["semantics"].shape[1]
     assert semantic.shape == (S, st["image_height"], st["image_width"])

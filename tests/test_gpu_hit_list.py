@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_utils import npy, raw_backward, raw_forward, switches
+from gpu_utils import check_hit_list, npy, raw_backward, raw_forward, switches
 from helpers import oracle_kwargs
 from street_gaussians_amd import _C
 from street_gaussians_amd import synthetic as syn
@@ -61,31 +61,8 @@ def test_compact_walk_equals_positional_walk_and_the_list_is_what_it_says(name, 
     for k in g_old:
         assert np.array_equal(g_new[k], g_old[k]), (name, mode, k, int((g_new[k] != g_old[k]).sum()))
 
-    # the list against its definition
-    ranges = arr["ranges"].view(np.uint32).reshape(-1, 2).astype(np.int64)
-    nc = arr["n_contrib"].view(np.uint32).reshape(H, W).astype(np.int64)
-    nk = arr["n_contrib_k"].view(np.uint32).reshape(H, W).astype(np.int64)
-    hits = arr["hits"]
-    hl = arr["hit_list"].view(np.uint32).astype(np.int64)
-    gx = (W + 15) // 16
-    checked = 0
-    for t, (a, b) in enumerate(ranges):
-        ty, tx = divmod(t, gx)
-        blk_c = nc[ty * 16:(ty + 1) * 16, tx * 16:(tx + 1) * 16]
-        blk_k = nk[ty * 16:(ty + 1) * 16, tx * 16:(tx + 1) * 16]
-        top = int(blk_c.max()) if blk_c.size else 0
-        if top == 0:
-            assert int(blk_k.max(initial=0)) == 0
-            continue
-        pos = np.nonzero(hits[a:a + top])[0]  # the record is defined for the batches the tile processed: covers [0, top)
-        assert np.array_equal(hl[a:a + len(pos)], pos), (name, mode, t)
-        # per pixel: entries of the list in front of its last contributor + 1 ... and the last contributor is in the list
-        want = np.searchsorted(pos, blk_c, side="left")  # = #{entries with position < n_contrib}
-        assert np.array_equal(blk_k, want), (name, mode, t)
-        lastpos = blk_c[blk_c > 0] - 1
-        assert np.all(hits[a + lastpos] != 0)
-        checked += 1
-    assert checked > 5
+    # the list against its definition (gpu_utils.check_hit_list)
+    assert check_hit_list(arr, H, W, (name, mode)) > 5
 
 
 def test_compact_walk_is_what_runs_by_default_and_shortens_the_walk():
