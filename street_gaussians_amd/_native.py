@@ -97,6 +97,8 @@ def _signatures():
         "sgr_sky_forward": (i, [i, i, i, i] + [vp] * 9 + [i, vp, vp, vp]),
         "sgr_sky_backward": (i, [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
         "sgr_sky_test_rays": (i, [i, i, vp, vp, vp, vp, i, vp, vp, vp]),
+        "sgr_actor_pose_forward": (i, [i, vp, i] + [vp] * 7 + [vp]),
+        "sgr_actor_pose_backward": (i, [i, vp, i] + [vp] * 9 + [vp]),
         "sgr_test_sort32_count": (i, [vp, vp, vp, vp, u32, i, i, vp, vp, vp, vp]),
     }
 

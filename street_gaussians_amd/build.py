@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsgr_hip.so")
 SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_blend_fwd.hip", "sgr_blend_bwd.hip", "sgr_gauss_bwd.hip", "sgr_gauss_bwd_strict.hip",
-           "sgr_knn.hip", "sgr_multiview.hip", "sgr_scene.hip", "sgr_loss.hip", "sgr_densify.hip", "sgr_texture.hip", "sgr_sky.hip", "sgr_optim.hip", "sgr_api.hip"]
+           "sgr_knn.hip", "sgr_multiview.hip", "sgr_scene.hip", "sgr_loss.hip", "sgr_densify.hip", "sgr_texture.hip", "sgr_sky.hip", "sgr_optim.hip", "sgr_actor_pose.hip", "sgr_api.hip"]
 # Designs that were built, measured slower on MI355X and kept as A/B records: the scalar-walk blend
 # backward (its own file), and -- behind `#if SGR_WITH_VARIANTS` inside the files above -- the transposed-accumulation
 # backward, the one-sweep radix sorts and the wave-cooperative row sum.  NOT part of the shipped library:
@@ -26,7 +26,7 @@ VARIANT_SOURCES = [os.path.join("variants", "sgr_blend_bwd_sw.hip")]
 HEADERS = ["sgr_common.h", "sgr_math.h", "sgr_reduce.h", "sgr_cube.h", os.path.join("..", "..", "include", "sgr.h"),
            os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
-           os.path.join("..", "..", "include", "sgr_sky.h")]
+           os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 ops into v_pk_* and pays for it with v_mov
 # shuffles; measured on MI355X it costs 6 % in the blend backward and 7 % in the per-Gaussian backward.
 # -mllvm -enable-post-misched=0: without the post-RA machine scheduler the blend kernels keep the order they were
@@ -36,8 +36,10 @@ HEADERS = ["sgr_common.h", "sgr_math.h", "sgr_reduce.h", "sgr_cube.h", os.path.j
 # scan and on the tile sort at 1 M Gaussians) which costs the blend kernels 2 %.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fno-slp-vectorize", "-mllvm",
          "-enable-post-misched=0", "-mllvm", "-amdgpu-use-amdgpu-trackers=1", "-Wall", "-Wno-unused-function"]
-# sgr_optim.hip declares its arithmetic op by op (include/sgr_optim.h): no fused multiply-adds.
-PER_FILE_FLAGS = {"sgr_scan_sort.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "sgr_optim.hip": ["-ffp-contract=off"]}
+# sgr_optim.hip and sgr_actor_pose.hip declare their arithmetic op by op (include/sgr_optim.h, sgr_actor_pose.h): no fused
+# multiply-adds.
+PER_FILE_FLAGS = {"sgr_scan_sort.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "sgr_optim.hip": ["-ffp-contract=off"],
+                  "sgr_actor_pose.hip": ["-ffp-contract=off"]}
 # sources that #include another source (a second instantiation under other names / other FP settings)
 INCLUDES = {"sgr_gauss_bwd_strict.hip": ["sgr_gauss_bwd.hip"]}
 
