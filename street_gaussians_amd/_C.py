@@ -145,6 +145,53 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
     return rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom.tensor, binning.tensor, img.tensor
 
 
+class _LayerImages(C.Structure):  # sgr_layer_images (include/sgr_layers.h)
+    _fields_ = [("split", C.c_int), ("background", C.c_void_p), ("clamp", C.c_int), ("color", C.c_void_p * 2),
+                ("alpha", C.c_void_p * 2)]
+
+
+def rasterize_gaussians_layers(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
+                               cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                               degree, campos, prefiltered, debug, split, layer_background, clamp=True):
+    """sgr_forward_layers (include/sgr_layers.h): rasterize_gaussians plus the colour and alpha images of Gaussians
+    [0, split) and [split, P), each blended alone over ``layer_background`` -- one more launch on the same tile lists.
+    Returns rasterize_gaussians' nine values followed by (color0 [3, H, W], alpha0 [1, H, W], color1, alpha1).
+    Inference only; ctypes only (an entry point beyond the reference's API)."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    _dev_check(means3D, "means3D")
+    dev = means3D.device
+    P, H, W = means3D.size(0), int(image_height), int(image_width)
+    S = semantics.size(1) if semantics is not None and semantics.ndimension() == 2 else 0
+    M = sh.size(1) if sh is not None and sh.numel() != 0 and sh.size(0) != 0 else 0
+    with torch.cuda.device(dev):
+        mk = lambda *shape: _alloc.empty(shape, torch.float32, dev)
+        out_color, out_depth, out_alpha, out_semantic = mk(NUM_CHANNELS, H, W), mk(1, H, W), mk(1, H, W), mk(S, H, W)
+        layer = [mk(NUM_CHANNELS, H, W), mk(1, H, W), mk(NUM_CHANNELS, H, W), mk(1, H, W)]
+        radii = (torch.empty if P else torch.zeros)((P,), dtype=torch.int32, device=dev)
+        geom, binning, img = _Grow(dev), _Grow(dev), _Grow(dev)
+        keep = []
+        def p(t, n):
+            t, ptr = _fptr(t, n)
+            keep.append(t)
+            return ptr
+        lbg = p(layer_background, "layer_background")
+        li = _LayerImages(int(split), lbg, 1 if clamp else 0,
+                          (C.c_void_p * 2)(layer[0].data_ptr(), layer[2].data_ptr()),
+                          (C.c_void_p * 2)(layer[1].data_ptr(), layer[3].data_ptr()))
+        rendered = check(_native.lib().sgr_forward_layers(
+            geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, S, p(background, "bg"), W, H,
+            p(means3D, "means3D"), p(sh, "sh"), p(colors, "colors_precomp"), p(semantics, "semantics"),
+            p(opacity, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
+            p(cov3D_precomp, "cov3D_precomp"), p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"),
+            p(campos, "campos"), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
+            C.c_void_p(out_color.data_ptr()), C.c_void_p(out_depth.data_ptr()), C.c_void_p(out_alpha.data_ptr()),
+            C.c_void_p(out_semantic.data_ptr()) if S else None, C.c_void_p(radii.data_ptr()) if P else None,
+            int(bool(debug)), _stream(dev), C.byref(li)))
+    return (rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom.tensor, binning.tensor, img.tensor,
+            layer[0], layer[1], layer[2], layer[3])
+
+
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                  dL_dout_alpha, dL_dout_semantic, sh, degree, campos, geomBuffer, R, binningBuffer,

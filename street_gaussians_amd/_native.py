@@ -27,11 +27,13 @@ def _signatures():
     i64p = C.POINTER(C.c_int64)
     bwd = [i, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp, vp, vp, vp,
            vp, vp, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, i, vp]
+    fwd = [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, i,
+           vp, vp, vp, vp, vp, i, vp]
     return {
         "sgr_last_error": (C.c_char_p, []),
         "sgr_version": (i, []),
-        "sgr_forward": (i, [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, i, i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, f, vp,
-                            vp, vp, vp, vp, f, f, i, vp, vp, vp, vp, vp, i, vp]),
+        "sgr_forward": (i, fwd),
+        "sgr_forward_layers": (i, fwd + [vp]),
         "sgr_backward": (i, bwd),
         "sgr_backward_ex": (i, bwd + [vp]),
         "sgr_mark_visible": (i, [i, vp, vp, vp, vp, vp]),

@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "../../include/sgr.h"
+#include "../../include/sgr_layers.h"
 #include "sgr_math.h"
 
 // launchers implemented in the kernel translation units
@@ -34,6 +35,10 @@ void sgr_launch_blend_fwd(bool cull, bool exact, int gx, int gy, const uint2* ra
                           int S, const float4* rec, const float* semantics, const float* bg, float* out_color,
                           float* out_depth, float* out_alpha, float* out_semantic, uint32_t* n_contrib, uint8_t* hit4,
                           uint32_t* hlist, uint32_t* n_contrib_k, hipStream_t s);
+void sgr_launch_blend_layers(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
+                             const float4* rec, int split, int P, const float* bg, int clamp, float* const color[2],
+                             float* const alpha[2], hipStream_t s);
+void sgr_launch_layers_fill(int W, int H, const float* bg, int clamp, float* const color[2], float* const alpha[2], hipStream_t s);
 int sgr_partial_row_stride(int S);
 void sgr_launch_blend_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W,
                           int H, int S, const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* semantics, const float* alphas,
@@ -409,7 +414,7 @@ SgrFlagBlock sgr_acquire_flag_block() {
 extern "C" {
 
 const char* sgr_last_error(void) { return g_err.c_str(); }
-int sgr_version(void) { return 102; }  // 102: sgr_backward_extras gained masked_color_out + skip_sh_grad (101: color_ready_event + rows)
+int sgr_version(void) { return 103; }  // 103: sgr_forward_layers (include/sgr_layers.h); 102: sgr_backward_extras gained masked_color_out + skip_sh_grad (101: color_ready_event + rows)
 
 size_t sgr_geometry_bytes(int P) {
     return sgr_required([&](char* b, char** e) { sgr_geom_carve(b, (size_t)P, e); });
@@ -423,13 +428,16 @@ size_t sgr_image_bytes(int width, int height) {
 }
 int sgr_partial_row_floats(int S) { return sgr_partial_row_stride(S); }
 
-int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
-                sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
-                int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
-                const float* semantics, const float* opacities, const float* scales, float scale_modifier,
-                const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
-                float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_) {
+// The forward, and -- `layers` given -- the layer kernel behind it (include/sgr_layers.h; its arguments are checked by
+// sgr_forward_layers before this runs).  sgr_forward is this with layers == nullptr.
+static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
+                        sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
+                        int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                        const float* semantics, const float* opacities, const float* scales, float scale_modifier,
+                        const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                        const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                        float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_,
+                        const sgr_layer_images* layers) {
     hipStream_t stream = (hipStream_t)stream_;
     const Switches sw = resolve_switches();
     const int W = width, H = height;
@@ -446,6 +454,10 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
         SGR_HIP(hipMemsetAsync(out_depth, 0, N * sizeof(float), stream));
         SGR_HIP(hipMemsetAsync(out_alpha, 0, N * sizeof(float), stream));
         if (S) SGR_HIP(hipMemsetAsync(out_semantic, 0, (size_t)S * N * sizeof(float), stream));
+        if (layers) {  // the reference's empty model: background colour, alpha 0 (street_gaussian_renderer.py:138-151)
+            sgr_launch_layers_fill(W, H, layers->background, layers->clamp, layers->color, layers->alpha, stream);
+            SGR_STAGE("layers_fill");
+        }
         return 0;
     }
     if (!means3D || !opacities || !viewmatrix || !projmatrix || !background)
@@ -677,7 +689,49 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
                          sw.hit_list ? bv.hlist : nullptr, iv.n_contrib_k, stream);
     SGR_STAGE("blend_fwd");
     prof_end(stream);
+    if (layers) {
+        // one more walk of the same ranges, the same final list and the same records, in the same tile order: the images of
+        // Gaussians [0, split) and [split, P) alone (sgr_blend_layers.hip).  It writes none of the composite's buffers.
+        sgr_launch_blend_layers(sw.exact, gx, sw.lpt ? -gy : gy, iv.ranges, bv.vals[lcur], W, H, gv.rec, layers->split, P,
+                                layers->background, layers->clamp, layers->color, layers->alpha, stream);
+        SGR_STAGE("blend_layers");
+    }
     return R;
+}
+
+int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
+                sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
+                int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                const float* semantics, const float* opacities, const float* scales, float scale_modifier,
+                const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_) {
+    return forward_impl(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S,
+                        background, width, height, means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier,
+                        rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                        out_depth, out_alpha, out_semantic, radii, debug, stream_, nullptr);
+}
+
+int sgr_forward_layers(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
+                       sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
+                       int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                       const float* semantics, const float* opacities, const float* scales, float scale_modifier,
+                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                       const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                       float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_,
+                       const sgr_layer_images* layers) {
+    if (layers) {  // before any HIP call and any allocation callback
+        if (layers->split < 0 || layers->split > P) return fail(SGR_E_INVALID, "layers: split must lie in [0, P]");
+        if (!layers->background) return fail(SGR_E_INVALID, "layers: background is NULL");
+        for (int l = 0; l < 2; l++) {
+            if (!layers->color[l]) return fail(SGR_E_INVALID, "layers: color[" + std::to_string(l) + "] is NULL");
+            if (!layers->alpha[l]) return fail(SGR_E_INVALID, "layers: alpha[" + std::to_string(l) + "] is NULL");
+        }
+    }
+    return forward_impl(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S,
+                        background, width, height, means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier,
+                        rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                        out_depth, out_alpha, out_semantic, radii, debug, stream_, layers);
 }
 
 // which of the two ping-pong pairs holds the sorted tile keys: one flip per 8-bit pass

@@ -204,6 +204,15 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+class LayerImages(NamedTuple):
+    """The two layer images of GaussianRasterizer.forward_layers: Gaussians [0, split) (``first``) and [split, P)
+    (``rest``), each blended alone over the layer background."""
+    rgb_first: torch.Tensor  # [3, H, W]
+    acc_first: torch.Tensor  # [1, H, W]
+    rgb_rest: torch.Tensor
+    acc_rest: torch.Tensor
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
@@ -247,6 +256,54 @@ class GaussianRasterizer(nn.Module):
 
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, semantics, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.stats_sink)
+
+    def forward_layers(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                       cov3D_precomp=None, semantics=None, *, split, layer_background=None, clamp=True):
+        """Extension (not in the reference): ``forward`` plus the images of two layers of the same frame -- Gaussians
+        [0, split) and [split, P), each blended alone over ``layer_background`` (default: white) with its own transmittance
+        -- from one front end and one binning (sgr_forward_layers, include/sgr_layers.h).  What the reference's
+        StreetGaussianRenderer.render_all gets from three forwards (lib/models/street_gaussian_renderer.py:13-72).
+
+        Returns ``(color, radii, depth, alpha, semantics, layers)``: the first five are ``forward``'s, bit for bit; ``layers``
+        is a ``LayerImages`` whose entries equal ``forward`` over the subset alone with ``bg = layer_background``.  ``clamp``
+        clamps the layer colours to [0, 1] (render_kernel outside training, :242-243); the composite is never clamped.
+
+        Inference only: no output takes part in autograd.  Under enabled grad mode an input that requires grad raises
+        ValueError -- call it under ``torch.no_grad()``."""
+        raster_settings = self.raster_settings
+
+        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+        if torch.is_grad_enabled():
+            named = (("means3D", means3D), ("means2D", means2D), ("opacities", opacities), ("shs", shs),
+                     ("colors_precomp", colors_precomp), ("scales", scales), ("rotations", rotations),
+                     ("cov3D_precomp", cov3D_precomp), ("semantics", semantics), ("layer_background", layer_background))
+            tracked = [n for n, t in named if isinstance(t, torch.Tensor) and t.requires_grad]
+            if tracked:
+                raise ValueError("forward_layers is inference only and has no backward, but " + ", ".join(tracked) +
+                                 " require grad: call it under torch.no_grad() (use forward() for training)")
+
+        with torch.no_grad():
+            e = torch.Tensor([])
+            z = lambda t: e if t is None else t.detach()
+            if semantics is None:
+                semantics = torch.zeros(means3D.shape[0], 0, dtype=torch.float32, device=means3D.device)
+            if layer_background is None:
+                layer_background = torch.ones(3, dtype=torch.float32, device=means3D.device)
+            out = _C.rasterize_gaussians_layers(
+                raster_settings.bg, means3D.detach(), z(colors_precomp), semantics.detach(), opacities.detach(), z(scales),
+                z(rotations), raster_settings.scale_modifier, z(cov3D_precomp), raster_settings.viewmatrix,
+                raster_settings.projmatrix, raster_settings.tanfovx, raster_settings.tanfovy, raster_settings.image_height,
+                raster_settings.image_width, z(shs), raster_settings.sh_degree, raster_settings.campos,
+                raster_settings.prefiltered, raster_settings.debug, int(split), layer_background.detach(), bool(clamp))
+        num_rendered, color, depth, alpha, semantic, radii = out[:6]
+        _LAST["num_rendered"] = num_rendered
+        return color, radii, depth, alpha, semantic, LayerImages(*out[9:13])
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
         raster_settings = self.raster_settings
