@@ -54,6 +54,30 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
                 const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                 float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream);
 
+/* sgr_forward with per-call extras (NULL = plain sgr_forward; sgr_version() >= 104).
+ * color_jacobian != 0: a backward will follow this forward.  Where the colour comes from SH (shs given, no
+ * colors_precomp) the preprocess then also stores, for every Gaussian that passes the cull, the 3x3 Jacobian d rgb / d dir
+ * of the SH evaluation -- the reference's dRGBdx, dRGBdy, dRGBdz (cuda_rasterizer/backward.cu:46-129) -- 36 bytes per
+ * Gaussian in the geometry buffer, and records that in the buffer's header.  sgr_backward over such a frame forms
+ * dL/ddir = J . dL/dRGB from them (the reference's own association, backward.cu:131-136) and does not read the SH rows at
+ * all: 36 instead of 12 M bytes per visible Gaussian.  Every forward output is the same with and without it; of the
+ * gradients only dL_dmean3D differs, in its last bits (J first instead of the row contracted with dL/dRGB first).  A frame
+ * whose forward did not ask (sgr_forward, sgr_forward_layers, an inference render) is served by the row-reading backward as
+ * before: the backward follows the FRAME, not the call.  J holds the terms of the FORWARD's SH degree D: a backward over
+ * such a frame must be called with the same D (as the reference's is, which takes it from the same settings object); the
+ * row-reading path would honour a different D of the backward call, the J path cannot. */
+typedef struct sgr_forward_extras {
+    int color_jacobian;
+} sgr_forward_extras;
+int sgr_forward_ex(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
+                   sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
+                   int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                   const float* semantics, const float* opacities, const float* scales, float scale_modifier,
+                   const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                   const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                   float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream,
+                   const sgr_forward_extras* extras);
+
 /* CudaRasterizer::Rasterizer::backward  (cuda_rasterizer/rasterizer.h:64-102, rasterizer_impl.cu:396-506).
  * geom/binning/image buffers and R are the ones forward produced.  `scratch` provides temporary device
  * memory (one float4 per Gaussian + R partial rows of sgr_partial_row_floats(S) floats) that may be released when
@@ -118,8 +142,12 @@ typedef struct sgr_backward_extras {
     int skip_sh_grad; /* != 0: dL_dsh is NOT written (the pointer may be NULL although shs is given) -- the factored exchange
                        * rebuilds the SH gradient of ALL views from the gathered dRGB (sgr_sh_grad_from_views), so this view's
                        * own 12*M B/Gaussian would be written only to be overwritten.  Every other output is unchanged. */
-} sgr_backward_extras; /* layout of sgr_version() >= 102 (101 ended at rows, 100 at n_segments: a caller built against an
-                        * older header must not be run against this library -- check sgr_version() before passing the struct) */
+    int skip_cov3d_grad; /* != 0: dL_dcov3D is NOT written (the pointer may be NULL) -- a caller that rasterizes from scales and
+                          * rotations has no cov3D_precomp for the gradient to reach: 24 B/Gaussian that nobody reads.  Every
+                          * other output is unchanged. */
+} sgr_backward_extras; /* layout of sgr_version() >= 104 (103 and 102 ended at skip_sh_grad, 101 at rows, 100 at n_segments: a
+                        * caller built against an older header must not be run against this library -- check sgr_version()
+                        * before passing the struct) */
 int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, int width, int height,
                     const float* means3D, const float* shs, const float* colors_precomp, const float* semantics,
                     const float* alphas, const float* scales, float scale_modifier, const float* rotations,
@@ -172,6 +200,10 @@ size_t sgr_geometry_bytes(int P);
 size_t sgr_binning_bytes(int R);
 size_t sgr_image_bytes(int width, int height);
 int sgr_partial_row_floats(int S);
+/* Where the colour Jacobian of sgr_forward_ex lies in a geometry buffer of P Gaussians: byte offset from the buffer's
+ * pointer rounded up to 256.  Nine consecutive floats per Gaussian, {dRGBdx.rgb, dRGBdy.rgb, dRGBdz.rgb}, written for the
+ * Gaussians with radii > 0 of a frame that asked for it (tests read and overwrite it there). */
+size_t sgr_geometry_jac_offset(int P);
 
 /* ---- per-stage timing with HIP events recorded on the caller's stream (bench.py's roofline leg) ---------------
  * stages: 0 preprocess 1 scan 2 duplicate 3 sort 4 tile_ranges 5 blend_fwd 6 partials memset 7 blend_bwd

@@ -76,7 +76,12 @@ class _StatSegment(C.Structure):  # sgr_stat_segment (include/sgr.h)
 class _BackwardExtras(C.Structure):  # sgr_backward_extras (include/sgr.h)
     _fields_ = [("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii2D", C.c_void_p),
                 ("segments", C.POINTER(_StatSegment)), ("n_segments", C.c_int), ("color_ready_event", C.c_void_p),
-                ("rows", C.c_int), ("masked_color_out", C.c_void_p), ("skip_sh_grad", C.c_int)]
+                ("rows", C.c_int), ("masked_color_out", C.c_void_p), ("skip_sh_grad", C.c_int),
+                ("skip_cov3d_grad", C.c_int)]
+
+
+class _ForwardExtras(C.Structure):  # sgr_forward_extras (include/sgr.h)
+    _fields_ = [("color_jacobian", C.c_int)]
 
 
 MAX_STAT_SEGMENTS = 128  # SGR_MAX_STAT_SEGMENTS
@@ -102,8 +107,9 @@ def _fptr(t, name="tensor"):
 
 def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                        degree, campos, prefiltered, debug):
-    """RasterizeGaussiansCUDA (rasterize_points.cu:35-124)."""
+                        degree, campos, prefiltered, debug, color_jacobian=False):
+    """RasterizeGaussiansCUDA (rasterize_points.cu:35-124).  color_jacobian (extension): a backward will follow -- the
+    preprocess also stores the SH colour Jacobian for it (sgr_forward_extras.color_jacobian); same outputs."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     _dev_check(means3D, "means3D")
@@ -114,7 +120,7 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
         return _call_ext(ext.rasterize_gaussians, z(background), means3D, z(colors), z(semantics), z(opacity), z(scales),
                          z(rotations), float(scale_modifier), z(cov3D_precomp), z(viewmatrix), z(projmatrix),
                          float(tan_fovx), float(tan_fovy), int(image_height), int(image_width), z(sh), int(degree),
-                         z(campos), bool(prefiltered), bool(debug))
+                         z(campos), bool(prefiltered), bool(debug), *((True,) if color_jacobian else ()))
     dev = means3D.device
     P, H, W = means3D.size(0), int(image_height), int(image_width)
     S = semantics.size(1) if semantics is not None and semantics.ndimension() == 2 else 0
@@ -133,7 +139,8 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
             t, ptr = _fptr(t, n)
             keep.append(t)
             return ptr
-        rendered = check(_native.lib().sgr_forward(
+        fx = _ForwardExtras(1) if color_jacobian else None
+        rendered = check(_native.lib().sgr_forward_ex(
             geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, S, p(background, "bg"), W, H,
             p(means3D, "means3D"), p(sh, "sh"), p(colors, "colors_precomp"), p(semantics, "semantics"),
             p(opacity, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
@@ -141,7 +148,7 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
             p(campos, "campos"), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
             C.c_void_p(out_color.data_ptr()), C.c_void_p(out_depth.data_ptr()), C.c_void_p(out_alpha.data_ptr()),
             C.c_void_p(out_semantic.data_ptr()) if S else None, C.c_void_p(radii.data_ptr()) if P else None,
-            int(bool(debug)), _stream(dev)))
+            int(bool(debug)), _stream(dev), C.byref(fx) if fx is not None else None))
     return rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom.tensor, binning.tensor, img.tensor
 
 
@@ -196,7 +203,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                  dL_dout_alpha, dL_dout_semantic, sh, degree, campos, geomBuffer, R, binningBuffer,
                                  imageBuffer, alphas, semantics, debug, stats=None, color_event=None, out=None,
-                                 masked_color_out=None, skip_sh_grad=False):
+                                 masked_color_out=None, skip_sh_grad=False, skip_cov3d_grad=False):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:126-220).  Returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dsemantic).
     stats (extension): (xyz_gradient_accum [P,2], denom [P,1], max_radii2D [P]) contiguous float32 tensors updated in
@@ -209,7 +216,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     tensor} -- caller-supplied destinations for those gradients (contiguous float32 of the gradient's shape; e.g. views of
     a gradient-exchange bucket, street_gaussians_amd.multiview) instead of fresh allocations; they are what is returned.
     masked_color_out (extension): [P, 3] float32 destination of the clamp-masked colour gradient
-    (sgr_backward_extras.masked_color_out).  skip_sh_grad (extension): dL_dsh is not computed, None is returned for it."""
+    (sgr_backward_extras.masked_color_out).  skip_sh_grad (extension): dL_dsh is not computed, None is returned for it.
+    skip_cov3d_grad (extension): likewise for dL_dcov3D (sgr_backward_extras.skip_cov3d_grad)."""
     _dev_check(means3D, "means3D")
     ext = _pybind()
     if ext is not None and stats is None and color_event is None and not out and masked_color_out is None and not skip_sh_grad:
@@ -219,7 +227,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                          float(scale_modifier), z(cov3D_precomp), z(viewmatrix), z(projmatrix), float(tan_fovx),
                          float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_alpha, z(dL_dout_semantic), z(sh),
                          int(degree), z(campos), geomBuffer, int(R), binningBuffer, imageBuffer, alphas, z(semantics),
-                         bool(debug))
+                         bool(debug), *((True,) if skip_cov3d_grad else ()))
     dev = means3D.device
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -242,7 +250,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         dL_dmeans2D = mk((P, 3), "means2D")
         dL_dcolors = mk((P, NUM_CHANNELS), "colors")
         dL_dopacity = mk((P, 1), "opacity")
-        dL_dcov3D = mk((P, 6), "cov3D")
+        # (skipped: no allocation, NULL goes down -- unless the caller handed a destination, which is then left untouched)
+        dL_dcov3D = None if (skip_cov3d_grad and P and out.get("cov3D") is None) else mk((P, 6), "cov3D")
         dL_dsh = None if (skip_sh_grad and P) else mk((P, M, 3), "sh")
         dL_dscales = mk((P, 3), "scales")
         dL_drotations = mk((P, 4), "rotations")
@@ -277,10 +286,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                         raise SgrError("statistics segment outside the persistent tensors")
                     seg_arr[k] = _StatSegment(int(s0), int(cnt), int(d0))
                 keep.append(seg_arr)
-            extras = _BackwardExtras(acc.data_ptr(), den.data_ptr(), mr.data_ptr(), seg_arr, nseg, None, int(rows), None, 0)
-        if color_event is not None or masked_color_out is not None or skip_sh_grad:
+            extras = _BackwardExtras(acc.data_ptr(), den.data_ptr(), mr.data_ptr(), seg_arr, nseg, None, int(rows), None, 0, 0)
+        if color_event is not None or masked_color_out is not None or skip_sh_grad or skip_cov3d_grad:
             if extras is None:
-                extras = _BackwardExtras(None, None, None, None, 0, None, 0, None, 0)
+                extras = _BackwardExtras(None, None, None, None, 0, None, 0, None, 0, 0)
             if color_event is not None:
                 extras.color_ready_event = C.c_void_p(int(color_event.cuda_event))
             if masked_color_out is not None:
@@ -289,6 +298,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                     raise SgrError("masked_color_out must be a contiguous float32 HIP tensor of 3 * P elements")
                 extras.masked_color_out = C.c_void_p(m.data_ptr())
             extras.skip_sh_grad = 1 if skip_sh_grad else 0
+            extras.skip_cov3d_grad = 1 if skip_cov3d_grad else 0
         check(_native.lib().sgr_backward_ex(
             P, int(degree), M, int(R), S, p(background, "bg"), W, H, p(means3D, "means3D"), p(sh, "sh"),
             p(colors, "colors_precomp"), p(semantics, "semantics"), p(alphas, "alpha"), p(scales, "scales"),
@@ -473,6 +483,21 @@ KEY32 = 1 << 18  # 32-bit tile keys in the instance list (default: 16-bit whenev
 def test_switches(mask: int = -1) -> int:
     """sgr_test_switches: A/B switches of the blend kernels (tests and tools only); returns the previous mask."""
     return int(_native.lib().sgr_test_switches(int(mask)))
+
+
+def color_jacobian_view(geomBuffer, P):
+    """The [P, 9] float32 colour Jacobian inside a forward's geometry buffer, as a VIEW (sgr_geometry_jac_offset): rows of
+    Gaussians with radii > 0 are defined, and only when the forward ran with color_jacobian=True."""
+    P = int(P)
+    off = int(_native.lib().sgr_geometry_jac_offset(P))
+    pad = (-geomBuffer.data_ptr()) % 256
+    return geomBuffer[pad + off:pad + off + 36 * P].view(torch.float32).view(P, 9)
+
+
+def geometry_header(geomBuffer):
+    """The 64 header words of a forward's geometry buffer (int32 view): word 8 = the forward stored the colour Jacobian."""
+    pad = (-geomBuffer.data_ptr()) % 256
+    return geomBuffer[pad:pad + 256].view(torch.int32)
 
 
 def export_internal(name, P, R, image_height, image_width, geomBuffer, binningBuffer, imageBuffer, scales=None,

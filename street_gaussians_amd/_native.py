@@ -33,6 +33,7 @@ def _signatures():
         "sgr_last_error": (C.c_char_p, []),
         "sgr_version": (i, []),
         "sgr_forward": (i, fwd),
+        "sgr_forward_ex": (i, fwd + [vp]),
         "sgr_forward_layers": (i, fwd + [vp]),
         "sgr_backward": (i, bwd),
         "sgr_backward_ex": (i, bwd + [vp]),
@@ -43,6 +44,7 @@ def _signatures():
         "sgr_binning_bytes": (sz, [i]),
         "sgr_image_bytes": (sz, [i, i]),
         "sgr_partial_row_floats": (i, [i]),
+        "sgr_geometry_jac_offset": (sz, [i]),
         "sgr_export_internal": (i, [i, i, i, i, i, vp, vp, vp, vp, vp]),
         "sgr_export_cov3d": (i, [i, vp, f, vp, vp, vp]),
         "sgr_test_scan": (i, [vp, vp, sz, i, vp, vp]),

@@ -58,7 +58,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
                     const torch::Tensor& rotations, const float scale_modifier, const torch::Tensor& cov3D_precomp,
                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
                     const float tan_fovy, const int image_height, const int image_width, const torch::Tensor& sh,
-                    const int degree, const torch::Tensor& campos, const bool prefiltered, const bool debug) {
+                    const int degree, const torch::Tensor& campos, const bool prefiltered, const bool debug,
+                    const bool color_jacobian) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3) AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path");
     c10::DeviceGuard guard(means3D.device());
@@ -79,12 +80,13 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     const torch::Tensor bg = c(background), m3 = c(means3D), col = c(colors), sem = c(semantics), op = c(opacity),
                         sc = c(scales), rot = c(rotations), cov = c(cov3D_precomp), vm = c(viewmatrix),
                         pm = c(projmatrix), shc = c(sh), cp = c(campos);
-    const int rendered = sgr_forward(grow, &geom, grow, &binning, grow, &img, P, degree, M, S, fp(bg), W, H, fp(m3), fp(shc),
+    const sgr_forward_extras fx{color_jacobian ? 1 : 0};  // (extension) the backward's colour Jacobian, include/sgr.h
+    const int rendered = sgr_forward_ex(grow, &geom, grow, &binning, grow, &img, P, degree, M, S, fp(bg), W, H, fp(m3), fp(shc),
                                      fp(col), fp(sem), fp(op), fp(sc), scale_modifier, fp(rot), fp(cov), fp(vm), fp(pm),
                                      fp(cp), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(),
                                      out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(),
                                      S ? out_semantic.data_ptr<float>() : nullptr, P ? radii.data_ptr<int>() : nullptr,
-                                     debug ? 1 : 0, stream_of(means3D));
+                                     debug ? 1 : 0, stream_of(means3D), &fx);
     check(rendered);
     return std::make_tuple(rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom, binning, img);
 }
@@ -102,7 +104,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer,
                              const torch::Tensor& imageBuffer, const torch::Tensor& alphas, const torch::Tensor& semantics,
-                             const bool debug) {
+                             const bool debug, const bool skip_cov3d_grad) {
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path");
     c10::DeviceGuard guard(means3D.device());
     const int P = means3D.size(0), H = dL_dout_color.size(1), W = dL_dout_color.size(2);
@@ -120,7 +122,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         return buf.narrow(0, 0, n).view(shape);
     };
     torch::Tensor dL_dmeans3D = mk({P, 3}), dL_dmeans2D = mk({P, 3}), dL_dcolors = mk({P, 3}), dL_dopacity = mk({P, 1});
-    torch::Tensor dL_dcov3D = mk({P, 6}), dL_dsh = mk({P, M, 3}), dL_dscales = mk({P, 3}), dL_drotations = mk({P, 4});
+    // (extension) skip_cov3d_grad: the gradient nobody receives is neither allocated nor written (an empty tensor comes back)
+    torch::Tensor dL_dcov3D = (skip_cov3d_grad && P) ? torch::empty({0}, fo) : mk({P, 6}), dL_dsh = mk({P, M, 3}), dL_dscales = mk({P, 3}), dL_drotations = mk({P, 4});
     torch::Tensor dL_dsemantic = mk({P, S});
     if (P != 0) {
         torch::Tensor scratch = torch::empty({0}, means3D.options().dtype(torch::kByte));
@@ -131,12 +134,14 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                             ga = c(dL_dout_alpha), gs = c(dL_dout_semantic), rd = c(radii);
         auto bytes = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; };
         auto op = [](torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; };
-        check(sgr_backward(P, degree, M, R, S, fp(bg), W, H, fp(m3), fp(shc), fp(col), fp(sem), fp(al), fp(sc),
+        sgr_backward_extras bx{};
+        bx.skip_cov3d_grad = skip_cov3d_grad ? 1 : 0;
+        check(sgr_backward_ex(P, degree, M, R, S, fp(bg), W, H, fp(m3), fp(shc), fp(col), fp(sem), fp(al), fp(sc),
                            scale_modifier, fp(rot), fp(cov), fp(vm), fp(pm), fp(cp), tan_fovx, tan_fovy,
                            rd.numel() ? rd.data_ptr<int>() : nullptr, bytes(geomBuffer), bytes(binningBuffer),
                            bytes(imageBuffer), fp(gc), fp(gd), fp(ga), fp(gs), op(dL_dmeans2D), op(dL_dopacity),
                            op(dL_dcolors), op(dL_dmeans3D), op(dL_dcov3D), op(dL_dsh), op(dL_dscales), op(dL_drotations),
-                           op(dL_dsemantic), grow, &scratch, debug ? 1 : 0, stream_of(means3D)));
+                           op(dL_dsemantic), grow, &scratch, debug ? 1 : 0, stream_of(means3D), &bx));
     }
     return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
                            dL_dsemantic);
@@ -195,8 +200,19 @@ torch::Tensor distCUDA2(const torch::Tensor& points) {
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("rasterize_gaussians", &rasterize_gaussians);
-    m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward);
+    // the reference's argument lists (positional, as its callers pass them) + one trailing extension flag each, default off
+    namespace py = pybind11;
+    m.def("rasterize_gaussians", &rasterize_gaussians, py::arg("background"), py::arg("means3D"), py::arg("colors"),
+          py::arg("semantics"), py::arg("opacity"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"),
+          py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"),
+          py::arg("image_height"), py::arg("image_width"), py::arg("sh"), py::arg("degree"), py::arg("campos"),
+          py::arg("prefiltered"), py::arg("debug"), py::arg("color_jacobian") = false);
+    m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward, py::arg("background"), py::arg("means3D"),
+          py::arg("radii"), py::arg("colors"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"),
+          py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"),
+          py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("dL_dout_alpha"), py::arg("dL_dout_semantic"),
+          py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"),
+          py::arg("imageBuffer"), py::arg("alphas"), py::arg("semantics"), py::arg("debug"), py::arg("skip_cov3d_grad") = false);
     m.def("mark_visible", &mark_visible);
     m.def("rasterize_gaussians_filter", &rasterize_gaussians_filter);
     m.def("distCUDA2", &distCUDA2);

@@ -21,7 +21,7 @@ void sgr_launch_mark_visible(int P, const float* means3D, const float* viewmatri
 void sgr_launch_preprocess(int P, int D, int M, const float* means3D, const float* scales, const float* rotations,
                            const float* opacities, const float* shs, const float* cov3D_precomp,
                            const float* colors_precomp, const SgrCam* cam, const SgrGeomView& gv, int* radii,
-                           int prefiltered, bool stage_sh, int tight, hipStream_t s);
+                           int prefiltered, bool stage_sh, int tight, bool want_jac, hipStream_t s);
 void sgr_launch_filter(int P, const float* means3D, const float* scales, const float* rotations,
                        const float* cov3D_precomp, const SgrCamArgs& ca, const SgrGeomView& gv, int* radii,
                        float* means2D, int prefiltered, hipStream_t s);
@@ -51,7 +51,7 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
                           float4* cd, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                           float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dsemantic,
                           const SgrStatSink& sink, int quad, int exact, int W, int H, hipEvent_t after_rows, int rs_wave,
-                          uint32_t row_limit, float* masked_color_out, int skip_sh, hipStream_t s);
+                          uint32_t row_limit, float* masked_color_out, int skip_sh, int skip_cov, hipStream_t s);
 void sgr_launch_blend_bwd_sw(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
                              const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* alphas,
                              const uint32_t* n_contrib, const uint8_t* hit4, const float* dL_dpix, const float* dL_ddepth,
@@ -63,7 +63,7 @@ int sgr_launch_gauss_bwd_strict(int P, int D, int M, int S, const float* means3D
                                  float4* cd, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                                  float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dsemantic,
                                  const SgrStatSink& sink, int quad, int exact, int W, int H, hipEvent_t after_rows, int rs_wave,
-                                 uint32_t row_limit, float* masked_color_out, int skip_sh, hipStream_t s);
+                                 uint32_t row_limit, float* masked_color_out, int skip_sh, int skip_cov, hipStream_t s);
 void sgr_launch_masked_color_grad(int P, const uint32_t* clamped, const float* dL_dcolor, float* out, hipStream_t s);
 void sgr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, size_t means_stride,
                                    const float* campos, size_t campos_stride, const float* drgb, size_t drgb_stride,
@@ -361,8 +361,9 @@ sgr_pack_camera_kernel(SgrCam* cam, const float* view, const float* proj, const 
     if (blockIdx.x != 0) return;
     if (t < 16) {
         // word 6: the frame's tile-rect mode; word 7: whether its forward writes the compact hit list (the blend backward
-        // follows the FRAME's flag, whatever the switches say by the time it runs)
-        header[t] = t == 6 ? (rect_mode & 0xffu) : (t == 7 ? (rect_mode >> 8) : 0u);
+        // follows the FRAME's flag, whatever the switches say by the time it runs); word 8 (SGR_HDR_JAC): whether its
+        // preprocess writes the colour Jacobian (the per-Gaussian backward follows it the same way)
+        header[t] = t == 6 ? (rect_mode & 0xffu) : (t == 7 ? ((rect_mode >> 8) & 1u) : (t == SGR_HDR_JAC ? ((rect_mode >> 9) & 1u) : 0u));
         cam->view[t] = view[t];
         cam->proj[t] = proj ? proj[t] : 0.f;
     }
@@ -385,14 +386,14 @@ static_assert(SGR_STAT_SEG_MAX == SGR_MAX_STAT_SEGMENTS, "sgr_common.h and inclu
 
 static void pack_camera(const SgrGeomView& gv, const float* view, const float* proj, const float* campos,
                         float tan_fovx, float tan_fovy, int W, int H, float scale_modifier, uint2* ranges, int T,
-                        const Switches& sw, hipStream_t s) {
+                        const Switches& sw, bool jac, hipStream_t s) {
     const float focal_y = H / (2.0f * tan_fovy);  // rasterizer_impl.cu:225-226
     const float focal_x = W / (2.0f * tan_fovx);
     const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
     const int nb = std::max(1, std::min(64, (T + 255) / 256));
     sgr_pack_camera_kernel<<<nb, 256, 0, s>>>(cam_slot(gv), view, proj, campos, tan_fovx, tan_fovy, focal_x, focal_y, W, H,
                                              gx, gy, scale_modifier, gv.header, ranges, T,
-                                             (uint32_t)sw.rect_mode | (sw.hit_list ? 0x100u : 0u));
+                                             (uint32_t)sw.rect_mode | (sw.hit_list ? 0x100u : 0u) | (jac ? 0x200u : 0u));
 }
 
 // One 256-byte device block per DEVICE for the whole process (allocated on first use, kept): the flag word of
@@ -414,7 +415,7 @@ SgrFlagBlock sgr_acquire_flag_block() {
 extern "C" {
 
 const char* sgr_last_error(void) { return g_err.c_str(); }
-int sgr_version(void) { return 103; }  // 103: sgr_forward_layers (include/sgr_layers.h); 102: sgr_backward_extras gained masked_color_out + skip_sh_grad (101: color_ready_event + rows)
+int sgr_version(void) { return 104; }  // 104: sgr_forward_ex, sgr_backward_extras gained skip_cov3d_grad; 103: sgr_forward_layers (include/sgr_layers.h); 102: sgr_backward_extras gained masked_color_out + skip_sh_grad (101: color_ready_event + rows)
 
 size_t sgr_geometry_bytes(int P) {
     return sgr_required([&](char* b, char** e) { sgr_geom_carve(b, (size_t)P, e); });
@@ -427,6 +428,10 @@ size_t sgr_image_bytes(int width, int height) {
     return sgr_required([&](char* b, char** e) { sgr_img_carve(b, (size_t)width * height, T, e); });
 }
 int sgr_partial_row_floats(int S) { return sgr_partial_row_stride(S); }
+size_t sgr_geometry_jac_offset(int P) {
+    char* base = (char*)4096;  // (aligned: the carve starts where the caller's pointer, rounded up to 256, would)
+    return (size_t)((char*)sgr_geom_carve(base, (size_t)P).jac - base);
+}
 
 // The forward, and -- `layers` given -- the layer kernel behind it (include/sgr_layers.h; its arguments are checked by
 // sgr_forward_layers before this runs).  sgr_forward is this with layers == nullptr.
@@ -437,9 +442,12 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
                         const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                         const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                         float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_,
-                        const sgr_layer_images* layers) {
+                        const sgr_layer_images* layers, const sgr_forward_extras* fx = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     const Switches sw = resolve_switches();
+    // the call's own request, resolved with the switches: the preprocess stores the colour Jacobian for the backward
+    // (only where the colour comes from SH; the frame's header records it)
+    const bool want_jac = fx && fx->color_jacobian && shs != nullptr && colors_precomp == nullptr;
     const int W = width, H = height;
     if (P < 0 || W <= 0 || H <= 0) return fail(SGR_E_INVALID, "P, width and height must be positive");
     const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
@@ -530,10 +538,10 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
     // queues its own way -- the depth sort + scan.
     const auto preprocess = [&]() -> int {
         prof_begin(0, stream);
-        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, iv.ranges, (int)T, sw, stream);
+        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, iv.ranges, (int)T, sw, want_jac, stream);
         SGR_STAGE("pack_camera");
         sgr_launch_preprocess(P, D, M, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp,
-                              cam_slot(gv), gv, radii_ptr, prefiltered, sw.pre_stage(P), sw.rect_mode, stream);
+                              cam_slot(gv), gv, radii_ptr, prefiltered, sw.pre_stage(P), sw.rect_mode, want_jac, stream);
         SGR_STAGE("preprocess");
         prof_end(stream);
         return 0;
@@ -712,6 +720,20 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
                         out_depth, out_alpha, out_semantic, radii, debug, stream_, nullptr);
 }
 
+int sgr_forward_ex(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
+                   sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
+                   int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                   const float* semantics, const float* opacities, const float* scales, float scale_modifier,
+                   const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                   const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                   float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_,
+                   const sgr_forward_extras* extras) {
+    return forward_impl(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S,
+                        background, width, height, means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier,
+                        rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                        out_depth, out_alpha, out_semantic, radii, debug, stream_, nullptr, extras);
+}
+
 int sgr_forward_layers(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
                        sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
                        int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -820,9 +842,10 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
         return fail(SGR_E_INVALID, "means3D, background, alphas, dL_dpix, dL_dpix_depth and dL_dalphas are required");
     if (S > 0 && (!semantics || !dL_dpix_semantic || !dL_dsemantic))
         return fail(SGR_E_INVALID, "S > 0 needs semantics, dL_dpix_semantic and dL_dsemantic");
-    if (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot)
-        return fail(SGR_E_INVALID, "all gradient outputs except dL_dsh / dL_dsemantic are required");
     const int skip_sh = (extras && extras->skip_sh_grad) ? 1 : 0;
+    const int skip_cov = (extras && extras->skip_cov3d_grad) ? 1 : 0;
+    if (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || (!dL_dcov3D && !skip_cov) || !dL_dscale || !dL_drot)
+        return fail(SGR_E_INVALID, "all gradient outputs except dL_dsh / dL_dsemantic are required");
     if (shs && !dL_dsh && !skip_sh) return fail(SGR_E_INVALID, "shs given but dL_dsh is NULL");
     const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
     const size_t N = (size_t)W * H, T = (size_t)gx * gy;
@@ -881,7 +904,7 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
         P, D, M, S, means3D, radii_ptr, shs, scales, rotations, cov3D_precomp, cam_slot(gv), gv, partials, stride, touched, cd,
         dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dsemantic, sink, quad ? 1 : 0,
         sw.exact ? 1 : 0, W, H, extras ? (hipEvent_t)extras->color_ready_event : nullptr, sw.rs_wave ? 1 : 0,
-        (uint32_t)R, extras ? extras->masked_color_out : nullptr, skip_sh, stream);
+        (uint32_t)R, extras ? extras->masked_color_out : nullptr, skip_sh, skip_cov, stream);
     SGR_STAGE("gauss_bwd");
     prof_end(stream);
     if (ev_failed) return fail(SGR_E_HIP, "hipEventRecord(color_ready_event) failed: is it a valid event of this device?");

@@ -65,7 +65,12 @@ struct SgrGeomView {
     uint32_t* clamped;  // 3-bit mask per Gaussian, one u32 each (keeps stores simple and aligned)
     int* internal_radii;
     uint32_t* scan_tmp;   // block sums of the device-wide scan
-    uint32_t* header;     // [6]=tile-rect mode of the frame (0 reference rects, 1 bounding box, 2 box + mask, 3 marked list), [0]=error flag, [2]=depth beyond the 27-bit sort keys, [4]=num_rendered, [5]=num_rendered with the reference rects (one u64 counter), [16..]=SgrCam
+    float* jac;           // [9P] colour Jacobian d rgb / d dir of the SH evaluation, {dRGBdx.rgb, dRGBdy.rgb, dRGBdz.rgb} per Gaussian
+                          // (nine consecutive floats; nine planes and a 12-float padded record were measured and lost)
+                          // (backward.cu:46-140), written by the preprocess for the Gaussians that pass the cull when the
+                          // frame asked for it (header word SGR_HDR_JAC); the per-Gaussian backward then forms dL/ddir = J . dL/dRGB
+                          // from these 36 bytes instead of re-reading the 12 M-byte SH row.  LAST in the buffer: no other offset moved
+    uint32_t* header;     // [8]=the preprocess wrote `jac` (SGR_HDR_JAC), [6]=tile-rect mode of the frame (0 reference rects, 1 bounding box, 2 box + mask, 3 marked list), [0]=error flag, [2]=depth beyond the 27-bit sort keys, [4]=num_rendered, [5]=num_rendered with the reference rects (one u64 counter), [16..]=SgrCam
 };
 
 // 1: the forward writes the compact hit list (SgrBinView::hlist, SgrImgView::n_contrib_k) and the blend backward walks it.
@@ -108,6 +113,8 @@ struct SgrImgView {
     uint2* ranges;
     uint32_t* n_contrib_k;  // per pixel: n_contrib counted in entries of SgrBinView::hlist (last contributor's index in it + 1)
 };
+
+#define SGR_HDR_JAC 8  // geometry header word: 1 = this frame's preprocess wrote SgrGeomView::jac
 
 static inline size_t sgr_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -158,6 +165,7 @@ static inline SgrGeomView sgr_geom_carve(char* base, size_t P, char** end = null
         sgr_carve(p, v.dhist, nh);
         sgr_carve(p, v.scan_tmp, 2 * sgr_scan_tmp_count(nh > Pn ? nh : Pn));  // two sequences per scan launch
     }
+    sgr_carve(p, v.jac, 9 * Pn);
     if (end) *end = p;
     return v;
 }

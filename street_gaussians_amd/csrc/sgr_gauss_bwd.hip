@@ -336,7 +336,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
                      const SgrCam* __restrict__ camp, SgrGeomView gv, const float4* __restrict__ cd,
                      const float* __restrict__ dL_dmean2D, const float* __restrict__ dL_dcolor,
                      float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
-                     float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int skip_sh) {
+                     float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int skip_sh, int skip_cov) {
     const SgrCam& cam = *camp;
     // lanes past P stay alive (they help with the cooperative SH copies) on a clamped index; their stores are masked
     const int gidx = blockIdx.x * SGR_GB_THREADS + threadIdx.x;
@@ -352,6 +352,10 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
     // them into registers before the other half arrives.
     __shared__ float4 sSH[SGR_GB_THREADS / 64][32 * 12];
     const bool stage = shs != nullptr && M == 16;
+    // The frame's forward stored the colour Jacobian (header word SGR_HDR_JAC, wave-uniform): dL/ddir = J . dL/dRGB from 36
+    // bytes, and the SH row is not read at all.  Otherwise -- a forward that did not ask, or ran without SH -- `jac` was
+    // never written and is not touched: the row is read and contracted as before.
+    const bool has_jac = shs != nullptr && gv.header[SGR_HDR_JAC] != 0u;
     const int g0 = blockIdx.x * SGR_GB_THREADS + wave * 64;
     const int nrow4 = max(0, min(64, P - g0)) * 12;  // float4s of this wave's rows
     const int ncoef = (D + 1) * (D + 1);
@@ -429,7 +433,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
             for (int j = 0; j < 4; j++)
                 if ((4 * i + j) / 3 < ncoef) t[(4 * i + j) / 3] += e[j] * dRGB[(4 * i + j) % 3];
         };
-        if (stage) {
+        if (stage && !has_jac) {
             const uint64_t vis = __ballot(visible);
             const float4* src = reinterpret_cast<const float4*>(shs) + (size_t)g0 * 12;
 #pragma unroll
@@ -454,7 +458,13 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         if (visible) {
             sgr_sh_basis(D, dir[0], dir[1], dir[2], Y);
             const float* sh = shs + (size_t)idx * M * 3;
-            if (stage) {
+            float ddir[3], dm[3];
+            if (has_jac) {
+                float J[9];
+#pragma unroll
+                for (int e = 0; e < 9; e++) J[e] = gv.jac[9 * (size_t)idx + e];
+                sgr_jac_times_drgb(J, dRGB, ddir);
+            } else if (stage) {
                 // contracted above
             } else if (vec) {
                 const float4* sh4 = reinterpret_cast<const float4*>(sh);
@@ -466,8 +476,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
                 for (int k = 0; k < 16; k++)
                     if (k < ncoef) t[k] = sh[3 * k] * dRGB[0] + sh[3 * k + 1] * dRGB[1] + sh[3 * k + 2] * dRGB[2];
             }
-            float ddir[3], dm[3];
-            sgr_sh_dir_backward(D, dir[0], dir[1], dir[2], t, ddir);
+            if (!has_jac) sgr_sh_dir_backward(D, dir[0], dir[1], dir[2], t, ddir);
             sgr_dnormvdv(dir_orig, ddir, dm);
             dmean[0] += dm[0]; dmean[1] += dm[1]; dmean[2] += dm[2];
 #pragma unroll
@@ -518,7 +527,8 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
     dL_dmean3D[3 * idx + 1] = dmean[1];
     dL_dmean3D[3 * idx + 2] = dmean[2];
 #pragma unroll
-    for (int i = 0; i < 6; i++) dL_dcov3D[6 * (size_t)idx + i] = dcov[i];
+    for (int i = 0; i < 6; i++)
+        if (!skip_cov) dL_dcov3D[6 * (size_t)idx + i] = dcov[i];  // sgr_backward_extras.skip_cov3d_grad: nobody receives it
     dL_dscale[3 * idx + 0] = dscale[0];
     dL_dscale[3 * idx + 1] = dscale[1];
     dL_dscale[3 * idx + 2] = dscale[2];
@@ -532,7 +542,7 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
                           float4* cd, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                           float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dsemantic,
                           const SgrStatSink& sink, int quad, int exact, int W, int H, hipEvent_t after_rows, int rs_wave,
-                          uint32_t row_limit, float* masked_color_out, int skip_sh, hipStream_t s) {
+                          uint32_t row_limit, float* masked_color_out, int skip_sh, int skip_cov, hipStream_t s) {
     if (P <= 0) return 0;
     const float lsc = exact ? 1.0f : SGR_LOG2E;
     const float kx = (0.5f * (float)W) / lsc, ky = (0.5f * (float)H) / lsc;
@@ -568,6 +578,6 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
     const bool ev_failed = after_rows && hipEventRecord(after_rows, s) != hipSuccess;
     sgr_gauss_bwd_kernel<<<nb, SGR_GB_THREADS, 0, s>>>(P, D, M, means3D, radii, shs, scales, rotations, cov3D_precomp, cam,
                                                        gv, cd, dL_dmean2D, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                                       dL_dscale, dL_drot, skip_sh);
+                                                       dL_dscale, dL_drot, skip_sh, skip_cov);
     return ev_failed ? 1 : 0;
 }

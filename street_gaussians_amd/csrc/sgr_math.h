@@ -484,20 +484,22 @@ SGR_HD void sgr_cov2d_backward(const float* p, const float* cov3D, const SgrCam&
     const float c = A1x * T10 + A1y * T11 + A1z * T12 + 0.3f;
     const float denom = a * c - b * b;
     float dL_da = 0, dL_db = 0, dL_dc = 0;
+    float g0 = 0, g1 = 0, g2 = 0, g3 = 0, g4 = 0, g5 = 0;  // dL/dcov3D; zero where the reference leaves it at its zero fill
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
     if (denom2inv != 0) {
         dL_da = denom2inv * (-c * c * dcx + 2 * b * c * dcy + (denom - a * c) * dcw);
         dL_dc = denom2inv * (-a * a * dcw + 2 * a * b * dcy + (denom - a * c) * dcx);
         dL_db = denom2inv * 2 * (b * c * dcx - (denom + 2 * b * b) * dcy + a * b * dcw);
-        dL_dcov[0] = (T00 * T00 * dL_da + T00 * T10 * dL_db + T10 * T10 * dL_dc);
-        dL_dcov[3] = (T01 * T01 * dL_da + T01 * T11 * dL_db + T11 * T11 * dL_dc);
-        dL_dcov[5] = (T02 * T02 * dL_da + T02 * T12 * dL_db + T12 * T12 * dL_dc);
-        dL_dcov[1] = 2 * T00 * T01 * dL_da + (T00 * T11 + T01 * T10) * dL_db + 2 * T10 * T11 * dL_dc;
-        dL_dcov[2] = 2 * T00 * T02 * dL_da + (T00 * T12 + T02 * T10) * dL_db + 2 * T10 * T12 * dL_dc;
-        dL_dcov[4] = 2 * T02 * T01 * dL_da + (T01 * T12 + T02 * T11) * dL_db + 2 * T11 * T12 * dL_dc;
-    } else {
-        for (int i = 0; i < 6; i++) dL_dcov[i] = 0;
+        g0 = (T00 * T00 * dL_da + T00 * T10 * dL_db + T10 * T10 * dL_dc);
+        g3 = (T01 * T01 * dL_da + T01 * T11 * dL_db + T11 * T11 * dL_dc);
+        g5 = (T02 * T02 * dL_da + T02 * T12 * dL_db + T12 * T12 * dL_dc);
+        g1 = 2 * T00 * T01 * dL_da + (T00 * T11 + T01 * T10) * dL_db + 2 * T10 * T11 * dL_dc;
+        g2 = 2 * T00 * T02 * dL_da + (T00 * T12 + T02 * T10) * dL_db + 2 * T10 * T12 * dL_dc;
+        g4 = 2 * T02 * T01 * dL_da + (T01 * T12 + T02 * T11) * dL_db + 2 * T11 * T12 * dL_dc;
     }
+    // (stored once, behind the branch: with a store to dL_dcov in both arms the compiler merges them into ONE store with a
+    // variable index, and the caller's array -- registers otherwise -- lands in scratch memory)
+    dL_dcov[0] = g0; dL_dcov[1] = g1; dL_dcov[2] = g2; dL_dcov[3] = g3; dL_dcov[4] = g4; dL_dcov[5] = g5;
     const float dL_dT00 = 2 * A0x * dL_da + A1x * dL_db;
     const float dL_dT01 = 2 * A0y * dL_da + A1y * dL_db;
     const float dL_dT02 = 2 * A0z * dL_da + A1z * dL_db;
@@ -541,33 +543,55 @@ SGR_HD void sgr_proj_depth_backward(const float* m, const SgrCam& cam, float g2x
 // t[k] = sum_ch sh[3k + ch] * dL/dRGB[ch], returns dL/ddir = sum_k dY_k/d{x,y,z} * t[k]; the caller applies dnormvdv.
 // The reference sums dRGB/d{x,y,z} per channel first and contracts with dL/dRGB last; contracting first is the same sum
 // reassociated and needs 16 live values per Gaussian instead of 48 (the per-Gaussian backward's register budget).
+// TS = the stride of t: 3 reads one channel of an SH row in place (sgr_sh_color_jacobian).
+template <int TS = 1>
 SGR_HD void sgr_sh_dir_backward(int deg, float x, float y, float z, const float* t, float* dL_ddir) {
     float dx = 0.f, dy = 0.f, dz = 0.f;
     if (deg > 0) {
-        dx = -SGR_SH_C1 * t[3];
-        dy = -SGR_SH_C1 * t[1];
-        dz = SGR_SH_C1 * t[2];
+        dx = -SGR_SH_C1 * t[TS * 3];
+        dy = -SGR_SH_C1 * t[TS * 1];
+        dz = SGR_SH_C1 * t[TS * 2];
         if (deg > 1) {
             const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            dx += SGR_SH_C2_0 * y * t[4] + SGR_SH_C2_2 * 2.f * -x * t[6] + SGR_SH_C2_3 * z * t[7] + SGR_SH_C2_4 * 2.f * x * t[8];
-            dy += SGR_SH_C2_0 * x * t[4] + SGR_SH_C2_1 * z * t[5] + SGR_SH_C2_2 * 2.f * -y * t[6] + SGR_SH_C2_4 * 2.f * -y * t[8];
-            dz += SGR_SH_C2_1 * y * t[5] + SGR_SH_C2_2 * 2.f * 2.f * z * t[6] + SGR_SH_C2_3 * x * t[7];
+            dx += SGR_SH_C2_0 * y * t[TS * 4] + SGR_SH_C2_2 * 2.f * -x * t[TS * 6] + SGR_SH_C2_3 * z * t[TS * 7] + SGR_SH_C2_4 * 2.f * x * t[TS * 8];
+            dy += SGR_SH_C2_0 * x * t[TS * 4] + SGR_SH_C2_1 * z * t[TS * 5] + SGR_SH_C2_2 * 2.f * -y * t[TS * 6] + SGR_SH_C2_4 * 2.f * -y * t[TS * 8];
+            dz += SGR_SH_C2_1 * y * t[TS * 5] + SGR_SH_C2_2 * 2.f * 2.f * z * t[TS * 6] + SGR_SH_C2_3 * x * t[TS * 7];
             if (deg > 2) {
-                dx += (SGR_SH_C3_0 * t[9] * 3.f * 2.f * xy + SGR_SH_C3_1 * t[10] * yz + SGR_SH_C3_2 * t[11] * -2.f * xy +
-                       SGR_SH_C3_3 * t[12] * -3.f * 2.f * xz + SGR_SH_C3_4 * t[13] * (-3.f * xx + 4.f * zz - yy) +
-                       SGR_SH_C3_5 * t[14] * 2.f * xz + SGR_SH_C3_6 * t[15] * 3.f * (xx - yy));
-                dy += (SGR_SH_C3_0 * t[9] * 3.f * (xx - yy) + SGR_SH_C3_1 * t[10] * xz +
-                       SGR_SH_C3_2 * t[11] * (-3.f * yy + 4.f * zz - xx) + SGR_SH_C3_3 * t[12] * -3.f * 2.f * yz +
-                       SGR_SH_C3_4 * t[13] * -2.f * xy + SGR_SH_C3_5 * t[14] * -2.f * yz + SGR_SH_C3_6 * t[15] * -3.f * 2.f * xy);
-                dz += (SGR_SH_C3_1 * t[10] * xy + SGR_SH_C3_2 * t[11] * 4.f * 2.f * yz +
-                       SGR_SH_C3_3 * t[12] * 3.f * (2.f * zz - xx - yy) + SGR_SH_C3_4 * t[13] * 4.f * 2.f * xz +
-                       SGR_SH_C3_5 * t[14] * (xx - yy));
+                dx += (SGR_SH_C3_0 * t[TS * 9] * 3.f * 2.f * xy + SGR_SH_C3_1 * t[TS * 10] * yz + SGR_SH_C3_2 * t[TS * 11] * -2.f * xy +
+                       SGR_SH_C3_3 * t[TS * 12] * -3.f * 2.f * xz + SGR_SH_C3_4 * t[TS * 13] * (-3.f * xx + 4.f * zz - yy) +
+                       SGR_SH_C3_5 * t[TS * 14] * 2.f * xz + SGR_SH_C3_6 * t[TS * 15] * 3.f * (xx - yy));
+                dy += (SGR_SH_C3_0 * t[TS * 9] * 3.f * (xx - yy) + SGR_SH_C3_1 * t[TS * 10] * xz +
+                       SGR_SH_C3_2 * t[TS * 11] * (-3.f * yy + 4.f * zz - xx) + SGR_SH_C3_3 * t[TS * 12] * -3.f * 2.f * yz +
+                       SGR_SH_C3_4 * t[TS * 13] * -2.f * xy + SGR_SH_C3_5 * t[TS * 14] * -2.f * yz + SGR_SH_C3_6 * t[TS * 15] * -3.f * 2.f * xy);
+                dz += (SGR_SH_C3_1 * t[TS * 10] * xy + SGR_SH_C3_2 * t[TS * 11] * 4.f * 2.f * yz +
+                       SGR_SH_C3_3 * t[TS * 12] * 3.f * (2.f * zz - xx - yy) + SGR_SH_C3_4 * t[TS * 13] * 4.f * 2.f * xz +
+                       SGR_SH_C3_5 * t[TS * 14] * (xx - yy));
             }
         }
     }
     dL_ddir[0] = dx;
     dL_ddir[1] = dy;
     dL_ddir[2] = dz;
+}
+
+// The colour Jacobian J = d rgb / d dir of the SH evaluation, the reference's dRGBdx, dRGBdy, dRGBdz (backward.cu:46-129)
+// in that order: jac[3 a + c] = d rgb[c] / d dir[a].  Column c is sgr_sh_dir_backward of the row's channel c alone (the
+// polynomial has one definition); sh = the Gaussian's row, element 3 k + c = coefficient k of channel c.  The forward
+// stores J (SgrGeomView::jac) and the backward contracts it with dL/dRGB: sgr_jac_times_drgb, the reference's own
+// association (backward.cu:131-136).
+SGR_HD void sgr_sh_color_jacobian(int deg, float x, float y, float z, const float* sh, float* jac) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float d[3];
+        sgr_sh_dir_backward<3>(deg, x, y, z, sh + c, d);  // (reads coefficients below (deg + 1)^2 only)
+        jac[c] = d[0];
+        jac[3 + c] = d[1];
+        jac[6 + c] = d[2];
+    }
+}
+SGR_HD void sgr_jac_times_drgb(const float* jac, const float* dRGB, float* dL_ddir) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) dL_ddir[a] = jac[3 * a] * dRGB[0] + jac[3 * a + 1] * dRGB[1] + jac[3 * a + 2] * dRGB[2];
 }
 
 // auxiliary.h:107-117

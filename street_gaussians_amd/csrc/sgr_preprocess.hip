@@ -83,6 +83,18 @@ sgr_filter_kernel(int P, const float* __restrict__ means3D, const float* __restr
     filter_means2D[2 * idx + 1] = pr.py;
 }
 
+// The colour Jacobian of one Gaussian (sgr_math.h: sgr_sh_color_jacobian) from the SH row the colour was just evaluated
+// from, stored for the per-Gaussian backward (SgrGeomView::jac).  Called from inside the colour evaluation's
+// `fp contract(off)` scope, but a pragma is lexical: these products contract as the translation unit's default says, and
+// the colour's own operations are untouched.
+__device__ __forceinline__ void sgr_store_color_jacobian(int D, float x, float y, float z, const float* row,
+                                                         float* __restrict__ dst) {
+    float J[9];
+    sgr_sh_color_jacobian(D, x, y, z, row, J);
+#pragma unroll
+    for (int e = 0; e < 9; e++) dst[e] = J[e];
+}
+
 // K2.  One Gaussian per lane.  The SH rows of a wave's 64 Gaussians are one contiguous 12 KB block (M = 16) which every
 // lane reads with per-lane float4 loads at a 192-byte stride.  A/B form behind switch bit 6 (SGR_PRE_STAGE=1): once the
 // geometry has decided which Gaussians survive the cull, the wave copies the survivors' rows through LDS with
@@ -91,12 +103,13 @@ sgr_filter_kernel(int P, const float* __restrict__ means3D, const float* __restr
 // default.
 // num_rendered = sum of tiles_touched does not depend on the depth order, so it is accumulated here (one atomic per
 // workgroup into header[4]) and the host can read it back while the depth sort and the offset scan are still running.
+// (93 VGPRs with the J store, 3 below the 96 of five waves per SIMD: the next register costs a wave -- tools/occupancy_audit.py)
 __global__ void __launch_bounds__(SGR_PRE_THREADS)
 sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ scales,
                       const float* __restrict__ rotations, const float* __restrict__ opacities,
                       const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
                       const float* __restrict__ colors_precomp, const SgrCam* __restrict__ camp, SgrGeomView gv,
-                      int* __restrict__ radii, int prefiltered, int stage_sh, int tight) {
+                      int* __restrict__ radii, int prefiltered, int stage_sh, int tight, int want_jac) {
     // rows padded to 13 float4 (52 dwords): the per-lane float4 reads of 16 consecutive rows then fall on 16 disjoint
     // 4-bank groups (a 48-dword stride puts them on 4).  Dynamic LDS: none when the rows are read directly.
     extern __shared__ float4 sSHdyn[];
@@ -119,8 +132,8 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     if (stage) {
 #pragma clang fp contract(off)
         float Y[16];
+        float dx = p[0] - cam.campos[0], dy = p[1] - cam.campos[1], dz = p[2] - cam.campos[2];
         {
-            float dx = p[0] - cam.campos[0], dy = p[1] - cam.campos[1], dz = p[2] - cam.campos[2];
             const float t0 = dx * dx, t1 = dy * dy, t2 = dz * dz;
             const float len = sqrtf(t0 + t1 + t2);
             dx = dx / len; dy = dy / len; dz = dz / len;
@@ -154,6 +167,10 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                         }
                     }
                 }
+                // (J from the staged row itself, a second read of LDS: held in registers for it, the row costs a wave of occupancy)
+                if (want_jac)
+                    sgr_store_color_jacobian(D, dx, dy, dz, reinterpret_cast<const float*>(&sSH[wave][(lane & 31) * 13]),
+                                             gv.jac + 9 * (size_t)idx);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -206,11 +223,14 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                         else { r = r + Y[k] * buf[3 * k]; g = g + Y[k] * buf[3 * k + 1]; b = b + Y[k] * buf[3 * k + 2]; }
                     }
                 }
+                if (want_jac) sgr_store_color_jacobian(D, dx, dy, dz, buf, gv.jac + 9 * (size_t)idx);
             } else {
                 for (int k = 0; k < ncoef; k++) {
                     if (k == 0) { r = Y[0] * sh[0]; g = Y[0] * sh[1]; b = Y[0] * sh[2]; }
                     else { r = r + Y[k] * sh[3 * k]; g = g + Y[k] * sh[3 * k + 1]; b = b + Y[k] * sh[3 * k + 2]; }
                 }
+                // (rows that are not 16-byte aligned: the coefficients a second time, from the cache)
+                if (want_jac) sgr_store_color_jacobian(D, dx, dy, dz, sh, gv.jac + 9 * (size_t)idx);
             }
             r += 0.5f; g += 0.5f; b += 0.5f;
             clamped = (r < 0 ? 1u : 0u) | (g < 0 ? 2u : 0u) | (b < 0 ? 4u : 0u);
@@ -546,13 +566,13 @@ void sgr_launch_mark_visible(int P, const float* means3D, const float* viewmatri
 void sgr_launch_preprocess(int P, int D, int M, const float* means3D, const float* scales, const float* rotations,
                            const float* opacities, const float* shs, const float* cov3D_precomp,
                            const float* colors_precomp, const SgrCam* cam, const SgrGeomView& gv, int* radii,
-                           int prefiltered, bool stage_sh, int tight, hipStream_t s) {
+                           int prefiltered, bool stage_sh, int tight, bool want_jac, hipStream_t s) {
     if (P <= 0) return;
     const bool stage = stage_sh && shs != nullptr && colors_precomp == nullptr && M == 16;
     const size_t lds = stage ? (size_t)(SGR_PRE_THREADS / 64) * 32 * 13 * sizeof(float4) : 0;
     sgr_preprocess_kernel<<<(P + SGR_PRE_THREADS - 1) / SGR_PRE_THREADS, SGR_PRE_THREADS, lds, s>>>(
         P, D, M, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp, cam, gv, radii, prefiltered,
-        stage ? 1 : 0, tight);
+        stage ? 1 : 0, tight, (want_jac && shs != nullptr && colors_precomp == nullptr) ? 1 : 0);
 }
 
 void sgr_launch_filter(int P, const float* means3D, const float* scales, const float* rotations,

@@ -21,8 +21,9 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, stats=None):
+    # (grad mode is read HERE: inside an autograd Function's forward it is always off)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, stats)
+                                     cov3Ds_precomp, raster_settings, stats, torch.is_grad_enabled())
 
 
 # extension (not in the reference): the number of tile instances R of this process' most recent forward -- the reference
@@ -86,25 +87,28 @@ def _color_event(device):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, stats=None):
+                raster_settings, stats=None, grad_mode=True):
         # argument order of the native entry point (reference __init__.py:62-83)
         args = (raster_settings.bg, means3D, colors_precomp, semantics, opacities, scales, rotations,
                 raster_settings.scale_modifier, cov3Ds_precomp, raster_settings.viewmatrix, raster_settings.projmatrix,
                 raster_settings.tanfovx, raster_settings.tanfovy, raster_settings.image_height,
                 raster_settings.image_width, sh, raster_settings.sh_degree, raster_settings.campos,
                 raster_settings.prefiltered, raster_settings.debug)
+        # (extension) a backward will follow and the colour comes from SH: the forward also stores the colour Jacobian
+        # for it (sgr_forward_extras.color_jacobian).  Inference renders do not ask
+        want_jac = bool(grad_mode) and any(ctx.needs_input_grad) and isinstance(sh, torch.Tensor) and sh.numel() != 0
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args)  # copy them before they can be corrupted
             try:
                 (num_rendered, color, depth, alpha, semantic, radii, geomBuffer, binningBuffer,
-                 imgBuffer) = _C.rasterize_gaussians(*args)
+                 imgBuffer) = _C.rasterize_gaussians(*args, color_jacobian=want_jac)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise ex
         else:
             (num_rendered, color, depth, alpha, semantic, radii, geomBuffer, binningBuffer,
-             imgBuffer) = _C.rasterize_gaussians(*args)
+             imgBuffer) = _C.rasterize_gaussians(*args, color_jacobian=want_jac)
 
         _LAST["num_rendered"] = num_rendered
         ctx.raster_settings = raster_settings
@@ -148,6 +152,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         if BACKWARD_OBSERVERS and means3D.is_cuda:
             color_event = _color_event(means3D.device)
         kw = {}
+        if cov3Ds_precomp is None or cov3Ds_precomp.numel() == 0:
+            kw["skip_cov3d_grad"] = True  # scales / rotations are used: nobody receives dL/dcov3D
         if BACKWARD_SINKS and means3D.is_cuda:  # (weakly held reducers: see BACKWARD_SINKS)
             inputs = {"means3D": means3D, "scales": scales, "rotations": rotations, "sh": sh, "semantics": semantics,
                       "colors": colors_precomp, "cov3D": cov3Ds_precomp}
@@ -184,9 +190,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         # autograd (None / empty placeholders) are dropped instead of returned and ignored
         need = ctx.needs_input_grad
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_semantics, grad_opacities,
-                 grad_scales, grad_rotations, grad_cov3Ds_precomp, None, None)
-        grads = tuple(g if (g is not None and need[i]) else None for i, g in enumerate(grads))
-        return grads
+                 grad_scales, grad_rotations, grad_cov3Ds_precomp, None, None, None)
+        grads = tuple(g if (g is not None and need[i]) else None for i, g in enumerate(grads[:len(need)]))
+        return grads  # (one per argument apply() was given: stats and grad_mode are optional)
 
 
 class GaussianRasterizationSettings(NamedTuple):
