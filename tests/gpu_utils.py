@@ -364,7 +364,7 @@ def _reference_arrays(rf):
     return "oracle", get
 
 
-def strict_mode_against_reference(kw, wts, S, label, rf=None, gref=None, allow=None):
+def strict_mode_against_reference(kw, wts, S, label, rf=None, gref=None, allow=None, oracle_sum=False):
     """The library in its STRICTLY CONFORMING configuration -- parity arithmetic on the reference's own tile rects,
     `_C.EXACT | _C.REF_RECT` (SGR_EXACT=1 SGR_REF_RECT=1), the one bench.py reports -- against a reference, end to end,
     with nothing of the library's own between the two sides: the binning arrays are compared with the reference's ENTRY FOR
@@ -387,7 +387,9 @@ def strict_mode_against_reference(kw, wts, S, label, rf=None, gref=None, allow=N
 
     Whatever the reference: a second backward over the same forward state is bit-identical; the compact hit list and
     n_contrib_k are what check_hit_list defines; every list position outside its Gaussian's cut-down rect has a zero hit
-    byte (check_dead_marks).  Returns (res, g, internal)."""
+    byte (check_dead_marks).  `oracle_sum`: the `parallel` argument of the C oracle's backward (oracle.backward) -- "exact" where
+    one Gaussian covers millions of pixels and the oracle's sequential float32 sum is itself off by more than the gate (see
+    tests/test_gpu_frame_bounds.py).  Returns (res, g, internal)."""
     own = rf is None
     rerun = {}
     if own:
@@ -427,7 +429,7 @@ def strict_mode_against_reference(kw, wts, S, label, rf=None, gref=None, allow=N
             image_close(npy(res[k]), get(k), name=f"strict {label}: {k}")
         assert (nc != get("n_contrib").reshape(-1)).mean() <= 1e-3, f"{label}: n_contrib differs beyond exp-ulp flips"
         from oracle import oracle
-        same = oracle_backward_same_state(oracle, rf, res, wts, S)
+        same = oracle_backward_same_state(oracle, rf, res, wts, S, parallel=oracle_sum)
         for k in GRAD_NAMES:
             gate = dict(SAME_STATE_GATE)
             if (allow or {}).get(k):  # a documented per-case, per-tensor exception: that many elements, the cap unchanged

@@ -131,3 +131,51 @@ def test_reset_opacity_matches_reference():
     assert torch.allclose(new.cpu(), m.p["opacity"], rtol=2e-6, atol=2e-6)
     assert float(ag.abs().max()) == 0.0 and float(bg.abs().max()) == 0.0
     assert float(torch.sigmoid(new).max()) <= 0.01 * (1 + 1e-5)
+
+
+# ---- past the block caps ----------------------------------------------------------------------------------------------
+# sgr_densify_count_kernel runs at most 1024 workgroups of 256 lanes and sgr_densify_prune_kernel at most 2048, each with a
+# grid-stride loop behind the cap: the count wraps above N = 262 144, the prune above 524 288 candidates.  One N takes both
+# loops into their second trip, for each of the three prune rules.
+N_PAST_CAPS = 530000
+
+
+@pytest.mark.parametrize("variant", ["plain", "bkgd", "actor"])
+def test_densify_and_prune_past_the_block_caps(variant):
+    N = N_PAST_CAPS
+    params, states, accum, denom, g = _setup(N, 1, 4, 1, 41)
+    normals = torch.randn(2 * N, 3, generator=g)
+    extra, keys = {}, ["points_total", "points_clone", "points_split", "points_pruned"]
+    if variant == "bkgd":  # the sphere of test_background_model_prune_rule
+        extra = dict(variant="bkgd", sphere_center=torch.tensor([0.5, -1.0, 0.3]), sphere_radius=2.5)
+        keys = keys + ["points_below_min_opacity", "points_big_ws"]
+    elif variant == "actor":  # the box and box_normals of test_actor_model_prune_rule
+        params["xyz"] *= 0.3
+        probe = ref.Model(params, states, accum, denom)
+        probe.densify_and_prune(prune_big=False, normals=normals, **dict(KW, min_opacity=-1.0))
+        zb = torch.randn(probe.p["xyz"].shape[0], 2, 3, generator=g)
+        extra = dict(variant="actor", box_min=torch.tensor([-1.2, -0.9, -1.5]), box_max=torch.tensor([1.1, 1.0, 1.4]),
+                     box_normals=zb)
+    m = ref.Model(params, states, accum, denom)
+    want = m.densify_and_prune(prune_big=True, normals=normals, **extra, **KW)
+    # both loops wrap: the count kernel walks the N flags; the prune kernel walks the candidates -- the originals that were
+    # not split, the clones and two children per split point
+    n_cand = N + want["points_clone"] + want["points_split"]
+    assert N > 262144 and n_cand > 524288, (N, n_cand)
+    assert want["points_clone"] > 0 and want["points_split"] > 0 and 0 < want["points_pruned"] < n_cand
+    if variant == "bkgd":
+        assert want["points_big_ws"] > 0
+    dev = lambda t: t.cuda()
+    if "box_normals" in extra:
+        extra = dict(extra, box_normals=dev(extra["box_normals"]))
+    new_p, new_s, got, index = densify.densify_and_prune(
+        {k: dev(v) for k, v in params.items()}, dev(accum), dev(denom), prune_big=True,
+        states={k: (dev(a), dev(b)) for k, (a, b) in states.items()}, normals=dev(normals[:2 * want["points_split"]]),
+        **extra, **KW)
+    if variant == "plain":  # as test_densify_and_prune_matches_reference_steps: the whole result, and its tighter bound
+        assert got == want
+        for k in ("xyz", "scaling"):
+            assert torch.allclose(new_p[k].cpu(), m.p[k], rtol=2e-6, atol=2e-6), k
+    _check(new_p, new_s, got, index, m, want, keys)
+    kinds = index["kind"].cpu()
+    assert (kinds[:-1] <= kinds[1:]).all()  # originals, then clones, then split children

@@ -253,12 +253,12 @@ def test_strict_mode_cases_against_reference_kernels(name):
 STRICT_ORACLE_ALLOW = {"edge65": {"scales": 1}}
 
 
-def _strict_legs(kw, wts, S, label):
+def _strict_legs(kw, wts, S, label, oracle_sum=False):
     """The strict leg of a case that has a `mode` parameter: against the C oracle always, and against the reference's own
-    kernels as well where oracle/_ref travelled -- nothing is skipped."""
+    kernels as well where oracle/_ref travelled -- nothing is skipped.  (`oracle_sum`: strict_mode_against_reference.)"""
     from oracle import ref
     fw = oracle.forward(**kw)
-    strict_mode_against_reference(kw, wts, S, label, rf=fw, allow=STRICT_ORACLE_ALLOW.get(label))
+    strict_mode_against_reference(kw, wts, S, label, rf=fw, allow=STRICT_ORACLE_ALLOW.get(label), oracle_sum=oracle_sum)
     fw.free()
     if ref.available():
         strict_mode_against_reference(kw, wts, S, label, allow=STRICT_ALLOW.get(label))
