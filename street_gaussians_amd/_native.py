@@ -92,6 +92,12 @@ def _signatures():
         "sgr_densify_prune_mask": (i, [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i64p, vp]),
         "sgr_densify_compact": (i, [i, vp, vp, vp, i64p, vp]),
         "sgr_reset_opacity": (i, [i, vp, vp, vp, vp]),
+        "sgr_densify_scene_work_bytes": (sz, [i, i]),
+        "sgr_densify_scene_plan": (i, [i, i] + [vp] * 7 + [i64p, vp]),
+        "sgr_densify_scene_layout": (i, [i, vp, i64p, i64p]),
+        "sgr_densify_scene_map": (i, [i, i] + [vp] * 7),
+        "sgr_densify_scene_prune": (i, [i, i] + [vp] * 14 + [i64p, vp]),
+        "sgr_densify_scene_gather_ragged": (i, [i, vp, vp, i64p, vp, i, vp, vp, vp, i, vp, vp]),
         "sgr_texture_cube_workspace_bytes": (sz, [i, i, i, i, i64]),
         "sgr_texture_cube_forward": (i, [i, i, i, i, i64, vp, vp, vp, vp]),
         "sgr_texture_cube_backward": (i, [i, i, i, i, i64, vp, vp, vp, vp, vp]),

@@ -14,57 +14,14 @@
 #include <cstdint>
 #include <string>
 
-#include "../../include/sgr_densify.h"
-#include "sgr_common.h"
-
-struct DnWork {
-    uint32_t *flags, *offA, *offB, *offS, *offC, *tmp, *totals;  // totals: nA nB nS nC nClone nPrunedCand
-};
-static DnWork dn_carve(char* base, size_t N) {
-    DnWork w;
-    char* p = base;
-    const size_t n = N ? N : 1;
-    sgr_carve(p, w.flags, n);
-    sgr_carve(p, w.offA, n);
-    sgr_carve(p, w.offB, n);
-    sgr_carve(p, w.offS, n);
-    sgr_carve(p, w.offC, n);
-    sgr_carve(p, w.tmp, sgr_scan_tmp_count(n));
-    sgr_carve(p, w.totals, 16);
-    return w;
-}
-
-#define DN_CLONE 1u
-#define DN_SPLIT 2u
-#define DN_PRUNE_SELF 4u
-#define DN_PRUNE_CHILD 8u
+#include "sgr_densify_rules.h"  // the work area and the two per-row decisions, shared with sgr_densify_scene.hip
 
 __global__ void __launch_bounds__(256)
 sgr_densify_flags_kernel(int N, sgr_densify_params p, const float* __restrict__ accum, const float* __restrict__ denom,
                          const float* __restrict__ scaling, const float* __restrict__ opacity, DnWork w) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    float g = accum[2 * i + p.grad_column] / denom[i];  // :523
-    if (g != g) g = 0.0f;                                // grads[grads.isnan()] = 0.0 (:524)
-    const float s0 = expf(scaling[3 * i]), s1 = expf(scaling[3 * i + 1]), s2 = expf(scaling[3 * i + 2]);
-    const float smax = fmaxf(s0, fmaxf(s1, s2));
-    const float dense = p.percent_dense * p.extent;
-    const bool clone = (fabsf(g) >= p.max_grad) && (smax <= dense);  // :497-499 (norm of a 1-vector)
-    const bool split = (g >= p.max_grad) && (smax > dense);          // :462-464
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));
-    const bool low = op < p.min_opacity;                              // :533
-    const float big = p.extent * p.percent_big_ws;
-    const bool prune_self = !p.defer_prune && (low || (p.prune_big && smax > big));  // :536-540
-    // children: log(scale / (0.8 N)) -> exp gives scale / (0.8 N) again (up to rounding, like the reference's log/exp)
-    const float child = expf(logf(smax / (0.8f * (float)p.n_split)));
-    const bool prune_child = !p.defer_prune && (low || (p.prune_big && child > big));
-    const uint32_t f = (clone ? DN_CLONE : 0u) | (split ? DN_SPLIT : 0u) | (prune_self ? DN_PRUNE_SELF : 0u) |
-                       (prune_child ? DN_PRUNE_CHILD : 0u);
-    w.flags[i] = f;
-    w.offA[i] = (!split && !prune_self) ? 1u : 0u;
-    w.offB[i] = (clone && !prune_self) ? 1u : 0u;
-    w.offS[i] = split ? 1u : 0u;
-    w.offC[i] = (split && !prune_child) ? 1u : 0u;
+    dn_store_masks(w, (size_t)i, dn_decide_flags(p, accum, denom, scaling, opacity, (size_t)i));
 }
 
 // number of cloned points (not a scan total: clones that are pruned again still count, gaussian_model.py:500-502).  An
@@ -90,28 +47,12 @@ sgr_densify_map_kernel(int N, int n_split, DnWork w, int32_t* __restrict__ src, 
                        int32_t* __restrict__ sample_row) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const uint32_t f = w.flags[i];
-    const uint32_t nA = w.totals[0], nB = w.totals[1], nS = w.totals[2], nC = w.totals[3];
-    const bool split = f & DN_SPLIT;
-    if (!split && !(f & DN_PRUNE_SELF)) {
-        const uint32_t o = w.offA[i];
-        src[o] = i; kind[o] = SGR_KIND_KEEP; sample_row[o] = -1;
-    }
-    if ((f & DN_CLONE) && !(f & DN_PRUNE_SELF)) {
-        const uint32_t o = nA + w.offB[i];
-        src[o] = i; kind[o] = SGR_KIND_CLONE; sample_row[o] = -1;
-    }
-    if (split && !(f & DN_PRUNE_CHILD)) {
-        for (int n = 0; n < n_split; n++) {  // repeat(N, 1): copy-major (:468-476)
-            const uint32_t o = nA + nB + (uint32_t)n * nC + w.offC[i];
-            src[o] = i; kind[o] = SGR_KIND_SPLIT_CHILD; sample_row[o] = (int32_t)((uint32_t)n * nS + w.offS[i]);
-        }
-    }
+    dn_map_row(w.flags[i], i, 0u, w.totals[0], w.totals[1], w.totals[2], w.totals[3], w.offA[i], w.offB[i], w.offS[i], w.offC[i],
+               n_split, 0u, src, kind, sample_row);
 }
 
-// One workgroup builds 128 consecutive result rows: their source rows / kinds are staged in LDS once, then one lane per
-// float walks the 128 * width outputs (coalesced stores, row-wise contiguous loads, 32-bit index arithmetic).
-#define SGR_DN_ROWS 128
+// One workgroup builds SGR_DN_ROWS (128) consecutive result rows: their source rows / kinds are staged in LDS once, then one
+// lane per float walks the 128 * width outputs (coalesced stores, row-wise contiguous loads, 32-bit index arithmetic).
 // WT > 0: the row width as a compile-time constant (the per-element row / column split is a multiply-shift instead of a
 // 32-bit division, which was most of the kernel's instructions: 1 TB/s with the runtime width); WT == 0: any width.
 template <int WT>
@@ -172,53 +113,17 @@ sgr_densify_children_kernel(int n_out, int n_split, const int32_t* __restrict__ 
 }
 
 // ---- prune rules on the candidate set (include/sgr_densify.h) ----------------------------------------------------
-struct DnSphere { float cx, cy, cz, r; };
-struct DnBox { float lo[3], hi[3]; };
 __global__ void __launch_bounds__(256)
 sgr_densify_prune_kernel(int n, sgr_densify_params p, int variant, const float* __restrict__ xyz,
                          const float* __restrict__ scaling, const float* __restrict__ rotation,
                          const float* __restrict__ opacity, DnSphere sph, DnBox box,
                          const float* __restrict__ box_normals, uint8_t* __restrict__ prune, uint32_t* __restrict__ cnt) {
-#pragma clang fp contract(off)
     uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    bool low = false, big = false, outside = false;
-    {
-        const float op = 1.0f / (1.0f + expf(-opacity[i]));
-        low = op < p.min_opacity;
-        const float s[3] = {expf(scaling[3 * i]), expf(scaling[3 * i + 1]), expf(scaling[3 * i + 2])};
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        if (p.prune_big) {
-            big = fmaxf(s[0], fmaxf(s[1], s[2])) > p.extent * p.percent_big_ws;
-            if (variant == SGR_PRUNE_BKGD) {  // gaussian_model_bkgd.py:95-97
-                const float dx = x - sph.cx, dy = y - sph.cy, dz = z - sph.cz;
-                const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
-                if (dist > 2.0f * sph.r) big = false;
-            }
-            if (variant == SGR_PRUNE_ACTOR) {  // gaussian_model_actor.py:231-249
-                float qw = rotation[4 * i], qx = rotation[4 * i + 1], qy = rotation[4 * i + 2], qz = rotation[4 * i + 3];
-                const float nrm = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-                qw /= nrm; qx /= nrm; qy /= nrm; qz /= nrm;
-                const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qw * qz), 2.f * (qx * qz + qw * qy),
-                                    2.f * (qx * qy + qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qw * qx),
-                                    2.f * (qx * qz - qw * qy), 2.f * (qy * qz + qw * qx), 1.f - 2.f * (qx * qx + qy * qy)};
-                const float c[3] = {x, y, z};
-                bool inside = true;
-                for (int m = 0; m < 2; m++) {
-                    const float* zn = box_normals + (size_t)(2 * i + m) * 3;
-                    const float v[3] = {zn[0] * s[0], zn[1] * s[1], zn[2] * s[2]};
-#pragma unroll
-                    for (int a = 0; a < 3; a++) {
-                        const float w = R[3 * a] * v[0] + R[3 * a + 1] * v[1] + R[3 * a + 2] * v[2] + c[a];
-                        inside = inside && (w >= box.lo[a]) && (w <= box.hi[a]);
-                    }
-                }
-                outside = !inside;
-            }
-        }
-        prune[i] = (low || big || outside) ? 1 : 0;
-    }
-    c0 += low; c1 += big; c2 += outside; c3 += (low || big || outside);
+        const uint32_t d = dn_decide_prune(p, variant, xyz, scaling, rotation, opacity, sph, box,
+                                           box_normals ? box_normals + 6 * (size_t)i : nullptr, (size_t)i);
+        prune[i] = d ? 1 : 0;
+        c0 += (d & DN_LOW) ? 1u : 0u; c1 += (d & DN_BIG) ? 1u : 0u; c2 += (d & DN_OUTSIDE) ? 1u : 0u; c3 += d ? 1u : 0u;
     }
     // four counters (integers: order-independent): per-thread over the grid-stride loop, then one atomic each per
     // WORKGROUP -- one per wave were 440 k device-scope atomics on four words at 7 M candidates, 3.7 ms (rocprofv3)

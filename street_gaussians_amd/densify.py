@@ -15,12 +15,17 @@ they are drawn with ``torch.randn`` -- same distribution, not the same random st
 ``"actor"`` = GaussianModelActor.densify_and_prune (gaussian_model_actor.py:204-261: points whose sampled extent
 leaves the tracking box are pruned).  Those rules look at the NEW points' positions, so the candidates (kept originals,
 clones, split children) are laid out first and pruned in a second step (sgr_densify_prune_mask / _compact).
-``reset_opacity`` is GaussianModel.reset_opacity (gaussian_model.py:410-414)."""
+``reset_opacity`` is GaussianModel.reset_opacity (gaussian_model.py:410-414).
+
+``densify_scene`` is the reference's loop over its models (street_gaussian_model.py:573-586) for a ``scene.FlatScene``: every
+model's own rule applied to its block of the flat tensors in one pass (include/sgr_densify_scene.h), bit-identical to
+calling ``densify_and_prune`` per model and concatenating."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _alloc, _native
@@ -246,6 +251,220 @@ def _densify_two_step(params, xyz_gradient_accum, denom, *, max_grad, min_opacit
         if prune_big:
             scalars["points_big_ws"] = int(pc[1])
     return new_params, new_states, scalars, {"src": src_f, "kind": kind_f}
+
+
+# ---- a whole FlatScene in one pass (include/sgr_densify_scene.h) -----------------------------------------------------
+class _CSceneSeg(C.Structure):
+    _fields_ = [("start", C.c_int32), ("count", C.c_int32), ("dc_width", C.c_int32), ("sem_width", C.c_int32),
+                ("dc_offset", C.c_int64), ("sem_offset", C.c_int64), ("params", _CParams), ("variant", C.c_int32),
+                ("sphere", C.c_float * 4), ("box", C.c_float * 6)]
+
+
+_RULE_REQUIRED = ("max_grad", "min_opacity", "extent", "percent_dense", "percent_big_ws", "prune_big")
+_RULE_OPTIONAL = {"grad_column": 0, "n_split": 2, "variant": None, "sphere_center": None, "sphere_radius": None,
+                  "box_min": None, "box_max": None}
+_FLAT_ATTRS = ("xyz", "rotation", "scaling", "opacity", "features_dc", "features_rest", "semantic")
+
+
+def _floats(v, n, what):
+    out = [float(x) for x in torch.as_tensor(v).flatten().tolist()]
+    if len(out) != n:
+        raise ValueError(f"densify_scene: {what} must hold {n} values, got {len(out)}")
+    return out
+
+
+def scene_table(meta: Sequence[dict], rules: Sequence[dict]):
+    """The sgr_densify_scene_segment table (host) of a FlatScene's ``meta`` and one rule per model: the keyword arguments
+    of ``densify_and_prune`` (max_grad, min_opacity, extent, percent_dense, percent_big_ws, prune_big; optional grad_column,
+    n_split, variant, sphere_center, sphere_radius, box_min, box_max).  ValueError for a malformed rule."""
+    if len(rules) != len(meta):
+        raise ValueError(f"densify_scene: {len(meta)} models but {len(rules)} rules")
+    tab = (_CSceneSeg * max(len(meta), 1))()
+    row = dc = sem = 0
+    nan = float("nan")
+    for i, (m, rule) in enumerate(zip(meta, rules)):
+        unknown = [k for k in rule if k not in _RULE_REQUIRED and k not in _RULE_OPTIONAL]
+        missing = [k for k in _RULE_REQUIRED if k not in rule]
+        if unknown or missing:
+            raise ValueError(f"densify_scene: rules[{i}]: unknown keys {unknown}, missing keys {missing}")
+        r = dict(_RULE_OPTIONAL, **rule)
+        if r["variant"] not in _VARIANTS:
+            raise ValueError(f"densify_scene: rules[{i}]: unknown variant {r['variant']!r}")
+        c = tab[i]
+        n, dcw, sw = int(m["count"]), 3 * int(m["fourier_dim"]), int(m["sem_width"])
+        c.start, c.count, c.dc_width, c.sem_width, c.dc_offset, c.sem_offset = row, n, dcw, sw, dc, sem
+        row, dc, sem = row + n, dc + n * dcw, sem + n * sw
+        c.params = _CParams(float(r["max_grad"]), float(r["min_opacity"]), float(r["extent"]), float(r["percent_dense"]),
+                            float(r["percent_big_ws"]), int(bool(r["prune_big"])), int(r["grad_column"]), int(r["n_split"]), 1)
+        c.variant = _VARIANTS[r["variant"]]
+        c.sphere = (C.c_float * 4)(nan, nan, nan, nan)
+        c.box = (C.c_float * 6)(*[nan] * 6)
+        if r["variant"] == "bkgd":
+            if r["sphere_center"] is None or r["sphere_radius"] is None:
+                raise ValueError(f'densify_scene: rules[{i}]: variant "bkgd" needs sphere_center and sphere_radius')
+            c.sphere = (C.c_float * 4)(*_floats(r["sphere_center"], 3, "sphere_center"), *_floats(r["sphere_radius"], 1, "sphere_radius"))
+        if r["variant"] == "actor" and r["prune_big"]:
+            if r["box_min"] is None or r["box_max"] is None:
+                raise ValueError(f'densify_scene: rules[{i}]: variant "actor" needs box_min and box_max')
+            c.box = (C.c_float * 6)(*_floats(r["box_min"], 3, "box_min"), *_floats(r["box_max"], 3, "box_max"))
+    return tab
+
+
+def scene_layout(table, nseg: int, totals) -> dict:
+    """Where every model's blocks start, from the per-model totals of the plan ([nseg, 4]: kept originals, clones, split
+    points, split points with children), by sgr_densify_scene_layout (host only).  Returns ``cand_base``, ``normals_base``,
+    ``box_base`` (nseg + 1 entries each, the last = the size of the candidate arrays / of ``normals`` / of ``box_normals``
+    in rows) and ``requests``: the ``(model, "split" | "box", rows)`` blocks of standard normals in the order the per-model
+    loop asks its ``normal_source`` for them -- per model its split block (when it splits anything), then its box block (the
+    actor rule with prune_big: two samples per candidate, also when it has no candidates)."""
+    tot = (C.c_int64 * (4 * nseg))(*[int(v) for v in np.asarray(totals).reshape(-1)])
+    lay = (C.c_int64 * (3 * (nseg + 1)))()
+    check(_native.lib().sgr_densify_scene_layout(nseg, table, tot, lay))
+    lay = np.array(lay[:], dtype=np.int64).reshape(nseg + 1, 3)
+    requests = []
+    for s in range(nseg):
+        n_norm, n_box = int(lay[s + 1, 1] - lay[s, 1]), int(lay[s + 1, 0] - lay[s, 0])
+        if n_norm:
+            requests.append((s, "split", n_norm))
+        if table[s].variant == _VARIANTS["actor"] and table[s].params.prune_big:
+            requests.append((s, "box", 2 * n_box))
+    return {"cand_base": lay[:, 0], "normals_base": lay[:, 1], "box_base": lay[:, 2], "requests": requests}
+
+
+def _scene_normals(lay, normals, box_normals, normal_source, dev):
+    """The scene's ``normals`` [rows, 3] and ``box_normals`` [rows, 2, 3]: the caller's tensors (shape-checked), else
+    filled block by block from ``normal_source`` / ``torch.randn`` in the order of ``lay['requests']``."""
+    n_norm, n_box = int(lay["normals_base"][-1]), int(lay["box_base"][-1])
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()
+    given = {"split": normals is not None, "box": box_normals is not None}
+    if given["split"] and tuple(normals.shape) != (n_norm, 3):
+        raise ValueError(f"densify_scene: normals must have dimensions ({n_norm}, 3)")
+    if given["box"] and tuple(box_normals.shape) != (n_box, 2, 3):
+        raise ValueError(f"densify_scene: box_normals must have dimensions ({n_box}, 2, 3)")
+    out = {"split": f32(normals) if given["split"] else torch.empty(n_norm, 3, device=dev),
+           "box": f32(box_normals).view(2 * n_box, 3) if given["box"] else torch.empty(2 * n_box, 3, device=dev)}
+    base = {"split": lay["normals_base"], "box": 2 * lay["box_base"]}
+    for s, what, rows in lay["requests"]:
+        if given[what]:
+            continue
+        t = normal_source(rows, dev) if normal_source is not None else torch.randn(rows, 3, device=dev)
+        if tuple(t.shape) != (rows, 3):
+            raise ValueError(f"densify_scene: normal_source returned {tuple(t.shape)} for a request of ({rows}, 3)")
+        if rows:
+            b = int(base[what][s])
+            out[what][b:b + rows].copy_(t)
+    return out["split"], out["box"]
+
+
+def densify_scene(flat, xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, rules: Sequence[dict],
+                  moments: Optional[Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]] = None,
+                  normals: Optional[torch.Tensor] = None, box_normals: Optional[torch.Tensor] = None, normal_source=None):
+    """Density control of every model of a ``scene.FlatScene`` in one pass: ``rules[i]`` (see ``scene_table``) is applied to
+    model i's block.  ``xyz_gradient_accum`` [N, 2] / ``denom`` [N, 1] are ``scene.FlatStats``' flat tensors; ``moments`` =
+    ``(exp_avg, exp_avg_sq)``, dicts keyed by flat attribute as ``optim.SegmentedAdam`` holds them.
+
+    Returns ``(new_flat, new_moments, scalars, index)``: block i of every new flat tensor is bit for bit what
+    ``densify_and_prune(flat.views()[i], ..., **rules[i])`` returns (moments of new rows zero), ``scalars[i]`` is that
+    call's counter dict, ``index`` = {'src' (flat source row), 'kind', 'counts' (rows per model)}.  ``new_flat`` shares
+    ``flat``'s pose leaf and per-model settings; hand ``new_moments`` to ``SegmentedAdam.rebuild_flat``.
+
+    ``normals`` [sum of n_split * points_split, 3] / ``box_normals`` [sum of the candidates of the actor models with
+    prune_big, 2, 3] are the per-model tensors concatenated in model order; when not given, ``normal_source`` (or
+    ``torch.randn``) is asked per model, in the per-model loop's order and sizes (``scene_layout``).  Two host waits and
+    a fixed number of launches, whatever the number of models; n_split is one value for the scene.  GPU only."""
+    from .optim import _pinned_to
+    from .scene import FlatScene
+    K = len(flat.meta)
+    table = scene_table(flat.meta, rules)
+    if K == 0:
+        raise ValueError("densify_scene: the scene has no models")
+    if moments is not None:
+        if len(moments) != 2 or any(set(d) != set(_FLAT_ATTRS) for d in moments):
+            raise ValueError(f"densify_scene: moments = (exp_avg, exp_avg_sq), each a dict with the keys {_FLAT_ATTRS}")
+    ins = [flat.tensors[k] for k in _FLAT_ATTRS] + [xyz_gradient_accum, denom] + ([t for d in moments for t in d.values()] if moments else [])
+    if not all(t.is_cuda for t in ins):
+        raise SgrError("densify_scene needs HIP (cuda) tensors: there is no CPU path")
+    dev, N = flat.xyz.device, int(flat.xyz.shape[0])
+    L = _native.lib()
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()
+    T = {k: f32(flat.tensors[k]) for k in _FLAT_ATTRS}
+    if moments is not None:
+        for d in moments:
+            for k in _FLAT_ATTRS:
+                if d[k].numel() != T[k].numel():
+                    raise ValueError(f"densify_scene: the moments of {k} have {d[k].numel()} elements, the parameter {T[k].numel()}")
+    acc, den = f32(xyz_gradient_accum), f32(denom)
+    if acc.numel() != 2 * N or den.numel() != N:
+        raise ValueError(f"densify_scene: statistics of {den.numel()} rows for a scene of {N}")
+    want = {"xyz": 3 * N, "rotation": 4 * N, "scaling": 3 * N, "opacity": N,  # the kernels index by these sizes
+            "features_dc": sum(c.count * c.dc_width for c in table), "semantic": sum(c.count * c.sem_width for c in table)}
+    if sum(c.count for c in table) != N or any(T[k].numel() != n for k, n in want.items()) or T["features_rest"].shape[0] != N:
+        raise ValueError("densify_scene: the flat tensors do not have the sizes flat.meta describes")
+    n_split = int(table[0].params.n_split)
+    stream = _native.stream(dev)
+    with torch.cuda.device(dev):
+        table_dev = _pinned_to(np.frombuffer(table, dtype=np.uint8), dev)
+        segs = (table, ptr(table_dev))
+        work = torch.empty(L.sgr_densify_scene_work_bytes(N, K), dtype=torch.uint8, device=dev)
+        totals = (C.c_int64 * (4 * K))()
+        check(L.sgr_densify_scene_plan(N, K, *segs, ptr(acc), ptr(den), ptr(T["scaling"]), ptr(T["opacity"]), ptr(work),
+                                       totals, stream))                                                   # host wait 1
+        lay = scene_layout(table, K, totals)
+        n_cand, n_norm = int(lay["cand_base"][-1]), int(lay["normals_base"][-1])
+        zs, zb = _scene_normals(lay, normals, box_normals, normal_source, dev)
+        src = torch.empty(n_cand, dtype=torch.int32, device=dev)
+        kind = torch.empty(n_cand, dtype=torch.uint8, device=dev)
+        srow = torch.empty(n_cand, dtype=torch.int32, device=dev)
+        check(L.sgr_densify_scene_map(N, K, *segs, ptr(work), ptr(src), ptr(kind), ptr(srow), stream))
+        # the candidates' geometry: gathered rows, split children computed (the per-model kernels: src holds flat rows)
+        cand = {k: _gather(L, T[k], src, kind, n_cand, False, stream, N) for k in ("xyz", "scaling", "rotation", "opacity")}
+        if n_norm:
+            check(L.sgr_densify_split_children(n_cand, n_split, ptr(src), ptr(kind), ptr(srow), ptr(T["xyz"]), ptr(T["scaling"]),
+                                               ptr(T["rotation"]), ptr(zs), ptr(cand["xyz"]), ptr(cand["scaling"]), stream))
+        sel = torch.empty(n_cand, dtype=torch.int32, device=dev)
+        src_f = torch.empty(n_cand, dtype=torch.int32, device=dev)
+        kind_f = torch.empty(n_cand, dtype=torch.uint8, device=dev)
+        cand_work = torch.empty(L.sgr_densify_scene_work_bytes(n_cand, K), dtype=torch.uint8, device=dev)
+        pc = (C.c_int64 * (5 * K))()
+        check(L.sgr_densify_scene_prune(n_cand, K, *segs, ptr(cand["xyz"]), ptr(cand["scaling"]), ptr(cand["rotation"]),
+                                        ptr(cand["opacity"]), ptr(zb) if zb.numel() else None, ptr(src), ptr(kind), ptr(work),
+                                        ptr(cand_work), ptr(sel), ptr(src_f), ptr(kind_f), pc, stream))        # host wait 2
+        pc = np.array(pc[:], dtype=np.int64).reshape(K, 5)
+        new_counts = [int(v) for v in pc[:, 4]]
+        n_out = sum(new_counts)
+        sel, src_f, kind_f = sel[:n_out], src_f[:n_out], kind_f[:n_out]
+        nc = (C.c_int64 * K)(*new_counts)
+
+        def ragged(t, which, zero_new):
+            width = "sem_width" if which else "dc_width"
+            out = _alloc.empty((sum(n * getattr(table[s], width) for s, n in enumerate(new_counts)),), torch.float32, dev)
+            check(L.sgr_densify_scene_gather_ragged(K, *segs, nc, ptr(work), which, ptr(t), ptr(src_f), ptr(kind_f),
+                                                    int(zero_new), ptr(out), stream))
+            return out
+
+        def final(k, t, zero_new):
+            if k in ("features_dc", "semantic"):
+                return ragged(t, int(k == "semantic"), zero_new)
+            if k in cand and not zero_new:  # rows of the candidate arrays as they are (split children are computed rows)
+                return _gather(L, cand[k], sel, kind_f, n_out, False, stream, n_cand)
+            return _gather(L, t, src_f, kind_f, n_out, zero_new, stream, N)
+
+        new_tensors = {k: final(k, T[k], False).requires_grad_(flat.tensors[k].requires_grad) for k in _FLAT_ATTRS}
+        new_moments = None
+        if moments is not None:
+            new_moments = tuple({k: final(k, f32(d[k]).view(T[k].shape), True) for k in _FLAT_ATTRS} for d in moments)
+    new_flat = FlatScene([dict(m, count=n) for m, n in zip(flat.meta, new_counts)], new_tensors, flat.poses)
+    tot = np.array(totals[:], dtype=np.int64).reshape(K, 4)
+    scalars = []
+    for s in range(K):
+        d = {"points_total": int(table[s].count), "points_clone": int(tot[s, 1]), "points_split": int(tot[s, 2]),
+             "points_pruned": int(pc[s, 3])}
+        if table[s].variant == _VARIANTS["bkgd"]:
+            d["points_below_min_opacity"] = int(pc[s, 0])
+            if table[s].params.prune_big:
+                d["points_big_ws"] = int(pc[s, 1])
+        scalars.append(d)
+    return new_flat, new_moments, scalars, {"src": src_f, "kind": kind_f, "counts": new_counts}
 
 
 def reset_opacity(opacity: torch.Tensor, state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:

@@ -341,3 +341,21 @@ class SegmentedAdam:
                             dst[ATTR[g]].reshape(-1)[off:off + cnt].copy_(t.detach().reshape(-1))
         self.flat, self.exp_avg, self.exp_avg_sq = new_flat, ea, eas
         self._relayout()
+
+    def rebuild_flat(self, new_flat, new_moments) -> None:
+        """Adopts ``densify.densify_scene``'s results without a copy: ``new_moments`` = ``(exp_avg, exp_avg_sq)``, dicts
+        keyed by flat attribute and shaped like ``new_flat``'s leaves, become this optimiser's moments.  Learning rates and
+        step counts carry over per segment, as ``rebuild`` keeps them."""
+        if len(new_flat.meta) != len(self.layout):
+            raise ValueError(f"rebuild_flat: {len(self.layout)} segments before, {len(new_flat.meta)} after")
+        self._check_flat(new_flat)
+        if len(new_moments) != 2:
+            raise ValueError("rebuild_flat: new_moments = (exp_avg, exp_avg_sq)")
+        for d in new_moments:
+            for a, t in new_flat.tensors.items():
+                m = d.get(a)
+                if m is None or m.shape != t.shape or m.dtype != torch.float32 or m.device != t.device or not m.is_contiguous():
+                    raise ValueError(f"rebuild_flat: the moments of {a} must be a contiguous float32 tensor shaped like the leaf")
+        self.flat = new_flat
+        self.exp_avg, self.exp_avg_sq = ({a: d[a] for a in new_flat.tensors} for d in new_moments)
+        self._relayout()
