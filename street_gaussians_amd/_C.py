@@ -11,7 +11,7 @@ import torch
 
 from . import _native
 from . import _alloc
-from ._native import SgrError, SgrLazyError, check
+from ._native import SgrError, SgrLazyError, call, check, ptr, require_hip
 # _native.py's shared helpers under the names this module has exported all along: callers drive the ctypes path through
 # _C._Grow and _C._stream (tests/test_gpu_tile_sort.py)
 from ._native import Grow as _Grow, stream as _stream
@@ -88,21 +88,70 @@ MAX_STAT_SEGMENTS = 128  # SGR_MAX_STAT_SEGMENTS
 
 
 def _dev_check(t: torch.Tensor, name: str):
-    if not t.is_cuda:
-        raise SgrError(f"{name} must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path")
+    require_hip(f"{name} must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path", t)
     if t.dtype != torch.float32 and t.dtype != torch.int32 and t.dtype != torch.uint8 and t.dtype != torch.bool:
         raise SgrError(f"{name} has unsupported dtype {t.dtype}")
 
 
-def _fptr(t, name="tensor"):
-    """device pointer of a float tensor; empty tensor -> NULL ("feature absent")."""
-    if t is None or t.numel() == 0:
-        return None, None
-    _dev_check(t, name)
-    if t.dtype != torch.float32:
-        raise SgrError(f"{name} must be float32")
-    t = t.contiguous()
-    return t, C.c_void_p(t.data_ptr())
+def _means3D_check(means3D):
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    _dev_check(means3D, "means3D")
+
+
+def _addr(t):
+    """device address of a buffer or an output as it is; None or an empty tensor -> NULL."""
+    return ptr(t) if t is not None and t.numel() else None
+
+
+class _Inputs:
+    """The float tensors one native call reads: ``p(t, name)`` is the device address of ``t`` made contiguous -- None or an
+    empty tensor -> NULL ("feature absent"), anything but float32 on the GPU an SgrError naming it -- and the
+    object keeps what it made alive until the caller drops it, after the call."""
+
+    def __init__(self):
+        self.keep = []
+
+    def __call__(self, t, name):
+        if t is None or t.numel() == 0:
+            return None
+        _dev_check(t, name)
+        if t.dtype != torch.float32:
+            raise SgrError(f"{name} must be float32")
+        t = t.contiguous()
+        self.keep.append(t)
+        return ptr(t)
+
+
+def _forward(entry, alloc, tail, background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
+             cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+             prefiltered, debug):
+    """The forward of sgr_forward_ex and sgr_forward_layers (``entry``): sizes, outputs, the three growable buffers and the
+    one argument list.  ``alloc(shape, device)`` makes a float32 output image; ``tail(image, p)`` -- ``image(*shape)`` an
+    output image, ``p`` the call's _Inputs -- returns the entry point's trailing structure (None -> NULL) and the outputs
+    it holds, made once the common outputs exist.  Returns rasterize_gaussians' nine values followed by those outputs."""
+    dev = means3D.device
+    P, H, W = means3D.size(0), int(image_height), int(image_width)
+    S = semantics.size(1) if semantics is not None and semantics.ndimension() == 2 else 0
+    M = sh.size(1) if sh is not None and sh.numel() != 0 and sh.size(0) != 0 else 0
+    with torch.cuda.device(dev):
+        image = lambda *shape: alloc(shape, dev)
+        out_color, out_depth, out_alpha = image(NUM_CHANNELS, H, W), image(1, H, W), image(1, H, W)
+        out_semantic = image(S, H, W)
+        p = _Inputs()
+        extras, more = tail(image, p)
+        # the preprocess kernel writes every element (0 for culled Gaussians): no zero fill (rasterize_points.cu:74)
+        radii = (torch.empty if P else torch.zeros)((P,), dtype=torch.int32, device=dev)
+        geom, binning, img = _Grow(dev), _Grow(dev), _Grow(dev)
+        rendered = check(getattr(_native.lib(), entry)(
+            geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, S, p(background, "bg"), W, H,
+            p(means3D, "means3D"), p(sh, "sh"), p(colors, "colors_precomp"), p(semantics, "semantics"),
+            p(opacity, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
+            p(cov3D_precomp, "cov3D_precomp"), p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"),
+            p(campos, "campos"), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color), ptr(out_depth),
+            ptr(out_alpha), ptr(out_semantic) if S else None, ptr(radii) if P else None, int(bool(debug)), _stream(dev),
+            C.byref(extras) if extras is not None else None))
+    return (rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom.tensor, binning.tensor, img.tensor) + more
 
 
 def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
@@ -110,9 +159,7 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
                         degree, campos, prefiltered, debug, color_jacobian=False):
     """RasterizeGaussiansCUDA (rasterize_points.cu:35-124).  color_jacobian (extension): a backward will follow -- the
     preprocess also stores the SH colour Jacobian for it (sgr_forward_extras.color_jacobian); same outputs."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    _dev_check(means3D, "means3D")
+    _means3D_check(means3D)
     ext = _pybind()
     if ext is not None:
         e = torch.Tensor([])
@@ -121,35 +168,11 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
                          z(rotations), float(scale_modifier), z(cov3D_precomp), z(viewmatrix), z(projmatrix),
                          float(tan_fovx), float(tan_fovy), int(image_height), int(image_width), z(sh), int(degree),
                          z(campos), bool(prefiltered), bool(debug), *((True,) if color_jacobian else ()))
-    dev = means3D.device
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    S = semantics.size(1) if semantics is not None and semantics.ndimension() == 2 else 0
-    M = sh.size(1) if sh is not None and sh.numel() != 0 and sh.size(0) != 0 else 0
-    with torch.cuda.device(dev):
-        fopt = dict(dtype=torch.float32, device=dev)
-        out_color = torch.empty((NUM_CHANNELS, H, W), **fopt)
-        out_depth = torch.empty((1, H, W), **fopt)
-        out_alpha = torch.empty((1, H, W), **fopt)
-        out_semantic = torch.empty((S, H, W), **fopt)
-        # the preprocess kernel writes every element (0 for culled Gaussians): no zero fill (rasterize_points.cu:74)
-        radii = (torch.empty if P else torch.zeros)((P,), dtype=torch.int32, device=dev)
-        geom, binning, img = _Grow(dev), _Grow(dev), _Grow(dev)
-        keep = []
-        def p(t, n):
-            t, ptr = _fptr(t, n)
-            keep.append(t)
-            return ptr
-        fx = _ForwardExtras(1) if color_jacobian else None
-        rendered = check(_native.lib().sgr_forward_ex(
-            geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, S, p(background, "bg"), W, H,
-            p(means3D, "means3D"), p(sh, "sh"), p(colors, "colors_precomp"), p(semantics, "semantics"),
-            p(opacity, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
-            p(cov3D_precomp, "cov3D_precomp"), p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"),
-            p(campos, "campos"), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-            C.c_void_p(out_color.data_ptr()), C.c_void_p(out_depth.data_ptr()), C.c_void_p(out_alpha.data_ptr()),
-            C.c_void_p(out_semantic.data_ptr()) if S else None, C.c_void_p(radii.data_ptr()) if P else None,
-            int(bool(debug)), _stream(dev), C.byref(fx) if fx is not None else None))
-    return rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom.tensor, binning.tensor, img.tensor
+    return _forward("sgr_forward_ex", lambda shape, dev: torch.empty(shape, dtype=torch.float32, device=dev),
+                    lambda image, p: (_ForwardExtras(1) if color_jacobian else None, ()),
+                    background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                    viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                    debug)
 
 
 class _LayerImages(C.Structure):  # sgr_layer_images (include/sgr_layers.h)
@@ -164,39 +187,18 @@ def rasterize_gaussians_layers(background, means3D, colors, semantics, opacity, 
     [0, split) and [split, P), each blended alone over ``layer_background`` -- one more launch on the same tile lists.
     Returns rasterize_gaussians' nine values followed by (color0 [3, H, W], alpha0 [1, H, W], color1, alpha1).
     Inference only; ctypes only (an entry point beyond the reference's API)."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    _dev_check(means3D, "means3D")
-    dev = means3D.device
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    S = semantics.size(1) if semantics is not None and semantics.ndimension() == 2 else 0
-    M = sh.size(1) if sh is not None and sh.numel() != 0 and sh.size(0) != 0 else 0
-    with torch.cuda.device(dev):
-        mk = lambda *shape: _alloc.empty(shape, torch.float32, dev)
-        out_color, out_depth, out_alpha, out_semantic = mk(NUM_CHANNELS, H, W), mk(1, H, W), mk(1, H, W), mk(S, H, W)
-        layer = [mk(NUM_CHANNELS, H, W), mk(1, H, W), mk(NUM_CHANNELS, H, W), mk(1, H, W)]
-        radii = (torch.empty if P else torch.zeros)((P,), dtype=torch.int32, device=dev)
-        geom, binning, img = _Grow(dev), _Grow(dev), _Grow(dev)
-        keep = []
-        def p(t, n):
-            t, ptr = _fptr(t, n)
-            keep.append(t)
-            return ptr
-        lbg = p(layer_background, "layer_background")
-        li = _LayerImages(int(split), lbg, 1 if clamp else 0,
-                          (C.c_void_p * 2)(layer[0].data_ptr(), layer[2].data_ptr()),
-                          (C.c_void_p * 2)(layer[1].data_ptr(), layer[3].data_ptr()))
-        rendered = check(_native.lib().sgr_forward_layers(
-            geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, S, p(background, "bg"), W, H,
-            p(means3D, "means3D"), p(sh, "sh"), p(colors, "colors_precomp"), p(semantics, "semantics"),
-            p(opacity, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
-            p(cov3D_precomp, "cov3D_precomp"), p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"),
-            p(campos, "campos"), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-            C.c_void_p(out_color.data_ptr()), C.c_void_p(out_depth.data_ptr()), C.c_void_p(out_alpha.data_ptr()),
-            C.c_void_p(out_semantic.data_ptr()) if S else None, C.c_void_p(radii.data_ptr()) if P else None,
-            int(bool(debug)), _stream(dev), C.byref(li)))
-    return (rendered, out_color, out_depth, out_alpha, out_semantic, radii, geom.tensor, binning.tensor, img.tensor,
-            layer[0], layer[1], layer[2], layer[3])
+    _means3D_check(means3D)
+    H, W = int(image_height), int(image_width)
+
+    def tail(image, p):
+        layer = (image(NUM_CHANNELS, H, W), image(1, H, W), image(NUM_CHANNELS, H, W), image(1, H, W))
+        return _LayerImages(int(split), p(layer_background, "layer_background"), 1 if clamp else 0,
+                            (C.c_void_p * 2)(layer[0].data_ptr(), layer[2].data_ptr()),
+                            (C.c_void_p * 2)(layer[1].data_ptr(), layer[3].data_ptr())), layer
+    return _forward("sgr_forward_layers", lambda shape, dev: _alloc.empty(shape, torch.float32, dev), tail,
+                    background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                    viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                    debug)
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -260,12 +262,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
                     dL_dsemantic)
         scratch = _Grow(dev)
-        keep = []
-        def p(t, n):
-            t, ptr = _fptr(t, n)
-            keep.append(t)
-            return ptr
-        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        p = _Inputs()
         extras = None
         if stats is not None:
             acc, den, mr = stats[:3]
@@ -285,7 +282,6 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                     if d0 < 0 or cnt < 0 or d0 + cnt > rows:
                         raise SgrError("statistics segment outside the persistent tensors")
                     seg_arr[k] = _StatSegment(int(s0), int(cnt), int(d0))
-                keep.append(seg_arr)
             extras = _BackwardExtras(acc.data_ptr(), den.data_ptr(), mr.data_ptr(), seg_arr, nseg, None, int(rows), None, 0, 0)
         if color_event is not None or masked_color_out is not None or skip_sh_grad or skip_cov3d_grad:
             if extras is None:
@@ -296,7 +292,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 m = masked_color_out
                 if not (m.is_cuda and m.dtype == torch.float32 and m.is_contiguous() and m.numel() == 3 * P):
                     raise SgrError("masked_color_out must be a contiguous float32 HIP tensor of 3 * P elements")
-                extras.masked_color_out = C.c_void_p(m.data_ptr())
+                extras.masked_color_out = ptr(m)
             extras.skip_sh_grad = 1 if skip_sh_grad else 0
             extras.skip_cov3d_grad = 1 if skip_cov3d_grad else 0
         check(_native.lib().sgr_backward_ex(
@@ -304,10 +300,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             p(colors, "colors_precomp"), p(semantics, "semantics"), p(alphas, "alpha"), p(scales, "scales"),
             float(scale_modifier), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"),
             p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"), p(campos, "campos"), float(tan_fovx),
-            float(tan_fovy), vp(radii.contiguous()), vp(geomBuffer), vp(binningBuffer), vp(imageBuffer),
+            float(tan_fovy), _addr(radii.contiguous()), _addr(geomBuffer), _addr(binningBuffer), _addr(imageBuffer),
             p(dL_dout_color, "dL_dout_color"), p(dL_dout_depth, "dL_dout_depth"), p(dL_dout_alpha, "dL_dout_alpha"),
-            p(dL_dout_semantic, "dL_dout_semantic"), vp(dL_dmeans2D), vp(dL_dopacity), vp(dL_dcolors), vp(dL_dmeans3D),
-            vp(dL_dcov3D), vp(dL_dsh), vp(dL_dscales), vp(dL_drotations), vp(dL_dsemantic), scratch.cb, None,
+            p(dL_dout_semantic, "dL_dout_semantic"), _addr(dL_dmeans2D), _addr(dL_dopacity), _addr(dL_dcolors), _addr(dL_dmeans3D),
+            _addr(dL_dcov3D), _addr(dL_dsh), _addr(dL_dscales), _addr(dL_drotations), _addr(dL_dsemantic), scratch.cb, None,
             int(bool(debug)), _stream(dev), C.byref(extras) if extras is not None else None))
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
             dL_dsemantic)
@@ -323,20 +319,14 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     P = means3D.size(0)
     present = torch.zeros((P,), dtype=torch.bool, device=dev)
     if P:
-        with torch.cuda.device(dev):
-            m, v, pr = means3D.contiguous(), viewmatrix.contiguous(), projmatrix.contiguous()
-            check(_native.lib().sgr_mark_visible(P, C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()),
-                                                 C.c_void_p(pr.data_ptr()), C.c_void_p(present.data_ptr()),
-                                                 _stream(dev)))
+        call("sgr_mark_visible", dev, P, means3D.contiguous(), viewmatrix.contiguous(), projmatrix.contiguous(), present)
     return present
 
 
 def rasterize_gaussians_filter(means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
                                tan_fovx, tan_fovy, image_height, image_width, prefiltered, debug):
     """RasterizeGaussiansfilterCUDA (rasterize_points.cu:243-307)."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    _dev_check(means3D, "means3D")
+    _means3D_check(means3D)
     ext = _pybind()
     if ext is not None:
         e = torch.Tensor([])
@@ -349,18 +339,11 @@ def rasterize_gaussians_filter(means3D, scales, rotations, scale_modifier, cov3D
     radii = torch.zeros((P,), dtype=torch.int32, device=dev)
     means2D = torch.zeros((P, 2), dtype=torch.float32, device=dev)
     if P:
-        with torch.cuda.device(dev):
-            keep = []
-            def p(t, n):
-                t, ptr = _fptr(t, n)
-                keep.append(t)
-                return ptr
-            check(_native.lib().sgr_visible_filter(
-                P, int(image_width), int(image_height), p(means3D, "means3D"), p(scales, "scales"),
-                float(scale_modifier), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"),
-                p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"), float(tan_fovx), float(tan_fovy),
-                int(bool(prefiltered)), C.c_void_p(radii.data_ptr()), C.c_void_p(means2D.data_ptr()),
-                int(bool(debug)), _stream(dev)))
+        p = _Inputs()
+        call("sgr_visible_filter", dev, P, int(image_width), int(image_height), p(means3D, "means3D"), p(scales, "scales"),
+             float(scale_modifier), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"),
+             p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"), float(tan_fovx), float(tan_fovy),
+             int(bool(prefiltered)), radii, means2D, int(bool(debug)))
     return radii, means2D
 
 
@@ -374,14 +357,12 @@ def distCUDA2(points):
     P = points.size(0)
     means = torch.zeros((P,), dtype=torch.float32, device=dev)
     if P:
-        with torch.cuda.device(dev):
-            pts = points.contiguous()
-            if pts.dtype != torch.float32:
-                raise SgrError("points must be float32")
-            scratch = _Grow(dev)
-            check(_native.lib().sgr_knn(P, C.c_void_p(pts.data_ptr()), C.c_void_p(means.data_ptr()), scratch.cb, None,
-                                        _stream(dev)))
-            torch.cuda.current_stream(dev).synchronize()  # scratch must outlive the kernels
+        pts = points.contiguous()
+        if pts.dtype != torch.float32:
+            raise SgrError("points must be float32")
+        scratch = _Grow(dev)
+        call("sgr_knn", dev, P, pts, means, scratch.cb, None)
+        torch.cuda.current_stream(dev).synchronize()  # scratch must outlive the kernels
     return means
 
 
@@ -403,10 +384,7 @@ def masked_color_grad(geomBuffer, grad_colors, P):
     _dev_check(grad_colors, "grad_colors")
     dev = grad_colors.device
     out = torch.empty((int(P), 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(_native.lib().sgr_masked_color_grad(int(P), C.c_void_p(geomBuffer.data_ptr()),
-                                                  C.c_void_p(grad_colors.contiguous().data_ptr()),
-                                                  C.c_void_p(out.data_ptr()), _stream(dev)))
+    call("sgr_masked_color_grad", dev, int(P), geomBuffer, grad_colors.contiguous(), out)
     return out
 
 
@@ -421,10 +399,7 @@ def sh_grad_from_views(means3D, campos, drgb, degree, M):
     out = torch.empty((P, int(M), 3), dtype=torch.float32, device=dev)
     f32 = lambda t: t.detach().to(torch.float32).contiguous()
     means3D, campos, drgb = f32(means3D), f32(campos), f32(drgb)
-    with torch.cuda.device(dev):
-        check(_native.lib().sgr_sh_grad_from_views(P, int(degree), int(M), V, C.c_void_p(means3D.data_ptr()),
-                                                   C.c_void_p(campos.data_ptr()), C.c_void_p(drgb.data_ptr()),
-                                                   C.c_void_p(out.data_ptr()), _stream(dev)))
+    call("sgr_sh_grad_from_views", dev, P, int(degree), int(M), V, means3D, campos, drgb, out)
     return out
 
 
@@ -432,11 +407,8 @@ def sh_grad_from_rows(P, degree, M, V, means_ptr, means_stride, campos_ptr, camp
     """sgr_sh_grad_from_views_ex on raw device addresses + per-view strides (in floats): the rebuild of
     multiview.FactoredGradReducer reads its inputs straight out of the all-gathered payload rows.  -> [P, M, 3]."""
     out = torch.empty((int(P), int(M), 3), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        check(_native.lib().sgr_sh_grad_from_views_ex(int(P), int(degree), int(M), int(V), C.c_void_p(means_ptr),
-                                                      int(means_stride), C.c_void_p(campos_ptr), int(campos_stride),
-                                                      C.c_void_p(drgb_ptr), int(drgb_stride), C.c_void_p(out.data_ptr()),
-                                                      _stream(device)))
+    call("sgr_sh_grad_from_views_ex", device, int(P), int(degree), int(M), int(V), C.c_void_p(means_ptr),
+         int(means_stride), C.c_void_p(campos_ptr), int(campos_stride), C.c_void_p(drgb_ptr), int(drgb_stride), out)
     return out
 
 
@@ -509,7 +481,6 @@ def export_internal(name, P, R, image_height, image_width, geomBuffer, binningBu
     T = ((W + 15) // 16) * ((H + 15) // 16)
     dev = geomBuffer.device
     out = torch.zeros(shp(P, R, H * W, T), dtype=dtype, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     if name == "cov3D":
         if scales is None or rotations is None:
             raise SgrError("cov3D is not kept in the buffers: pass the forward's scales and rotations")
@@ -518,12 +489,9 @@ def export_internal(name, P, R, image_height, image_width, geomBuffer, binningBu
         sc, rot = scales.detach().float().contiguous(), rotations.detach().float().contiguous()
         if sc.shape != (P, 3) or rot.shape != (P, 4):
             raise RuntimeError("scales must have dimensions (num_points, 3), rotations (num_points, 4)")
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_export_cov3d(int(P), vp(sc), float(scale_modifier), vp(rot), vp(out), _stream(dev)))
-            torch.cuda.current_stream(dev).synchronize()
-        return out
-    with torch.cuda.device(dev):
-        check(_native.lib().sgr_export_internal(which, P, R, W, H, vp(geomBuffer), vp(binningBuffer), vp(imageBuffer),
-                                                vp(out), _stream(dev)))
-        torch.cuda.current_stream(dev).synchronize()
+        call("sgr_export_cov3d", dev, int(P), _addr(sc), float(scale_modifier), _addr(rot), _addr(out))
+    else:
+        call("sgr_export_internal", dev, which, P, R, W, H, _addr(geomBuffer), _addr(binningBuffer), _addr(imageBuffer),
+             _addr(out))
+    torch.cuda.current_stream(dev).synchronize()
     return out

@@ -164,6 +164,26 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def launch(name: str, stream_, *args) -> int:
+    """The stream-taking entry point ``name`` on ``stream_``: tensors go down as their device addresses (``ptr``; None stays
+    NULL), every other argument as it is, the stream is appended as the last argument and the return code goes through
+    ``check``.  Nothing is copied or converted: a tensor the kernel needs contiguous or float32 is made so by the caller.
+    For a block of launches under one device guard and one stream lookup; a single launch is ``call``."""
+    return check(getattr(lib(), name)(*[ptr(a) if isinstance(a, torch.Tensor) else a for a in args], stream_))
+
+
+def call(name: str, device, *args) -> int:
+    """One ``launch`` with ``device`` current, on its current stream."""
+    with torch.cuda.device(device):
+        return launch(name, stream(device), *args)
+
+
+def require_hip(message: str, *tensors) -> None:
+    """SgrError with the caller's ``message`` unless every tensor is a HIP (cuda) tensor: there is no CPU path."""
+    if not all(t.is_cuda for t in tensors):
+        raise SgrError(message)
+
+
 class Grow:
     """Growable byte buffer handed to the C side (resizeFunctional, rasterize_points.cu:27-33).
 

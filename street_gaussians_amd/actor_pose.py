@@ -17,8 +17,7 @@ from typing import Dict, Hashable, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _native
-from ._native import SgrError, check, ptr, stream
+from ._native import call, require_hip
 
 CONTRIB, PARTS = 16, 23  # include/sgr_actor_pose.h SGR_ACTOR_POSE_CONTRIB / _PARTS
 
@@ -94,10 +93,8 @@ class _Poses(torch.autograd.Function):
         d_trans = torch.empty_like(opt_trans, memory_format=torch.contiguous_format)
         d_rots = torch.empty_like(opt_rots, memory_format=torch.contiguous_format)
         contrib = torch.empty(K * CONTRIB, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_actor_pose_backward(
-                K, ptr(ctx.recs), o.n_cells, ptr(o.input_trans), ptr(o.input_rots), ptr(opt_trans), ptr(opt_rots),
-                ptr(ctx.ego), ptr(g), ptr(contrib), ptr(d_trans), ptr(d_rots), stream(dev)))
+        call("sgr_actor_pose_backward", dev, K, ctx.recs, o.n_cells, o.input_trans, o.input_rots, opt_trans, opt_rots,
+             ctx.ego, g, contrib, d_trans, d_rots)
         return d_trans, d_rots, None, None, None, None
 
 
@@ -204,15 +201,13 @@ class ActorPoses:
         dev = self.input_trans.device
         out = torch.empty(K, 7, dtype=torch.float32, device=dev)
         pt = torch.empty(K, PARTS, dtype=torch.float32, device=dev) if parts else None
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_actor_pose_forward(K, ptr(recs), self.n_cells, ptr(self.input_trans), ptr(self.input_rots),
-                                                       ptr(opt_trans), ptr(opt_rots), ptr(ego), ptr(out), ptr(pt), stream(dev)))
+        call("sgr_actor_pose_forward", dev, K, recs, self.n_cells, self.input_trans, self.input_rots, opt_trans, opt_rots,
+             ego, out, pt)
         return out, pt
 
     def _check_device(self, ego_pose):
         ts = [self.input_trans, self.input_rots, ego_pose] + ([self.opt_trans, self.opt_rots] if self.opt_track else [])
-        if not all(t.is_cuda for t in ts):
-            raise SgrError("ActorPoses.poses: every tensor must be a HIP (cuda) tensor: there is no CPU path")
+        require_hip("ActorPoses.poses: every tensor must be a HIP (cuda) tensor: there is no CPU path", *ts)
         if any(t.device != ts[0].device for t in ts):
             raise ValueError("ActorPoses.poses: every tensor must be on the same device")
 

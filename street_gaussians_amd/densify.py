@@ -23,13 +23,14 @@ calling ``densify_and_prune`` per model and concatenating."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _alloc, _native
-from ._native import SgrError, check, ptr
+from ._native import SgrError, call, check, ptr, require_hip
 
 PARAMS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "semantic")  # optimiser group names (:409-412)
 
@@ -107,149 +108,171 @@ def densify_and_prune(params: Dict[str, torch.Tensor], xyz_gradient_accum: torch
     identical across ranks (multiview.ReplicatedNormals)."""
     if variant not in _VARIANTS:
         raise ValueError(f"unknown variant {variant!r}")
-    if _VARIANTS[variant] != 0:
-        return _densify_two_step(params, xyz_gradient_accum, denom, max_grad=max_grad, min_opacity=min_opacity,
-                                 extent=extent, percent_dense=percent_dense, percent_big_ws=percent_big_ws,
-                                 prune_big=prune_big, states=states, grad_column=grad_column, n_split=n_split,
-                                 normals=normals, variant=variant, sphere_center=sphere_center,
-                                 sphere_radius=sphere_radius, box_min=box_min, box_max=box_max, box_normals=box_normals,
-                                 normal_source=normal_source)
-    xyz = params["xyz"]
-    if not xyz.is_cuda:
-        raise SgrError("densify_and_prune needs HIP (cuda) tensors: there is no CPU path")
-    dev, N = xyz.device, xyz.shape[0]
-    L = _native.lib()
-    f32 = lambda t: t.detach().to(torch.float32).contiguous()
-    cp = _CParams(float(max_grad), float(min_opacity), float(extent), float(percent_dense), float(percent_big_ws),
-                  int(bool(prune_big)), int(grad_column), int(n_split), 0)
-    counts = (C.c_int64 * 6)()
-    work = torch.empty(L.sgr_densify_work_bytes(N), dtype=torch.uint8, device=dev)
-    stream = _native.stream(dev)
-    acc, den, sc, op = f32(xyz_gradient_accum), f32(denom), f32(params["scaling"]), f32(params["opacity"])
+    require_hip("densify_and_prune needs HIP (cuda) tensors: there is no CPU path", params["xyz"])
+    dev = params["xyz"].device
+    rule = dict(max_grad=max_grad, min_opacity=min_opacity, extent=extent, percent_dense=percent_dense,
+                percent_big_ws=percent_big_ws, prune_big=prune_big, grad_column=grad_column, n_split=n_split)
+    # one guard, one library and stream lookup and hand-written launches for the ~30 launches of a call: _native.call per
+    # launch costs 1-2 us each, which shows in a loop over many small models (profiles/bindings_refactor/bench.json)
     with torch.cuda.device(dev):
-        check(L.sgr_densify_plan(N, C.byref(cp), ptr(acc), ptr(den), ptr(sc), ptr(op), ptr(work), counts, stream))
-        n_out, n_norm = int(counts[4]), int(counts[5])
-        src = torch.empty(n_out, dtype=torch.int32, device=dev)
-        kind = torch.empty(n_out, dtype=torch.uint8, device=dev)
-        srow = torch.empty(n_out, dtype=torch.int32, device=dev)
-        check(L.sgr_densify_map(N, C.byref(cp), ptr(work), ptr(src), ptr(kind), ptr(srow), stream))
-
-        def gather(t, zero_new):
-            t = f32(t)
-            width = t[0].numel() if N else 0
-            out = _alloc.empty((n_out,) + tuple(t.shape[1:]), torch.float32, dev)  # ladder-sized backing: see _alloc.py
-            check(L.sgr_densify_gather(n_out, width, ptr(t), ptr(src), ptr(kind), int(zero_new), ptr(out), stream))
-            return out
-
-        new_params = {k: gather(params[k], False) for k in PARAMS if k in params}
-        if n_norm:
-            if normals is None:
-                normals = normal_source(n_norm, dev) if normal_source is not None else torch.randn(n_norm, 3, device=dev)
-            if tuple(normals.shape) != (n_norm, 3):
-                raise RuntimeError(f"normals must have dimensions ({n_norm}, 3)")
-            check(L.sgr_densify_split_children(n_out, int(n_split), ptr(src), ptr(kind), ptr(srow), ptr(f32(params["xyz"])),
-                                               ptr(sc), ptr(f32(params["rotation"])), ptr(f32(normals)), ptr(new_params["xyz"]),
-                                               ptr(new_params["scaling"]), stream))
+        on = (_native.lib(), _native.stream(dev))
+        if _VARIANTS[variant] != 0:
+            return _densify_two_step(on, params, xyz_gradient_accum, denom, states=states, normals=normals,
+                                     variant=variant, sphere_center=sphere_center, sphere_radius=sphere_radius,
+                                     box_min=box_min, box_max=box_max, box_normals=box_normals,
+                                     normal_source=normal_source, **rule)
+        cp, counts, src, kind, srow, new_params = _candidates(on, params, xyz_gradient_accum, denom,
+                                                              [k for k in PARAMS if k in params], False, normals,
+                                                              normal_source, **rule)
+        N, n_out = params["xyz"].shape[0], src.numel()
         new_states = None
         if states is not None:
-            new_states = {k: (gather(a, True), gather(b, True)) for k, (a, b) in states.items()}
-    scalars = {"points_total": int(counts[0]), "points_clone": int(counts[1]), "points_split": int(counts[2]),
-               "points_pruned": int(counts[3])}
-    return new_params, new_states, scalars, {"src": src, "kind": kind}
+            new_states = {k: (_gather(on, a, src, kind, n_out, True, N), _gather(on, b, src, kind, n_out, True, N))
+                          for k, (a, b) in states.items()}
+    return new_params, new_states, _scalars(counts[0], counts[1], counts[2], counts[3]), {"src": src, "kind": kind}
 
 
-def _gather(L, t, src, kind, n_out, zero_new, stream, N):
-    t = t.detach().to(torch.float32).contiguous()
+def _f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _gather(on, t, src, kind, n_out, zero_new, N):
+    t = _f32(t)
     width = t[0].numel() if N else 0
-    out = _alloc.empty((n_out,) + tuple(t.shape[1:]), torch.float32, t.device)
-    check(L.sgr_densify_gather(n_out, width, ptr(t), ptr(src), ptr(kind), int(zero_new), ptr(out), stream))
+    out = _alloc.empty((n_out,) + tuple(t.shape[1:]), torch.float32, t.device)  # ladder-sized backing: see _alloc.py
+    L, s = on
+    check(L.sgr_densify_gather(n_out, width, ptr(t), ptr(src), ptr(kind), int(zero_new), ptr(out), s))
     return out
 
 
-def _densify_two_step(params, xyz_gradient_accum, denom, *, max_grad, min_opacity, extent, percent_dense, percent_big_ws,
-                      prune_big, states, grad_column, n_split, normals, variant, sphere_center, sphere_radius, box_min,
-                      box_max, box_normals, normal_source=None):
+def _draw_normals(given, shape, normal_source, dev, name):
+    """Standard normals of ``shape`` ([rows, 3] or [rows, 2, 3]) as contiguous float32: the caller's tensor ``given``, else
+    the rows ``normal_source`` hands out, else ``torch.randn``'s."""
+    if given is None:
+        if normal_source is None:
+            given = torch.randn(*shape, device=dev)
+        else:
+            given = normal_source(math.prod(shape[:-1]), dev)
+            if len(shape) > 2:
+                given = given.view(shape)
+    if tuple(given.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must have dimensions {tuple(shape)}")
+    return _f32(given)
+
+
+def _gather_and_split(on, T, scaling, keys, src, kind, srow, N, n_split, n_norm, normals, normal_source=None):
+    """The candidates' rows of ``T[k]`` for k in ``keys`` (xyz and scaling among them), split children computed from
+    ``n_norm`` standard normals (``_draw_normals``).  ``scaling``: T["scaling"] as contiguous float32, which the caller has."""
+    n_cand = src.numel()
+    cand = {k: _gather(on, T[k], src, kind, n_cand, False, N) for k in keys}
+    if n_norm:
+        zs = _draw_normals(normals, (n_norm, 3), normal_source, src.device, "normals")
+        L, s = on
+        check(L.sgr_densify_split_children(n_cand, int(n_split), ptr(src), ptr(kind), ptr(srow), ptr(_f32(T["xyz"])),
+                                           ptr(scaling), ptr(_f32(T["rotation"])), ptr(zs), ptr(cand["xyz"]),
+                                           ptr(cand["scaling"]), s))
+    return cand
+
+
+def _candidates(on, params, xyz_gradient_accum, denom, keys, defer_prune, normals, normal_source, *, max_grad,
+                min_opacity, extent, percent_dense, percent_big_ws, prune_big, grad_column, n_split):
+    """The front of a per-model densify: the parameter struct, the plan (``counts``: total, clones, split points, pruned,
+    candidate rows, normals), the candidates' ``src`` / ``kind`` / ``srow`` map and their rows of ``params[k]`` for k in
+    ``keys`` with the split children computed.  ``defer_prune``: the plan prunes nothing (the two-step variants)."""
     xyz = params["xyz"]
-    if not xyz.is_cuda:
-        raise SgrError("densify_and_prune needs HIP (cuda) tensors: there is no CPU path")
     dev, N = xyz.device, xyz.shape[0]
-    L = _native.lib()
-    f32 = lambda t: t.detach().to(torch.float32).contiguous()
     cp = _CParams(float(max_grad), float(min_opacity), float(extent), float(percent_dense), float(percent_big_ws),
-                  int(bool(prune_big)), int(grad_column), int(n_split), 1)
+                  int(bool(prune_big)), int(grad_column), int(n_split), int(defer_prune))
     counts = (C.c_int64 * 6)()
-    stream = _native.stream(dev)
-    acc, den, sc, op = f32(xyz_gradient_accum), f32(denom), f32(params["scaling"]), f32(params["opacity"])
-    with torch.cuda.device(dev):
-        work = torch.empty(L.sgr_densify_work_bytes(N), dtype=torch.uint8, device=dev)
-        check(L.sgr_densify_plan(N, C.byref(cp), ptr(acc), ptr(den), ptr(sc), ptr(op), ptr(work), counts, stream))
-        n_cand, n_norm = int(counts[4]), int(counts[5])
-        src = torch.empty(n_cand, dtype=torch.int32, device=dev)
-        kind = torch.empty(n_cand, dtype=torch.uint8, device=dev)
-        srow = torch.empty(n_cand, dtype=torch.int32, device=dev)
-        check(L.sgr_densify_map(N, C.byref(cp), ptr(work), ptr(src), ptr(kind), ptr(srow), stream))
-        # the candidates' geometry: gathered rows, split children computed
-        cand = {k: _gather(L, params[k], src, kind, n_cand, False, stream, N) for k in ("xyz", "scaling", "rotation", "opacity")}
-        if n_norm:
-            if normals is None:
-                normals = normal_source(n_norm, dev) if normal_source is not None else torch.randn(n_norm, 3, device=dev)
-            if tuple(normals.shape) != (n_norm, 3):
-                raise RuntimeError(f"normals must have dimensions ({n_norm}, 3)")
-            check(L.sgr_densify_split_children(n_cand, int(n_split), ptr(src), ptr(kind), ptr(srow), ptr(f32(params["xyz"])),
-                                               ptr(sc), ptr(f32(params["rotation"])), ptr(f32(normals)), ptr(cand["xyz"]),
-                                               ptr(cand["scaling"]), stream))
-        sphere = box = None
-        if variant == "bkgd":
-            if sphere_center is None or sphere_radius is None:
-                raise ValueError('variant "bkgd" needs sphere_center and sphere_radius')
-            c = [float(v) for v in torch.as_tensor(sphere_center).flatten().tolist()]
-            sphere = (C.c_float * 4)(c[0], c[1], c[2], float(torch.as_tensor(sphere_radius).flatten()[0]))
-        if variant == "actor" and prune_big:
-            if box_min is None or box_max is None:
-                raise ValueError('variant "actor" needs box_min and box_max')
-            lo = [float(v) for v in torch.as_tensor(box_min).flatten().tolist()]
-            hi = [float(v) for v in torch.as_tensor(box_max).flatten().tolist()]
-            box = (C.c_float * 6)(*lo, *hi)
-            if box_normals is None:
-                box_normals = (normal_source(n_cand * 2, dev).view(n_cand, 2, 3) if normal_source is not None
-                               else torch.randn(n_cand, 2, 3, device=dev))
-            if tuple(box_normals.shape) != (n_cand, 2, 3):
-                raise RuntimeError(f"box_normals must have dimensions ({n_cand}, 2, 3)")
-            box_normals = f32(box_normals)
-        prune = torch.empty(n_cand, dtype=torch.uint8, device=dev)
-        pc = (C.c_int64 * 4)()
-        check(L.sgr_densify_prune_mask(n_cand, C.byref(cp), _VARIANTS[variant], ptr(cand["xyz"]), ptr(cand["scaling"]),
-                                       ptr(cand["rotation"]), ptr(cand["opacity"]), sphere, box,
-                                       ptr(box_normals) if box is not None else None, ptr(prune), pc, stream))
-        sel = torch.empty(n_cand, dtype=torch.int32, device=dev)
-        n_out = C.c_int64(0)
-        work2 = torch.empty(L.sgr_densify_work_bytes(n_cand), dtype=torch.uint8, device=dev)
-        check(L.sgr_densify_compact(n_cand, ptr(prune), ptr(work2), ptr(sel), C.byref(n_out), stream))
-        n_out = int(n_out.value)
-        sel = sel[:n_out]
-        sel64 = sel.long()
-        src_f, kind_f = src[sel64].contiguous(), kind[sel64].contiguous()
-        keep0 = torch.zeros(n_out, dtype=torch.uint8, device=dev)  # rows copied from the candidate arrays as they are
-        new_params = {}
-        for k in PARAMS:
-            if k not in params:
-                continue
-            if k in cand:
-                new_params[k] = _gather(L, cand[k], sel, keep0, n_out, False, stream, n_cand)
-                if params[k].dim() != new_params[k].dim():
-                    new_params[k] = new_params[k].reshape((n_out,) + tuple(params[k].shape[1:]))
-            else:
-                new_params[k] = _gather(L, params[k], src_f, kind_f, n_out, False, stream, N)
-        new_states = None
-        if states is not None:
-            new_states = {k: (_gather(L, a, src_f, kind_f, n_out, True, stream, N), _gather(L, b, src_f, kind_f, n_out, True, stream, N))
-                          for k, (a, b) in states.items()}
-    scalars = {"points_total": int(counts[0]), "points_clone": int(counts[1]), "points_split": int(counts[2]),
-               "points_pruned": int(pc[3])}
-    if variant == "bkgd":
-        scalars["points_below_min_opacity"] = int(pc[0])
+    acc, den, sc, op = _f32(xyz_gradient_accum), _f32(denom), _f32(params["scaling"]), _f32(params["opacity"])
+    L, s = on
+    work = torch.empty(L.sgr_densify_work_bytes(N), dtype=torch.uint8, device=dev)
+    check(L.sgr_densify_plan(N, C.byref(cp), ptr(acc), ptr(den), ptr(sc), ptr(op), ptr(work), counts, s))
+    n_cand, n_norm = int(counts[4]), int(counts[5])
+    src = torch.empty(n_cand, dtype=torch.int32, device=dev)
+    kind = torch.empty(n_cand, dtype=torch.uint8, device=dev)
+    srow = torch.empty(n_cand, dtype=torch.int32, device=dev)
+    check(L.sgr_densify_map(N, C.byref(cp), ptr(work), ptr(src), ptr(kind), ptr(srow), s))
+    cand = _gather_and_split(on, params, sc, keys, src, kind, srow, N, n_split, n_norm, normals, normal_source)
+    return cp, counts, src, kind, srow, cand
+
+
+def _floats(v, n, what, strict):
+    """``v`` as a list of floats; with ``strict``, a ValueError unless it holds n values."""
+    out = [float(x) for x in torch.as_tensor(v).flatten().tolist()]
+    if strict and len(out) != n:
+        raise ValueError(f"densify_scene: {what} must hold {n} values, got {len(out)}")
+    return out
+
+
+def _regions(rule, where="", strict=False):
+    """A rule's (sphere, box) as the kernels take them -- centre + radius for the bkgd variant, min + max for the actor
+    variant with prune_big, None where the rule has none.  ValueError for a missing value and, with ``strict``, for one of
+    the wrong length; ``where`` prefixes the message."""
+    sphere = box = None
+    if rule["variant"] == "bkgd":
+        if rule["sphere_center"] is None or rule["sphere_radius"] is None:
+            raise ValueError(f'{where}variant "bkgd" needs sphere_center and sphere_radius')
+        c = _floats(rule["sphere_center"], 3, "sphere_center", strict)
+        sphere = (C.c_float * 4)(c[0], c[1], c[2], _floats(rule["sphere_radius"], 1, "sphere_radius", strict)[0])
+    if rule["variant"] == "actor" and rule["prune_big"]:
+        if rule["box_min"] is None or rule["box_max"] is None:
+            raise ValueError(f'{where}variant "actor" needs box_min and box_max')
+        box = (C.c_float * 6)(*_floats(rule["box_min"], 3, "box_min", strict), *_floats(rule["box_max"], 3, "box_max", strict))
+    return sphere, box
+
+
+def _scalars(total, clone, split, pruned, variant=0, prune_big=False, pc=None):
+    """The reference's scalar_dict of one model.  For the bkgd variant (``variant`` is its number) the extras come from the
+    prune's counters ``pc`` (below min opacity, big in world space, ...)."""
+    d = {"points_total": int(total), "points_clone": int(clone), "points_split": int(split), "points_pruned": int(pruned)}
+    if variant == _VARIANTS["bkgd"]:
+        d["points_below_min_opacity"] = int(pc[0])
         if prune_big:
-            scalars["points_big_ws"] = int(pc[1])
+            d["points_big_ws"] = int(pc[1])
+    return d
+
+
+def _densify_two_step(on, params, xyz_gradient_accum, denom, *, states, normals, variant, sphere_center, sphere_radius,
+                      box_min, box_max, box_normals, normal_source=None, **rule):
+    cp, counts, src, kind, srow, cand = _candidates(on, params, xyz_gradient_accum, denom,
+                                                    ("xyz", "scaling", "rotation", "opacity"), True, normals, normal_source,
+                                                    **rule)
+    dev, N, n_cand = src.device, params["xyz"].shape[0], src.numel()
+    sphere, box = _regions(dict(variant=variant, prune_big=rule["prune_big"], sphere_center=sphere_center,
+                                sphere_radius=sphere_radius, box_min=box_min, box_max=box_max))
+    if box is not None:
+        box_normals = _draw_normals(box_normals, (n_cand, 2, 3), normal_source, dev, "box_normals")
+    prune = torch.empty(n_cand, dtype=torch.uint8, device=dev)
+    pc = (C.c_int64 * 4)()
+    L, s = on
+    check(L.sgr_densify_prune_mask(n_cand, C.byref(cp), _VARIANTS[variant], ptr(cand["xyz"]), ptr(cand["scaling"]),
+                                   ptr(cand["rotation"]), ptr(cand["opacity"]), sphere, box,
+                                   ptr(box_normals) if box is not None else None, ptr(prune), pc, s))
+    sel = torch.empty(n_cand, dtype=torch.int32, device=dev)
+    n_out = C.c_int64(0)
+    work2 = torch.empty(L.sgr_densify_work_bytes(n_cand), dtype=torch.uint8, device=dev)
+    check(L.sgr_densify_compact(n_cand, ptr(prune), ptr(work2), ptr(sel), C.byref(n_out), s))
+    n_out = int(n_out.value)
+    sel = sel[:n_out]
+    sel64 = sel.long()
+    src_f, kind_f = src[sel64].contiguous(), kind[sel64].contiguous()
+    keep0 = torch.zeros(n_out, dtype=torch.uint8, device=dev)  # rows copied from the candidate arrays as they are
+    new_params = {}
+    for k in PARAMS:
+        if k not in params:
+            continue
+        if k in cand:
+            new_params[k] = _gather(on, cand[k], sel, keep0, n_out, False, n_cand)
+            if params[k].dim() != new_params[k].dim():
+                new_params[k] = new_params[k].reshape((n_out,) + tuple(params[k].shape[1:]))
+        else:
+            new_params[k] = _gather(on, params[k], src_f, kind_f, n_out, False, N)
+    new_states = None
+    if states is not None:
+        new_states = {k: (_gather(on, a, src_f, kind_f, n_out, True, N), _gather(on, b, src_f, kind_f, n_out, True, N))
+                      for k, (a, b) in states.items()}
+    scalars = _scalars(counts[0], counts[1], counts[2], pc[3], _VARIANTS[variant], rule["prune_big"], pc)
     return new_params, new_states, scalars, {"src": src_f, "kind": kind_f}
 
 
@@ -264,13 +287,6 @@ _RULE_REQUIRED = ("max_grad", "min_opacity", "extent", "percent_dense", "percent
 _RULE_OPTIONAL = {"grad_column": 0, "n_split": 2, "variant": None, "sphere_center": None, "sphere_radius": None,
                   "box_min": None, "box_max": None}
 _FLAT_ATTRS = ("xyz", "rotation", "scaling", "opacity", "features_dc", "features_rest", "semantic")
-
-
-def _floats(v, n, what):
-    out = [float(x) for x in torch.as_tensor(v).flatten().tolist()]
-    if len(out) != n:
-        raise ValueError(f"densify_scene: {what} must hold {n} values, got {len(out)}")
-    return out
 
 
 def scene_table(meta: Sequence[dict], rules: Sequence[dict]):
@@ -297,16 +313,9 @@ def scene_table(meta: Sequence[dict], rules: Sequence[dict]):
         c.params = _CParams(float(r["max_grad"]), float(r["min_opacity"]), float(r["extent"]), float(r["percent_dense"]),
                             float(r["percent_big_ws"]), int(bool(r["prune_big"])), int(r["grad_column"]), int(r["n_split"]), 1)
         c.variant = _VARIANTS[r["variant"]]
-        c.sphere = (C.c_float * 4)(nan, nan, nan, nan)
-        c.box = (C.c_float * 6)(*[nan] * 6)
-        if r["variant"] == "bkgd":
-            if r["sphere_center"] is None or r["sphere_radius"] is None:
-                raise ValueError(f'densify_scene: rules[{i}]: variant "bkgd" needs sphere_center and sphere_radius')
-            c.sphere = (C.c_float * 4)(*_floats(r["sphere_center"], 3, "sphere_center"), *_floats(r["sphere_radius"], 1, "sphere_radius"))
-        if r["variant"] == "actor" and r["prune_big"]:
-            if r["box_min"] is None or r["box_max"] is None:
-                raise ValueError(f'densify_scene: rules[{i}]: variant "actor" needs box_min and box_max')
-            c.box = (C.c_float * 6)(*_floats(r["box_min"], 3, "box_min"), *_floats(r["box_max"], 3, "box_max"))
+        sphere, box = _regions(r, f"densify_scene: rules[{i}]: ", strict=True)
+        c.sphere = sphere if sphere is not None else (C.c_float * 4)(nan, nan, nan, nan)
+        c.box = box if box is not None else (C.c_float * 6)(*[nan] * 6)
     return tab
 
 
@@ -335,14 +344,13 @@ def _scene_normals(lay, normals, box_normals, normal_source, dev):
     """The scene's ``normals`` [rows, 3] and ``box_normals`` [rows, 2, 3]: the caller's tensors (shape-checked), else
     filled block by block from ``normal_source`` / ``torch.randn`` in the order of ``lay['requests']``."""
     n_norm, n_box = int(lay["normals_base"][-1]), int(lay["box_base"][-1])
-    f32 = lambda t: t.detach().to(torch.float32).contiguous()
     given = {"split": normals is not None, "box": box_normals is not None}
     if given["split"] and tuple(normals.shape) != (n_norm, 3):
         raise ValueError(f"densify_scene: normals must have dimensions ({n_norm}, 3)")
     if given["box"] and tuple(box_normals.shape) != (n_box, 2, 3):
         raise ValueError(f"densify_scene: box_normals must have dimensions ({n_box}, 2, 3)")
-    out = {"split": f32(normals) if given["split"] else torch.empty(n_norm, 3, device=dev),
-           "box": f32(box_normals).view(2 * n_box, 3) if given["box"] else torch.empty(2 * n_box, 3, device=dev)}
+    out = {"split": _f32(normals) if given["split"] else torch.empty(n_norm, 3, device=dev),
+           "box": _f32(box_normals).view(2 * n_box, 3) if given["box"] else torch.empty(2 * n_box, 3, device=dev)}
     base = {"split": lay["normals_base"], "box": 2 * lay["box_base"]}
     for s, what, rows in lay["requests"]:
         if given[what]:
@@ -382,18 +390,16 @@ def densify_scene(flat, xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, r
         if len(moments) != 2 or any(set(d) != set(_FLAT_ATTRS) for d in moments):
             raise ValueError(f"densify_scene: moments = (exp_avg, exp_avg_sq), each a dict with the keys {_FLAT_ATTRS}")
     ins = [flat.tensors[k] for k in _FLAT_ATTRS] + [xyz_gradient_accum, denom] + ([t for d in moments for t in d.values()] if moments else [])
-    if not all(t.is_cuda for t in ins):
-        raise SgrError("densify_scene needs HIP (cuda) tensors: there is no CPU path")
+    require_hip("densify_scene needs HIP (cuda) tensors: there is no CPU path", *ins)
     dev, N = flat.xyz.device, int(flat.xyz.shape[0])
     L = _native.lib()
-    f32 = lambda t: t.detach().to(torch.float32).contiguous()
-    T = {k: f32(flat.tensors[k]) for k in _FLAT_ATTRS}
+    T = {k: _f32(flat.tensors[k]) for k in _FLAT_ATTRS}
     if moments is not None:
         for d in moments:
             for k in _FLAT_ATTRS:
                 if d[k].numel() != T[k].numel():
                     raise ValueError(f"densify_scene: the moments of {k} have {d[k].numel()} elements, the parameter {T[k].numel()}")
-    acc, den = f32(xyz_gradient_accum), f32(denom)
+    acc, den = _f32(xyz_gradient_accum), _f32(denom)
     if acc.numel() != 2 * N or den.numel() != N:
         raise ValueError(f"densify_scene: statistics of {den.numel()} rows for a scene of {N}")
     want = {"xyz": 3 * N, "rotation": 4 * N, "scaling": 3 * N, "opacity": N,  # the kernels index by these sizes
@@ -402,6 +408,7 @@ def densify_scene(flat, xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, r
         raise ValueError("densify_scene: the flat tensors do not have the sizes flat.meta describes")
     n_split = int(table[0].params.n_split)
     stream = _native.stream(dev)
+    on = (L, stream)  # what the per-model helpers launch on
     with torch.cuda.device(dev):
         table_dev = _pinned_to(np.frombuffer(table, dtype=np.uint8), dev)
         segs = (table, ptr(table_dev))
@@ -417,10 +424,8 @@ def densify_scene(flat, xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, r
         srow = torch.empty(n_cand, dtype=torch.int32, device=dev)
         check(L.sgr_densify_scene_map(N, K, *segs, ptr(work), ptr(src), ptr(kind), ptr(srow), stream))
         # the candidates' geometry: gathered rows, split children computed (the per-model kernels: src holds flat rows)
-        cand = {k: _gather(L, T[k], src, kind, n_cand, False, stream, N) for k in ("xyz", "scaling", "rotation", "opacity")}
-        if n_norm:
-            check(L.sgr_densify_split_children(n_cand, n_split, ptr(src), ptr(kind), ptr(srow), ptr(T["xyz"]), ptr(T["scaling"]),
-                                               ptr(T["rotation"]), ptr(zs), ptr(cand["xyz"]), ptr(cand["scaling"]), stream))
+        cand = _gather_and_split(on, T, T["scaling"], ("xyz", "scaling", "rotation", "opacity"), src, kind, srow, N, n_split,
+                                 n_norm, zs)
         sel = torch.empty(n_cand, dtype=torch.int32, device=dev)
         src_f = torch.empty(n_cand, dtype=torch.int32, device=dev)
         kind_f = torch.empty(n_cand, dtype=torch.uint8, device=dev)
@@ -446,32 +451,24 @@ def densify_scene(flat, xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, r
             if k in ("features_dc", "semantic"):
                 return ragged(t, int(k == "semantic"), zero_new)
             if k in cand and not zero_new:  # rows of the candidate arrays as they are (split children are computed rows)
-                return _gather(L, cand[k], sel, kind_f, n_out, False, stream, n_cand)
-            return _gather(L, t, src_f, kind_f, n_out, zero_new, stream, N)
+                return _gather(on, cand[k], sel, kind_f, n_out, False, n_cand)
+            return _gather(on, t, src_f, kind_f, n_out, zero_new, N)
 
         new_tensors = {k: final(k, T[k], False).requires_grad_(flat.tensors[k].requires_grad) for k in _FLAT_ATTRS}
         new_moments = None
         if moments is not None:
-            new_moments = tuple({k: final(k, f32(d[k]).view(T[k].shape), True) for k in _FLAT_ATTRS} for d in moments)
+            new_moments = tuple({k: final(k, _f32(d[k]).view(T[k].shape), True) for k in _FLAT_ATTRS} for d in moments)
     new_flat = FlatScene([dict(m, count=n) for m, n in zip(flat.meta, new_counts)], new_tensors, flat.poses)
     tot = np.array(totals[:], dtype=np.int64).reshape(K, 4)
-    scalars = []
-    for s in range(K):
-        d = {"points_total": int(table[s].count), "points_clone": int(tot[s, 1]), "points_split": int(tot[s, 2]),
-             "points_pruned": int(pc[s, 3])}
-        if table[s].variant == _VARIANTS["bkgd"]:
-            d["points_below_min_opacity"] = int(pc[s, 0])
-            if table[s].params.prune_big:
-                d["points_big_ws"] = int(pc[s, 1])
-        scalars.append(d)
+    scalars = [_scalars(c.count, tot[s, 1], tot[s, 2], pc[s, 3], c.variant, c.params.prune_big, pc[s])
+               for s, c in enumerate(table)]
     return new_flat, new_moments, scalars, {"src": src_f, "kind": kind_f, "counts": new_counts}
 
 
 def reset_opacity(opacity: torch.Tensor, state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """GaussianModel.reset_opacity (gaussian_model.py:410-414): returns inverse_sigmoid(min(sigmoid(opacity), 0.01)) as a
     new tensor; ``state`` = the group's (exp_avg, exp_avg_sq), zero-filled IN PLACE like reset_optimizer (:344-361)."""
-    if not opacity.is_cuda:
-        raise SgrError("reset_opacity needs a HIP (cuda) tensor: there is no CPU path")
+    require_hip("reset_opacity needs a HIP (cuda) tensor: there is no CPU path", opacity)
     dev = opacity.device
     out = opacity.detach().to(torch.float32).contiguous().clone()
     a = b = None
@@ -480,7 +477,5 @@ def reset_opacity(opacity: torch.Tensor, state: Optional[Tuple[torch.Tensor, tor
         for t in (a, b):
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != out.numel():
                 raise SgrError("the Adam moments must be contiguous float32 tensors shaped like opacity")
-    with torch.cuda.device(dev):
-        check(_native.lib().sgr_reset_opacity(out.numel(), ptr(out), ptr(a), ptr(b),
-                                              _native.stream(dev)))
+    call("sgr_reset_opacity", dev, out.numel(), out, a, b)
     return out

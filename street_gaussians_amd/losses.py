@@ -12,12 +12,11 @@ from typing import Optional
 import torch
 
 from . import _native
-from ._native import SgrError, check, ptr, stream
+from ._native import call, require_hip
 
 
 def _prep(img, name):
-    if not img.is_cuda:
-        raise SgrError(f"{name} must be a HIP (cuda) tensor: there is no CPU path")
+    require_hip(f"{name} must be a HIP (cuda) tensor: there is no CPU path", img)
     if img.dim() == 4:
         img = img.reshape(-1, img.shape[-2], img.shape[-1])
     if img.dim() != 3:
@@ -44,8 +43,7 @@ class _SSIM(torch.autograd.Function):
         out = torch.empty(1, dtype=torch.float32, device=dev)
         ws = torch.empty(L.sgr_ssim_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
         partials = torch.empty(3 * Cc * H * W, dtype=torch.float32, device=dev) if need else None
-        with torch.cuda.device(dev):
-            check(L.sgr_ssim_forward(Cc, H, W, ptr(img1), ptr(img2), ptr(mask), ptr(out), ptr(partials), ptr(ws), stream(dev)))
+        call("sgr_ssim_forward", dev, Cc, H, W, img1, img2, mask, out, partials, ws)
         ctx.save_for_backward(img1, img2, mask if mask is not None else torch.empty(0, device=dev), partials
                               if partials is not None else torch.empty(0, device=dev))
         ctx.has_mask = mask is not None
@@ -60,9 +58,7 @@ class _SSIM(torch.autograd.Function):
             raise RuntimeError("ssim forward ran without requires_grad")
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(img1)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_ssim_backward(Cc, H, W, ptr(img1), ptr(img2), ptr(mask) if ctx.has_mask else None,
-                                                  ptr(partials), ptr(up), ptr(grad), stream(dev)))
+        call("sgr_ssim_backward", dev, Cc, H, W, img1, img2, mask if ctx.has_mask else None, partials, up, grad)
         return grad, None, None
 
 
@@ -74,8 +70,7 @@ class _L1(torch.autograd.Function):
         dev = a.device
         out = torch.empty(2, dtype=torch.float32, device=dev)
         ws = torch.empty(L.sgr_l1_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(L.sgr_l1_forward(Cc, H, W, ptr(a), ptr(b), ptr(mask), ptr(out), ptr(ws), stream(dev)))
+        call("sgr_l1_forward", dev, Cc, H, W, a, b, mask, out, ws)
         ctx.save_for_backward(a, b, mask if mask is not None else torch.empty(0, device=dev), out)
         ctx.has_mask = mask is not None
         return out[0]
@@ -87,9 +82,7 @@ class _L1(torch.autograd.Function):
         dev = a.device
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(a)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_l1_backward(Cc, H, W, ptr(a), ptr(b), ptr(mask) if ctx.has_mask else None, ptr(out),
-                                                ptr(up), ptr(grad), stream(dev)))
+        call("sgr_l1_backward", dev, Cc, H, W, a, b, mask if ctx.has_mask else None, out, up, grad)
         return grad, None, None
 
 
@@ -100,8 +93,7 @@ class _BCE(torch.autograd.Function):
         dev, n = acc.device, acc.numel()
         out = torch.empty(1, dtype=torch.float32, device=dev)
         ws = torch.empty(L.sgr_l1_workspace_floats(1, 1, 1), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(L.sgr_bce_forward(n, mode, ptr(acc), ptr(mask), ptr(out), ptr(ws), stream(dev)))
+        call("sgr_bce_forward", dev, n, mode, acc, mask, out, ws)
         ctx.save_for_backward(acc, mask)
         ctx.mode = mode
         return out[0]
@@ -112,8 +104,7 @@ class _BCE(torch.autograd.Function):
         dev = acc.device
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(acc)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_bce_backward(acc.numel(), ctx.mode, ptr(acc), ptr(mask), ptr(up), ptr(grad), stream(dev)))
+        call("sgr_bce_backward", dev, acc.numel(), ctx.mode, acc, mask, up, grad)
         return grad, None, None
 
 
@@ -124,9 +115,7 @@ class _Lidar(torch.autograd.Function):
         dev, n = depth.device, depth.numel()
         out = torch.empty(4, dtype=torch.float32, device=dev)
         work = torch.empty(L.sgr_lidar_work_bytes(n), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(L.sgr_lidar_depth_forward(n, ptr(depth), ptr(acc), ptr(lidar), ptr(mask), float(keep), ptr(out), ptr(work),
-                                            stream(dev)))
+        call("sgr_lidar_depth_forward", dev, n, depth, acc, lidar, mask, float(keep), out, work)
         ctx.save_for_backward(depth, acc, lidar, out, work)
         return out[0]
 
@@ -136,15 +125,12 @@ class _Lidar(torch.autograd.Function):
         dev = depth.device
         up = upstream.reshape(1).to(torch.float32).contiguous()
         gd, ga = torch.empty_like(depth), torch.empty_like(acc)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_lidar_depth_backward(depth.numel(), ptr(depth), ptr(acc), ptr(lidar), ptr(out), ptr(work),
-                                                         ptr(up), ptr(gd), ptr(ga), stream(dev)))
+        call("sgr_lidar_depth_backward", dev, depth.numel(), depth, acc, lidar, out, work, up, gd, ga)
         return gd, ga, None, None, None
 
 
 def _flat(t, name, like=None):
-    if not t.is_cuda:
-        raise SgrError(f"{name} must be a HIP (cuda) tensor: there is no CPU path")
+    require_hip(f"{name} must be a HIP (cuda) tensor: there is no CPU path", t)
     if like is not None and t.numel() != like.numel():
         raise RuntimeError(f"{name} must have as many elements as the rendered map")
     return t.to(torch.float32).contiguous()
@@ -193,9 +179,8 @@ class _ColorLoss(torch.autograd.Function):
         ws = torch.empty(max(L.sgr_ssim_workspace_floats(Cc, H, W), L.sgr_l1_workspace_floats(Cc, H, W)),
                          dtype=torch.float32, device=dev)
         partials = torch.empty(3 * Cc * H * W, dtype=torch.float32, device=dev) if img.requires_grad else None
-        with torch.cuda.device(dev):
-            check(L.sgr_l1_forward(Cc, H, W, ptr(img), ptr(gt), ptr(mask), ptr(out_l), ptr(ws), stream(dev)))
-            check(L.sgr_ssim_forward(Cc, H, W, ptr(img), ptr(gt), ptr(mask), ptr(out_s), ptr(partials), ptr(ws), stream(dev)))
+        call("sgr_l1_forward", dev, Cc, H, W, img, gt, mask, out_l, ws)
+        call("sgr_ssim_forward", dev, Cc, H, W, img, gt, mask, out_s, partials, ws)
         ctx.save_for_backward(img, gt, mask if mask is not None else torch.empty(0, device=dev),
                               partials if partials is not None else torch.empty(0, device=dev), out_l)
         ctx.has_mask = mask is not None
@@ -213,10 +198,8 @@ class _ColorLoss(torch.autograd.Function):
             raise RuntimeError("color_loss forward ran without requires_grad")
         up = upstream.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(img)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_color_loss_backward(Cc, H, W, ptr(img), ptr(gt), ptr(mask) if ctx.has_mask else None,
-                                                        ptr(partials), ptr(out_l), ctx.w_l1, ctx.w_ssim, ptr(up), ptr(grad),
-                                                        stream(dev)))
+        call("sgr_color_loss_backward", dev, Cc, H, W, img, gt, mask if ctx.has_mask else None, partials, out_l, ctx.w_l1,
+             ctx.w_ssim, up, grad)
         return grad, None, None, None, None
 
 

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import SgrError, check
+from ._native import SgrError, launch, require_hip
 
 GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "semantic")
 # group name -> FlatScene attribute
@@ -228,8 +228,7 @@ class SegmentedAdam:
         dev = flat.xyz.device
         for a in (ATTR[g] for g in GROUPS):
             t = flat.tensors[a]
-            if not t.is_cuda:
-                raise SgrError("SegmentedAdam needs HIP (cuda) tensors: there is no CPU path")
+            require_hip("SegmentedAdam needs HIP (cuda) tensors: there is no CPU path", t)
             if t.device != dev:
                 raise ValueError("SegmentedAdam: every flat leaf must be on the same device")
             if t.dtype != torch.float32 or not t.is_contiguous():
@@ -285,11 +284,11 @@ class SegmentedAdam:
         if n_spans == 0:
             return
         dev = self.flat.xyz.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):  # the pinned staging buffers of the two tables are allocated with dev current
             chunks = self._chunk_table()
             recs = _pinned_to(rec, dev)
-            check(_native.lib().sgr_adam_step(_native.ptr(chunks), len(self.layout) * len(GROUPS), _native.ptr(recs), len(rec),
-                                              n_spans, self.betas[0], self.betas[1], _native.stream(dev)))
+            launch("sgr_adam_step", _native.stream(dev), chunks, len(self.layout) * len(GROUPS), recs, len(rec), n_spans,
+                   self.betas[0], self.betas[1])
         # the contiguous copies of strided gradients and the tables are freed on this stream: reused only after the launch
 
     # ---- state ---------------------------------------------------------------------------------------------------

@@ -24,8 +24,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import _native
-from ._native import Grow, SgrError, check, ptr, stream
+from ._native import Grow, SgrError, call, require_hip
 
 SEG_STATIC, SEG_ACTOR = 0, 1
 SEM_LOGITS, SEM_PROBABILITIES = 0, 1
@@ -107,8 +106,7 @@ class Segment:
 def _f32c(t, name):
     if t is None:
         return None
-    if not t.is_cuda:
-        raise SgrError(f"{name} must be a HIP (cuda) tensor: there is no CPU path")
+    require_hip(f"{name} must be a HIP (cuda) tensor: there is no CPU path", t)
     if t.dtype == torch.float32 and t.is_contiguous():
         return t  # only the data pointer is used
     return t.detach().to(torch.float32).contiguous()
@@ -153,10 +151,8 @@ class _Compose(torch.autograd.Function):
                 torch.empty(N, M, 3, **f), torch.empty(N, S, **f)]
         grow = Grow(dev)
         frame, fkeep = _frame(corr)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_forward_ex(
-                len(segs), arr, int(M), int(S), *[ptr(o) if o.numel() else None for o in outs], frame, grow.cb, None,
-                stream(dev)))
+        call("sgr_scene_compose_forward_ex", dev, len(segs), arr, int(M), int(S), *[o if o.numel() else None for o in outs],
+             frame, grow.cb, None)
         ctx.segs, ctx.M, ctx.S = segs, int(M), int(S)
         ctx.save_for_backward(*[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
@@ -195,10 +191,8 @@ class _Compose(torch.autograd.Function):
         dcorr = torch.empty(7, dtype=torch.float32, device=dev) if corr is not None and ctx.needs_input_grad[3] else None
         frame, fkeep = _frame(corr, dcorr)
         grow = Grow(dev)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_backward_ex(
-                len(segs), arr, garr, M, S, *[ptr(t) if t is not None and t.numel() else None for t in ins], frame,
-                grow.cb, None, stream(dev)))
+        call("sgr_scene_compose_backward_ex", dev, len(segs), arr, garr, M, S,
+             *[t if t is not None and t.numel() else None for t in ins], frame, grow.cb, None)
         del keep
         # kernels work in float32; hand autograd the dtype of each input
         grads = [g if g is None or g.dtype == t.dtype else g.to(t.dtype) for g, t in zip(grads, tensors)]
@@ -477,10 +471,8 @@ class _ComposeFlat(torch.autograd.Function):
                 torch.empty(N, M, 3, **f), torch.empty(N, S, **f)]
         grow = Grow(dev)
         cframe, fkeep = _frame(corr)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_forward_ex(
-                len(arr), arr, int(M), int(S), *[ptr(o) if o.numel() else None for o in outs], cframe, grow.cb, None,
-                stream(dev)))
+        call("sgr_scene_compose_forward_ex", dev, len(arr), arr, int(M), int(S), *[o if o.numel() else None for o in outs],
+             cframe, grow.cb, None)
         ctx.fs, ctx.frame, ctx.M, ctx.S = fs, frame, int(M), int(S)
         ctx.save_for_backward(*[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
@@ -504,10 +496,8 @@ class _ComposeFlat(torch.autograd.Function):
         dz = lambda t: None if t is None else _f32c(t, "grad")
         ins = [dz(d_means), dz(d_rot), dz(d_scale), dz(d_opac), dz(d_shs), dz(d_sem) if S else None]
         grow = Grow(dev)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_scene_compose_backward_ex(
-                len(arr), arr, garr, M, S, *[ptr(t) if t is not None and t.numel() else None for t in ins], cframe,
-                grow.cb, None, stream(dev)))
+        call("sgr_scene_compose_backward_ex", dev, len(arr), arr, garr, M, S,
+             *[t if t is not None and t.numel() else None for t in ins], cframe, grow.cb, None)
         del keep
         if dcorr is not None:
             dcorr = dcorr.view(correction.shape).to(correction.dtype)
@@ -519,8 +509,7 @@ def densification_stats(models: Sequence[dict], dL_dmeans2D: torch.Tensor, radii
     view's screen-space gradient [N,3] and radii [N] (models in concatenation order; dict keys as the attribute
     names of the reference's GaussianModel)."""
     dev = dL_dmeans2D.device
-    if not dL_dmeans2D.is_cuda:
-        raise SgrError("dL_dmeans2D must be a HIP (cuda) tensor: there is no CPU path")
+    require_hip("dL_dmeans2D must be a HIP (cuda) tensor: there is no CPU path", dL_dmeans2D)
     arr = (_CStatSeg * len(models))()
     for c, m in zip(arr, models):
         for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
@@ -533,9 +522,7 @@ def densification_stats(models: Sequence[dict], dL_dmeans2D: torch.Tensor, radii
     g = dL_dmeans2D.detach().to(torch.float32).contiguous()
     r = radii.to(torch.int32).contiguous()
     grow = Grow(dev)
-    with torch.cuda.device(dev):
-        check(_native.lib().sgr_scene_densification_stats(len(models), arr, ptr(g), ptr(r), grow.cb, None,
-                                                          stream(dev)))
+    call("sgr_scene_densification_stats", dev, len(models), arr, g, r, grow.cb, None)
 
 
 class FlatStats:

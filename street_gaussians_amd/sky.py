@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _native
-from ._native import SgrError, check, ptr, stream
+from ._native import call, require_hip
 
 TRAIN, WHITE, CLAMP = 1, 2, 4  # include/sgr_sky.h SGR_SKY_*
 SAVED, SCRATCH = 0, 1
@@ -25,9 +25,7 @@ class _SkyComposite(torch.autograd.Function):
         L = _native.lib()
         out = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         saved = torch.empty(L.sgr_sky_workspace_bytes(H, W, R, 3, SAVED), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(L.sgr_sky_forward(H, W, R, 3, ptr(rgb), ptr(acc), ptr(cube), ptr(K), ptr(w2c), ptr(mask), ptr(px), ptr(py),
-                                    ptr(affine), flags, ptr(out), ptr(saved), stream(dev)))
+        call("sgr_sky_forward", dev, H, W, R, 3, rgb, acc, cube, K, w2c, mask, px, py, affine, flags, out, saved)
         ctx.save_for_backward(rgb, acc, affine)
         ctx.saved_state = saved
         ctx.flags = flags
@@ -47,9 +45,8 @@ class _SkyComposite(torch.autograd.Function):
         dcube = torch.empty(ctx.cube_shape, dtype=torch.float32, device=dev)
         daff = torch.empty(3, 4, dtype=torch.float32, device=dev) if affine is not None else None
         scratch = torch.empty(L.sgr_sky_workspace_bytes(H, W, R, 3, SCRATCH), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(L.sgr_sky_backward(H, W, R, 3, ptr(g), ptr(rgb), ptr(acc), ptr(affine), ctx.flags, ptr(ctx.saved_state),
-                                     ptr(drgb), ptr(dacc), ptr(dcube), ptr(daff), ptr(scratch), stream(dev)))
+        call("sgr_sky_backward", dev, H, W, R, 3, g, rgb, acc, affine, ctx.flags, ctx.saved_state, drgb, dacc, dcube, daff,
+             scratch)
         return drgb, dacc, dcube, daff, None, None, None, None, None, None
 
 
@@ -115,8 +112,7 @@ def composite_sky(rgb, acc, cube_map, K, w2c, *, sky_mask=None, train=True, whit
     if perturb is not None and train:
         _f32("perturb", perturb, [(2, H, W)])
     tensors = [rgb, acc, cube_map, K, w2c] + [t for t in (affine, sky_mask, perturb if train else None) if t is not None]
-    if not all(t.is_cuda for t in tensors):
-        raise SgrError("composite_sky: every tensor must be a HIP (cuda) tensor: there is no CPU path")
+    require_hip("composite_sky: every tensor must be a HIP (cuda) tensor: there is no CPU path", *tensors)
     dev = rgb.device
     if any(t.device != dev for t in tensors):
         raise ValueError("composite_sky: every tensor must be on the same device")

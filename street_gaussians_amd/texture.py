@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _native
-from ._native import SgrError, check, ptr, stream
+from ._native import call, require_hip
 
 
 class _TextureCube(torch.autograd.Function):
@@ -20,8 +20,7 @@ class _TextureCube(torch.autograd.Function):
         B, H, W, _ = uv.shape
         dev = tex.device
         out = torch.empty(B, H, W, Cc, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(_native.lib().sgr_texture_cube_forward(Bt, B, R, Cc, H * W, ptr(tex), ptr(uv), ptr(out), stream(dev)))
+        call("sgr_texture_cube_forward", dev, Bt, B, R, Cc, H * W, tex, uv, out)
         ctx.save_for_backward(uv)
         ctx.tex_shape = tex.shape
         return out
@@ -36,8 +35,7 @@ class _TextureCube(torch.autograd.Function):
         up = dout.to(torch.float32).contiguous()
         grad = torch.empty(ctx.tex_shape, dtype=torch.float32, device=dev)
         work = torch.empty(L.sgr_texture_cube_workspace_bytes(Bt, B, R, Cc, H * W), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(L.sgr_texture_cube_backward(Bt, B, R, Cc, H * W, ptr(uv), ptr(up), ptr(grad), ptr(work), stream(dev)))
+        call("sgr_texture_cube_backward", dev, Bt, B, R, Cc, H * W, uv, up, grad, work)
         return grad, None
 
 
@@ -72,8 +70,7 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
         raise ValueError(f"texture: cube-map directions must have shape [B, H, W, 3], got {list(uv.shape)}")
     if tex.shape[0] not in (1, uv.shape[0]):
         raise ValueError(f"texture: tex batch {tex.shape[0]} must be 1 or the uv batch {uv.shape[0]}")
-    if not tex.is_cuda or not uv.is_cuda:
-        raise SgrError("texture: tex and uv must be HIP (cuda) tensors: there is no CPU path")
+    require_hip("texture: tex and uv must be HIP (cuda) tensors: there is no CPU path", tex, uv)
     if tex.device != uv.device:
         raise ValueError("texture: tex and uv must be on the same device")
     return _TextureCube.apply(tex.contiguous(), uv.detach().contiguous())
