@@ -105,6 +105,10 @@ int sgr_actor_pose_forward(int K, const sgr_actor_pose_record* records, int n_ce
                            const float* input_rots, const float* opt_trans, const float* opt_rots, const float* ego,
                            float* poses, float* parts, void* stream);
 
+/* workgroups (of 256 threads) of the backward's largest first launch: past it the zeroing of d_opt_trans / d_opt_rots and
+ * the actors are walked grid-stride */
+int sgr_actor_pose_backward_max_blocks(void);
+
 /* d_opt_trans [n_cells, 3] and d_opt_rots [n_cells] from dposes [K, 7]; contrib [K, SGR_ACTOR_POSE_CONTRIB] is scratch.
  * Needs opt_trans and opt_rots.  K = 0 zeroes the gradients. */
 int sgr_actor_pose_backward(int K, const sgr_actor_pose_record* records, int n_cells, const float* input_trans,

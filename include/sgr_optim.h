@@ -20,7 +20,9 @@
  *   chunks   [n_chunks]   sgr_adam_chunk: p, m, v, count; built once per layout
  *   records  [n_records]  sgr_adam_record, one per chunk stepped now, in increasing span_start with records[0].span_start
  *                         = 0: the gradient g of that chunk (count floats), the index of its chunk, its first span and
- *                         its f32 scalars.  A chunk without a record is not touched.
+ *                         its f32 scalars.  A chunk without a record is not touched.  One step takes at most
+ *                         sgr_adam_max_records() records (the span starts of all of them sit in LDS); a longer table
+ *                         is refused and nothing is launched: the caller splits the step.
  * A span is sgr_adam_span_elems() consecutive elements of one chunk; a chunk of count elements has
  * ceil(count / span) spans, record i owns spans [span_start_i, span_start_{i+1}) and n_spans is the total.  Chunks
  * may start at any 4-byte offset: where p, g, m and v are equally aligned modulo 16 bytes the body moves as float4,
@@ -55,10 +57,14 @@ typedef struct sgr_adam_record {
 
 /* elements per span (a power of two, a multiple of 4) */
 int sgr_adam_span_elems(void);
+/* workgroups of the largest grid: a step of more spans walks them grid-stride, span += the grid */
+int sgr_adam_max_blocks(void);
+/* records one step takes at most (4096) */
+int sgr_adam_max_records(void);
 
 /* One Adam step of every chunk named by a record.  beta1 / beta2 are the optimiser's betas (c1 = 1 - beta1 and
  * c2 = 1 - beta2 are formed in double, then rounded).  SGR_E_INVALID: negative sizes, n_spans > 0 without tables,
- * betas outside [0, 1). */
+ * betas outside [0, 1), n_records > sgr_adam_max_records(), n_spans > 2^31 - 1. */
 int sgr_adam_step(const sgr_adam_chunk* chunks, int n_chunks, const sgr_adam_record* records, int n_records,
                   int64_t n_spans, double beta1, double beta2, void* stream);
 

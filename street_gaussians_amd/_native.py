@@ -102,12 +102,15 @@ def _signatures():
         "sgr_texture_cube_forward": (i, [i, i, i, i, i64, vp, vp, vp, vp]),
         "sgr_texture_cube_backward": (i, [i, i, i, i, i64, vp, vp, vp, vp, vp]),
         "sgr_adam_span_elems": (i, []),
+        "sgr_adam_max_blocks": (i, []),
+        "sgr_adam_max_records": (i, []),
         "sgr_adam_step": (i, [vp, i, vp, i, i64, d, d, vp]),
         "sgr_sky_workspace_bytes": (sz, [i, i, i, i, i]),
         "sgr_sky_forward": (i, [i, i, i, i] + [vp] * 9 + [i, vp, vp, vp]),
         "sgr_sky_backward": (i, [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
         "sgr_sky_test_rays": (i, [i, i, vp, vp, vp, vp, i, vp, vp, vp]),
         "sgr_actor_pose_forward": (i, [i, vp, i] + [vp] * 7 + [vp]),
+        "sgr_actor_pose_backward_max_blocks": (i, []),
         "sgr_actor_pose_backward": (i, [i, vp, i] + [vp] * 9 + [vp]),
         "sgr_test_sort32_count": (i, [vp, vp, vp, vp, u32, i, i, vp, vp, vp, vp]),
     }

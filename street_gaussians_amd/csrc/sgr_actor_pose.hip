@@ -352,6 +352,8 @@ int check_args(const char* what, int K, const void* records, int n_cells, const 
 
 }  // namespace
 
+int sgr_actor_pose_backward_max_blocks(void) { return SGR_AP_MAX_BLOCKS; }
+
 int sgr_actor_pose_forward(int K, const sgr_actor_pose_record* records, int n_cells, const float* input_trans,
                            const float* input_rots, const float* opt_trans, const float* opt_rots, const float* ego,
                            float* poses, float* parts, void* stream_) {

@@ -120,6 +120,8 @@ sgr_adam_step_kernel(const sgr_adam_chunk* __restrict__ chunks, const sgr_adam_r
 }
 
 int sgr_adam_span_elems(void) { return (int)SGR_ADAM_SPAN; }
+int sgr_adam_max_blocks(void) { return SGR_ADAM_CUS * SGR_ADAM_BLOCKS_PER_CU; }
+int sgr_adam_max_records(void) { return SGR_ADAM_MAX_RECORDS; }
 
 int sgr_adam_step(const sgr_adam_chunk* chunks, int n_chunks, const sgr_adam_record* records, int n_records,
                   int64_t n_spans, double beta1, double beta2, void* stream_) {
@@ -134,7 +136,7 @@ int sgr_adam_step(const sgr_adam_chunk* chunks, int n_chunks, const sgr_adam_rec
         return sgr_set_error(SGR_E_INVALID, "adam: n_spans > 0 needs the chunk and record tables");
     if (n_spans > (int64_t)INT32_MAX) return sgr_set_error(SGR_E_INVALID, "adam: more than 2^31 - 1 spans");
     const AdamConsts k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2)};
-    const int64_t cap = (int64_t)SGR_ADAM_CUS * SGR_ADAM_BLOCKS_PER_CU;
+    const int64_t cap = sgr_adam_max_blocks();
     const unsigned grid = (unsigned)(n_spans < cap ? n_spans : cap);
     sgr_adam_step_kernel<<<grid, SGR_ADAM_THREADS, (size_t)n_records * sizeof(int32_t), (hipStream_t)stream_>>>(
         chunks, records, n_chunks, n_records, n_spans, k);

@@ -93,11 +93,12 @@ def chunk_table(layout, p: Dict[str, int], m: Dict[str, int], v: Dict[str, int])
 
 def plan_step(layout, steps: List[Dict[str, int]], lrs: List[Dict[str, float]], segments: Optional[Sequence[int]],
               grads: Dict[str, int], betas: Tuple[float, float], eps: float, span: int, advance: bool = True,
-              bc_cache: Optional[dict] = None) -> Tuple[np.ndarray, int]:
+              bc_cache: Optional[dict] = None, max_records: Optional[int] = None) -> Tuple[np.ndarray, int]:
     """The sgr_adam_record table (RECORD_DTYPE) of one step and its span total.  A (segment, group) takes part when
     the segment is in ``segments`` (None = all) and the group's flat gradient is in ``grads`` ({group: base address});
     with ``advance`` its step count goes up by one first -- count 0 included, as torch steps an empty parameter -- and
-    only chunks with count > 0 get a record."""
+    only chunks with count > 0 get a record.  A step of more than ``max_records`` records (sgr_adam_max_records()) is
+    refused with an SgrError before any step count advances."""
     nseg = len(layout)
     if segments is None:
         segs = range(nseg)
@@ -105,6 +106,11 @@ def plan_step(layout, steps: List[Dict[str, int]], lrs: List[Dict[str, float]], 
         segs = sorted({int(s) for s in segments})
         if segs and (segs[0] < 0 or segs[-1] >= nseg):
             raise IndexError(f"SegmentedAdam.step: segment index out of range [0, {nseg})")
+    if max_records is not None:
+        n = sum(1 for s in segs for g in GROUPS if g in grads and layout[s][g][1])
+        if n > max_records:
+            raise SgrError(f"SegmentedAdam: {n} records in one step, the limit is {max_records} (sgr_adam_max_records): "
+                           "step the segments in several calls")
     bc_cache = {} if bc_cache is None else bc_cache
     rec = np.zeros(nseg * len(GROUPS), dtype=RECORD_DTYPE)
     n, span_start = 0, 0
@@ -247,6 +253,7 @@ class SegmentedAdam:
     def _relayout(self):
         self.layout = segment_layout(self.flat.meta, _rest_width(self.flat))
         self._span = int(_native.lib().sgr_adam_span_elems())
+        self._max_records = int(_native.lib().sgr_adam_max_records())
         self._chunks_dev = None
         self._chunks_key = None
         self._bc = {}
@@ -267,7 +274,9 @@ class SegmentedAdam:
         """One Adam step of the segments in ``segments`` (indices into ``flat.meta``; None = every segment), on the
         current stream, without a host synchronisation.  A group whose flat leaf has ``.grad is None`` is skipped for
         every segment; a skipped (segment, group) keeps its bytes and its step count.  Set the leaves' ``.grad`` to
-        None afterwards, as the reference's ``zero_grad(set_to_none=True)`` does."""
+        None afterwards, as the reference's ``zero_grad(set_to_none=True)`` does.  One step takes at most
+        sgr_adam_max_records() (4096) non-empty (segment, group) blocks, 585 models with all seven: more is refused with
+        an SgrError before anything changes, and the caller steps the segments in several calls."""
         grads = {}
         for g in GROUPS:
             leaf = self.flat.tensors[ATTR[g]]
@@ -280,7 +289,7 @@ class SegmentedAdam:
                 raise ValueError(f"SegmentedAdam: flat.{ATTR[g]}.grad must be float32 and shaped like the leaf")
             grads[g] = gt if gt.is_contiguous() else gt.contiguous()
         rec, n_spans = plan_step(self.layout, self.steps, self.lrs, segments, {g: t.data_ptr() for g, t in grads.items()},
-                                 self.betas, self.eps, self._span, bc_cache=self._bc)
+                                 self.betas, self.eps, self._span, bc_cache=self._bc, max_records=self._max_records)
         if n_spans == 0:
             return
         dev = self.flat.xyz.device

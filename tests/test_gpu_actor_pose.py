@@ -244,3 +244,59 @@ def test_from_reference_shares_the_parameters():
     assert mk.gate("drots", module.opt_rots.grad.cpu().numpy(), c["drots64"], E_REF["drots"], c["drots32"])[0]
     optim.step()
     assert not torch.equal(before, module.opt_rots.detach())
+
+
+def _embedded(c, frames):
+    """The case as the LAST rows of a table of ``frames`` frames: the rows before them are padding no track lives in
+    (track_ids -1, timestamps well before the case's first), with values of their own in every tensor."""
+    F0, O = c["track_ids"].shape
+    pad = frames - F0
+    rng = np.random.default_rng(pad)
+    big = dict(c)
+    big["track_ids"] = np.concatenate([np.full((pad, O), -1, np.int32), c["track_ids"]])
+    for k in ("input_trans", "input_rots", "opt_trans", "opt_rots"):
+        big[k] = np.concatenate([rng.standard_normal((pad,) + c[k].shape[1:]).astype(np.float32), c[k]])
+    big["timestamps"] = np.concatenate([c["timestamps"][0] - 1000.0 - 0.125 * np.arange(pad, 0, -1), c["timestamps"]])
+    return big, pad
+
+
+@pytest.mark.parametrize("name,frames", [("mid_opt", 60_000), ("k65", 2_604)])
+def test_gradient_of_a_table_past_the_zeroing_grid(name, frames):
+    """A drive-length table (450 frames x 200 objects is past the cap too): the backward's first launch zeroes d_opt_trans
+    grid-stride, here in two full trips and a ragged third, and the case's cells are in the third.  The plan, the poses
+    and the case's gradient rows are those of the small table bit for bit (the per-address add order does not depend on the
+    cell index), inside the fixture's gate; every padding row of both gradients is exactly 0.0 although the blocks
+    torch.empty_like hands out were NaN.  The cap is the library's: were it raised, this fails instead of passing for
+    nothing."""
+    from street_gaussians_amd import _native
+    c = mk.case(D, name)
+    big, pad = _embedded(c, frames)
+    F0, O = c["track_ids"].shape
+    stride = _native.lib().sgr_actor_pose_backward_max_blocks() * 256
+    assert stride > 0 and 2 * stride < 3 * frames * O < 3 * stride, \
+        f"3 x {frames * O} cells no longer reach two full trips and a ragged third of {stride} threads"
+    assert 3 * pad * O > 2 * stride                         # the case's own cells are zeroed by the third trip
+    _, plan0, small = _run(c)
+
+    ap = _actor_poses(big)
+    plan = _plan(ap, big)
+    assert np.array_equal(plan.cells(), plan0.cells() + pad * O)
+    for f in ("wa", "wb", "wd", "r"):
+        assert np.array_equal(plan.records["s"][f].view(np.int32), plan0.records["s"][f].view(np.int32)), f
+    assert np.array_equal(plan.records["n_samples"], plan0.records["n_samples"])
+    out = ap.poses(plan, torch.from_numpy(big["ego"]).to(DEV))
+    junk = [torch.full_like(ap.opt_trans, float("nan")), torch.full_like(ap.opt_rots, float("nan"))]
+    del junk
+    out.backward(torch.from_numpy(big["g"]).to(DEV))
+    got = {"rot": out[:, :4].detach().cpu().numpy(), "trans": out[:, 4:].detach().cpu().numpy()}
+    for k in ("rot", "trans"):
+        assert np.array_equal(got[k].view(np.int32), small[k].view(np.int32)), k
+    for k, grad in (("dtrans", ap.opt_trans.grad), ("drots", ap.opt_rots.grad)):
+        assert grad.shape == (frames, O, 3 if k == "dtrans" else 1)
+        not_zero = int(grad[:pad].contiguous().view(torch.int32).count_nonzero())
+        assert not_zero == 0, f"{k}: {not_zero} elements of the padding rows are not exactly 0.0"
+        tail = grad[pad:].cpu().numpy()
+        ok, need = mk.gate(k, tail, c[k + "64"], E_REF[k], c[k + "32"])
+        print(f"actor_pose gate {name} in {frames} frames {k}: needs {need:.3f} x e_ref")
+        assert ok, (k, need)
+        assert np.array_equal(tail.view(np.int32), small[k].view(np.int32)), k

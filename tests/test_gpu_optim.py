@@ -1,7 +1,8 @@
 """The fused per-segment Adam step (street_gaussians_amd/optim.py, include/sgr_optim.h) on the GPU: bitwise against the
 float32 restatement of its declared arithmetic (torch_ref_optim.py), against one torch.optim.Adam(eps=1e-15) per model
 over 50 steps with schedules, lr = 0 and absent models, untouched absent chunks, densification, reproducibility, no
-host synchronisation and a non-default stream."""
+host synchronisation and a non-default stream; and past its loop bounds: more spans than the grid has workgroups, as many
+records as the table takes and one more, chunks that end on a span, every head length of the float4 path."""
 import copy
 import math
 
@@ -341,3 +342,183 @@ def test_state_dict_round_trip_on_device():
     for g in GROUPS:
         for x, y in zip(other.state_views(2)[g], opt.state_views(2)[g]):
             assert torch.equal(x, y)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# past the loop bounds: the grid-stride walk of the spans, the LDS copy and the search of the record table, the refusal
+# of a table that is too long, and the edges of a span.  Every value check is bitwise against the restatement.
+def _lib():
+    from street_gaussians_amd import _native
+    return _native.lib()
+
+
+def _set_wide_grads(flat, opt, seed):
+    """_wide_grads on every leaf; zero moments where the gradient is zero (0 / eps, as the first test has it)."""
+    for i, a in enumerate(ATTR[g] for g in GROUPS):
+        leaf = flat.tensors[a]
+        gr = _wide_grads(leaf.shape, seed + i)
+        z = gr.reshape(-1) == 0
+        opt.exp_avg[a].view(-1)[z] = 0.0
+        opt.exp_avg_sq[a].view(-1)[z] = 0.0
+        leaf.grad = gr
+
+
+def _snapshot(flat, opt):
+    """{attr: (p, exp_avg, exp_avg_sq, grad)} as flat host arrays."""
+    h = lambda t: t.detach().reshape(-1).cpu().numpy().copy()
+    return {a: (h(flat.tensors[a]), h(opt.exp_avg[a]), h(opt.exp_avg_sq[a]), h(flat.tensors[a].grad)) for a in flat.tensors}
+
+
+def _plan_only(opt, flat, segments=None):
+    """The record table and span total the next step will use, planned on a copy of the step counts."""
+    grads = {g: flat.tensors[ATTR[g]].grad.data_ptr() for g in GROUPS if flat.tensors[ATTR[g]].grad is not None}
+    return optim.plan_step(opt.layout, copy.deepcopy(opt.steps), opt.lrs, segments, grads, opt.betas, opt.eps, opt._span)
+
+
+def _assert_step_bitwise(flat, opt, before, steps0, present):
+    """After one step of the segments ``present``: every element of every flat p, exp_avg and exp_avg_sq is the
+    restatement's where a chunk was stepped and its bytes from before the step everywhere else (absent segments, and
+    whatever of a flat tensor no chunk covers)."""
+    want = {a: [x.copy() for x in before[a][:3]] for a in before}
+    for s, lay in enumerate(opt.layout):
+        for g in GROUPS:
+            off, cnt, _ = lay[g]
+            assert opt.steps[s][g] == steps0[s][g] + int(s in present), (s, g)
+            if not cnt or s not in present:
+                continue
+            sl = slice(off, off + cnt)
+            p0, m0, v0, g0 = (x[sl] for x in before[ATTR[g]])
+            for dst, new in zip(want[ATTR[g]], tr.adam_step(p0, g0, m0, v0, opt.lrs[s][g], opt.steps[s][g])):
+                dst[sl] = new
+    for a in before:
+        got = [t.detach().reshape(-1).cpu().numpy() for t in (flat.tensors[a], opt.exp_avg[a], opt.exp_avg_sq[a])]
+        for name, x, y in zip(("p", "exp_avg", "exp_avg_sq"), got, want[a]):
+            if not _bits_equal(x, y):
+                bad = np.flatnonzero(~((x.view(np.int32) == y.view(np.int32)) | (np.isnan(x) & np.isnan(y))))
+                raise AssertionError(f"{a} {name}: {bad.size} of {x.size} elements differ, the first at {bad[0]}")
+
+
+def test_one_step_past_the_grid_cap():
+    """A scene of more spans than the grid has workgroups: every workgroup walks two spans and some a third (the real
+    size, 1 M Gaussians, makes about 14 trips).  The cap is the library's: were it raised, this fails instead of passing
+    without reaching the loop."""
+    cap = _lib().sgr_adam_max_blocks()
+    specs = [(150_001, 1, 19, False), (7, 5, 1, True), (13, 3, 0, True), (1, 1, 1, True), (4_099, 1, 1, True)]
+    flat = _flat(specs, seed=21)
+    opt = SegmentedAdam(flat, _lrs(len(specs), 21))
+    _random_state(opt, 22)
+    _set_wide_grads(flat, opt, 30)
+    rec, n_spans = _plan_only(opt, flat)
+    assert cap > 0 and 2 * cap < n_spans < 3 * cap and n_spans % cap != 0, \
+        f"{n_spans} spans no longer reach two full trips and a ragged third of a grid of {cap}"
+    before, steps0 = _snapshot(flat, opt), copy.deepcopy(opt.steps)
+    opt.step()
+    torch.cuda.synchronize()
+    _assert_step_bitwise(flat, opt, before, steps0, set(range(len(specs))))
+    assert np.isnan(flat.features_rest.detach().cpu().numpy()).any()
+
+
+def _actor_specs(n_records):
+    """Actors of 1 to 7 points, fourier_dim 1, 3 or 5, that give exactly ``n_records`` records when all are stepped: 7 per
+    actor, 6 for one without a semantic column."""
+    n_actors = n_records // 7 + 1
+    no_sem = 7 * n_actors - n_records                      # 1 to 7 of them, spread over the table
+    stride = n_actors // no_sem
+    return [(1 + i % 7, (1, 3, 1, 5)[i % 4], 0 if i % stride == 0 and i // stride < no_sem else 1, True)
+            for i in range(n_actors)]
+
+
+def _many_record_scene(n_records, seed):
+    specs = _actor_specs(n_records)
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g).to(DEV)
+    segs = [Segment(r(n, 3), r(n, 4), r(n, 3), r(n, 1), r(n, fd, 3), r(n, 15, 3), semantic=r(n, sw) if sw else None,
+                    pose=r(7), idft=r(fd)) for n, fd, sw, _ in specs]
+    flat = FlatScene.from_segments(segs)
+    opt = SegmentedAdam(flat, _lrs(len(specs), seed))
+    _random_state(opt, seed + 1)
+    _set_wide_grads(flat, opt, seed + 2)
+    return specs, flat, opt
+
+
+@pytest.mark.parametrize("below", [1, 0], ids=["limit-1", "limit"])
+def test_one_step_of_as_many_records_as_the_table_takes(below):
+    """As many records as the table takes, and one less (4095 at a limit of 4096), of small actors, some with
+    fourier_dim > 1, some without a semantic column: the copy of the span starts into LDS makes 16 trips and the search
+    is 12 deep.  Then a subset of the segments, so that the records' chunk indices have gaps."""
+    limit = _lib().sgr_adam_max_records()
+    n_records = limit - below
+    assert n_records > 256 * 2, "the table no longer reaches a second trip of the LDS copy"
+    specs, flat, opt = _many_record_scene(n_records, seed=40 + below)
+    assert {fd for _, fd, _, _ in specs} >= {1, 3, 5} and {sw for _, _, sw, _ in specs} == {0, 1}
+    rec, n_spans = _plan_only(opt, flat)
+    assert len(rec) == n_records and n_spans == n_records
+    before, steps0 = _snapshot(flat, opt), copy.deepcopy(opt.steps)
+    opt.step()
+    torch.cuda.synchronize()
+    _assert_step_bitwise(flat, opt, before, steps0, set(range(len(specs))))
+
+    present = [s for s in range(len(specs)) if s % 3 != 1 and s % 11 != 0]
+    rec, _ = _plan_only(opt, flat, present)
+    assert len(rec) > 256 * 2 and (np.diff(rec["chunk"]) > 1).any()
+    before, steps0 = _snapshot(flat, opt), copy.deepcopy(opt.steps)
+    opt.step(segments=present)
+    torch.cuda.synchronize()
+    _assert_step_bitwise(flat, opt, before, steps0, set(present))
+
+
+def test_a_step_of_too_many_records_is_refused_with_nothing_changed():
+    """One record more than the table takes: an SgrError that names the limit, and the step counts, the parameters and
+    the moments are what they were (the step counts used to advance before the native call refused the table)."""
+    limit = _lib().sgr_adam_max_records()
+    specs, flat, opt = _many_record_scene(limit + 1, seed=50)
+    rec, _ = _plan_only(opt, flat)
+    assert len(rec) == limit + 1
+    before, steps0 = _snapshot(flat, opt), copy.deepcopy(opt.steps)
+    with pytest.raises(optim.SgrError, match=str(limit)):
+        opt.step()
+    torch.cuda.synchronize()
+    assert opt.steps == steps0
+    _assert_step_bitwise(flat, opt, before, steps0, set())
+    # a subset that fits still steps
+    opt.step(segments=range(1, len(specs)))
+    torch.cuda.synchronize()
+    _assert_step_bitwise(flat, opt, before, steps0, set(range(1, len(specs))))
+
+
+def test_span_edges_and_every_head_length():
+    """Chunks that end exactly on a span (4096 points: opacity is one span, xyz three; 1024 points: rotation is one span),
+    aligned and not, and the float4 path's head: every head length 0..3, a chunk shorter than its head, a chunk without
+    a single float4.  The coverage is computed from the layout and the addresses, so it holds or fails with them."""
+    span = _lib().sgr_adam_span_elems()
+    specs = [(span, 1, 19, False), (span // 4, 1, 1, True), (5, 3, 1, True), (1, 1, 1, True), (1, 1, 0, True),
+             (1, 5, 1, True), (7, 1, 1, True), (2, 1, 1, True), (span, 1, 1, True)]
+    flat = _flat(specs, seed=60)
+    opt = SegmentedAdam(flat, _lrs(len(specs), 60))
+    _random_state(opt, 61)
+    _set_wide_grads(flat, opt, 62)
+    heads, shorter, no_vec, exact = set(), 0, 0, set()
+    for lay in opt.layout:
+        for g in GROUPS:
+            off, cnt, _ = lay[g]
+            if not cnt:
+                continue
+            a = ATTR[g]
+            addr = [t.data_ptr() + 4 * off for t in (flat.tensors[a], flat.tensors[a].grad, opt.exp_avg[a], opt.exp_avg_sq[a])]
+            if len({x & 15 for x in addr}) != 1:
+                continue                                  # the scalar path
+            h = ((16 - (addr[0] & 15)) & 15) >> 2
+            heads.add(h)
+            shorter += cnt < h
+            last = cnt - (cnt - 1) // span * span         # elements of the chunk's last span
+            no_vec += (max(last - h, 0) >> 2) == 0
+            if cnt % span == 0:
+                exact.add((cnt // span, h))
+    assert heads == {0, 1, 2, 3}, heads
+    assert shorter > 0 and no_vec > shorter
+    assert {n for n, _ in exact} >= {1, 3} and {h for _, h in exact} > {0}, exact
+    assert opt.layout[1]["rotation"][1] == span
+    before, steps0 = _snapshot(flat, opt), copy.deepcopy(opt.steps)
+    opt.step()
+    torch.cuda.synchronize()
+    _assert_step_bitwise(flat, opt, before, steps0, set(range(len(specs))))

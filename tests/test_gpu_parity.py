@@ -878,14 +878,44 @@ def test_prefiltered_raises_instead_of_trapping():
         rast(m, None, dev(sc.opacities), shs=dev(sc.shs), scales=dev(sc.scales), rotations=dev(sc.rotations))
 
 
+def _knn_clouds(sizes, seed):
+    """(name, points): per size a cloud that straddles the origin on every axis, one with every coordinate positive (in
+    [3, 13]^3: the {0,0,0} initial value of the bounding-box reduction, cub's `init` in the reference, then widens the box)
+    and one with a constant non-zero axis (an all-zero axis divides 0 by 0 in the Morton code, which nothing defines).
+    Every cloud of more than one point has a duplicated point."""
+    g = torch.Generator().manual_seed(seed)
+    for n in sizes:
+        straddling = torch.rand(n, 3, generator=g) * torch.tensor([10.0, 4.0, 7.0]) - 2.0
+        positive = torch.rand(n, 3, generator=g) * 10.0 + 3.0
+        flat = torch.rand(n, 3, generator=g) * torch.tensor([10.0, 4.0, 7.0]) - 2.0
+        flat[:, 1] = -2.5 if n % 2 else 1.75
+        for name, pts in (("straddling", straddling), ("positive", positive), ("flat-y", flat)):
+            pts[n // 2] = pts[0]
+            yield f"{name} n={n}", pts
+
+
+def _same_bits(a, b):
+    """Array equality on the bits: inf (fewer than four points: a missing neighbour's distance stays FLT_MAX and the sum
+    overflows) is a value like any other."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+KNN_SMALL = [1, 2, 3, 4]  # fewer points than neighbours + 1, and the first size with three of them
+
+
 def test_knn_matches_oracle_bit_exact():
+    """Sizes: KNN_SMALL, one box exactly (1024) and one point more, the edge of the bounding-box reduction's blocks (4096 /
+    4097), and several boxes."""
     from simple_knn._C import distCUDA2
-    g = torch.Generator().manual_seed(3)
-    for n in [5, 1000, 1025, 50000]:
-        pts = torch.rand(n, 3, generator=g) * torch.tensor([10.0, 4.0, 7.0]) - 2.0
-        pts[n // 2] = pts[0]  # a duplicate point
-        d = distCUDA2(pts.cuda())
-        assert (npy(d) == oracle.dist2(pts)).all()
+    for name, pts in _knn_clouds(KNN_SMALL + [5, 1000, 1024, 1025, 4096, 4097, 50000], seed=3):
+        want = oracle.dist2(pts)
+        n = pts.shape[0]
+        if n < 3:    # the cases are what they are there for: no third neighbour, and below three points not even a sum
+            assert np.isinf(want).all(), name
+        else:
+            assert np.isfinite(want).all() and bool((want > 1e37).all()) == (n == 3), name
+        assert _same_bits(npy(distCUDA2(pts.cuda())), want), name
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -940,6 +970,8 @@ def test_knn_against_reference_kernels():
     g = torch.Generator().manual_seed(7)
     pts = torch.randn(200000, 3, generator=g) * torch.tensor([30.0, 3.0, 40.0])
     assert torch.equal(distCUDA2(pts.cuda()), ref.dist2(pts))
+    for name, pts in _knn_clouds(KNN_SMALL + [1024, 4097], seed=8):
+        assert _same_bits(npy(distCUDA2(pts.cuda())), npy(ref.dist2(pts))), name
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -33,6 +33,62 @@ def test_span_size_is_the_librarys():
     assert _native.lib().sgr_adam_span_elems() == SPAN
 
 
+def test_limits_are_the_librarys_and_the_header_states_them():
+    """The grid cap and the record limit are exported next to the span size (the GPU tests size their cases from them), the
+    header's contract names the record limit, and the native entry point refuses a longer table before it launches."""
+    import ctypes as C
+    import os
+    from street_gaussians_amd import _native, build
+    build.build()
+    lib = _native.lib()
+    limit = lib.sgr_adam_max_records()
+    assert lib.sgr_adam_max_blocks() == 1024 and limit == 4096
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sgr_optim.h")).read()
+    contract = header[:header.index("#ifndef SGR_OPTIM_H")]
+    assert "sgr_adam_max_records()" in contract and "refused" in contract
+    assert lib.sgr_adam_step(None, 1, None, limit + 1, C.c_int64(1), 0.9, 0.999, None) < 0
+    assert str(limit).encode() in lib.sgr_last_error()
+
+
+def _too_many(limit):
+    """Layout, step counts and learning rates of one-point actors that give limit + 1 records when all are stepped: 7 per
+    actor, 6 for the first few, which have no semantic column."""
+    n = limit // 7 + 1
+    no_sem = 7 * n - (limit + 1)
+    lay = optim.segment_layout([_meta(1, sw=int(i >= no_sem)) for i in range(n)], 45)
+    steps = [{g: 3 + s % 5 for g in GROUPS} for s in range(n)]
+    lrs = [{g: 1e-3 for g in GROUPS} for _ in range(n)]
+    return lay, steps, lrs
+
+
+def test_plan_refuses_too_many_records_before_any_step_count_advances():
+    from street_gaussians_amd import _native, build
+    build.build()
+    limit = _native.lib().sgr_adam_max_records()
+    lay, steps, lrs = _too_many(limit)
+    grads = {g: 0x20000000 * (i + 1) for i, g in enumerate(GROUPS)}
+    rest = ((0.9, 0.999), 1e-15, SPAN)
+    rec, n_spans = optim.plan_step(lay, steps, lrs, None, grads, *rest, advance=False)
+    assert len(rec) == limit + 1 == n_spans
+    steps0 = copy.deepcopy(steps)
+    with pytest.raises(optim.SgrError, match=str(limit)):
+        optim.plan_step(lay, steps, lrs, None, grads, *rest, max_records=limit)
+    assert steps == steps0
+    # exactly the limit passes, and advances what it steps: every segment with one group's gradient missing ...
+    fewer = {g: a for g, a in grads.items() if g != "opacity"}
+    assert limit + 1 - len(lay) <= limit
+    rec, _ = optim.plan_step(lay, steps, lrs, None, fewer, *rest, max_records=limit + 1 - len(lay))
+    assert len(rec) == limit + 1 - len(lay)
+    assert all(steps[s][g] == steps0[s][g] + int(g != "opacity") for s in range(len(lay)) for g in GROUPS)
+    # ... and every gradient without the last segment
+    steps = copy.deepcopy(steps0)
+    rec, _ = optim.plan_step(lay, steps, lrs, range(len(lay) - 1), grads, *rest, max_records=limit - 6)
+    assert len(rec) == limit - 6 and steps[-1] == steps0[-1]
+    assert all(steps[s][g] == steps0[s][g] + 1 for s in range(len(lay) - 1) for g in GROUPS)
+    with pytest.raises(optim.SgrError):
+        optim.plan_step(lay, steps, lrs, range(len(lay) - 1), grads, *rest, max_records=limit - 7)
+
+
 def test_layout_matches_flat_views_odd_counts_fourier_and_no_semantic():
     segs = [_seg(1001, sw=19, seed=1), _seg(7, fd=5, sw=1, actor=True, seed=2), _seg(13, fd=1, sw=0, actor=True, seed=3),
             _seg(1, fd=3, sw=1, actor=True, seed=4)]
