@@ -201,6 +201,58 @@ def rasterize_gaussians_layers(background, means3D, colors, semantics, opacity, 
                     debug)
 
 
+def layer_alpha_forward(P, R, image_height, image_width, split, geomBuffer, binningBuffer, imageBuffer):
+    """sgr_layer_alpha_forward (include/sgr_object_alpha.h): the alpha image of Gaussians [split, P) blended alone, from the
+    finished buffers of a rasterize_gaussians call of the same frame (R: its first return value).
+    Returns (alpha [1, H, W] float32, last [H, W] int32 -- the layer's per-pixel last contributor, for the backward)."""
+    require_hip("geomBuffer must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path", geomBuffer)
+    ext = _pybind()
+    if ext is not None:
+        return _call_ext(ext.layer_alpha_forward, int(P), int(R), int(image_height), int(image_width), int(split),
+                         geomBuffer, binningBuffer, imageBuffer)
+    dev = geomBuffer.device
+    H, W = int(image_height), int(image_width)
+    alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    last = torch.empty((H, W), dtype=torch.int32, device=dev)
+    call("sgr_layer_alpha_forward", dev, int(P), int(R), W, H, int(split), _addr(geomBuffer), _addr(binningBuffer),
+         _addr(imageBuffer), alpha, last)
+    return alpha, last
+
+
+def layer_alpha_backward(R, image_height, image_width, split, means3D, scales, rotations, scale_modifier, cov3D_precomp,
+                         radii, geomBuffer, binningBuffer, imageBuffer, layer_alpha, layer_last, dL_dlayer_alpha, debug):
+    """sgr_layer_alpha_backward (include/sgr_object_alpha.h).  Returns (dL_dmeans3D [P, 3], dL_dopacity [P, 1],
+    dL_dscales [P, 3], dL_drotations [P, 4], dL_dcov3D [P, 6] or None when cov3D_precomp is absent); rows [0, split) are
+    zero."""
+    _dev_check(means3D, "means3D")
+    ext = _pybind()
+    e = torch.Tensor([])
+    z = lambda t: e if t is None else t
+    if ext is not None:
+        out = _call_ext(ext.layer_alpha_backward, int(R), int(image_height), int(image_width), int(split), means3D,
+                        z(scales), z(rotations), float(scale_modifier), z(cov3D_precomp), radii, geomBuffer, binningBuffer,
+                        imageBuffer, layer_alpha, layer_last, dL_dlayer_alpha, bool(debug))
+        return out[:4] + (out[4] if out[4].numel() else None,)
+    dev = means3D.device
+    P = means3D.size(0)
+    with_cov = cov3D_precomp is not None and cov3D_precomp.numel() != 0
+    mk = (lambda *shape: _alloc.empty(shape, torch.float32, dev)) if P else (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
+    dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations = mk(P, 3), mk(P, 1), mk(P, 3), mk(P, 4)
+    dL_dcov3D = mk(P, 6) if with_cov else None
+    if P:
+        scratch = _Grow(dev)
+        p = _Inputs()
+        if layer_last.dtype != torch.int32:
+            raise SgrError("layer_last must be int32")
+        call("sgr_layer_alpha_backward", dev, P, int(R), int(image_width), int(image_height), int(split),
+             p(means3D, "means3D"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
+             p(cov3D_precomp, "cov3D_precomp"), _addr(radii.contiguous()), _addr(geomBuffer), _addr(binningBuffer),
+             _addr(imageBuffer), p(layer_alpha, "layer_alpha"), _addr(layer_last.contiguous()),
+             p(dL_dlayer_alpha, "dL_dlayer_alpha"), dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
+             scratch.cb, None, int(bool(debug)))
+    return dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D
+
+
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                  dL_dout_alpha, dL_dout_semantic, sh, degree, campos, geomBuffer, R, binningBuffer,

@@ -35,6 +35,8 @@ def _signatures():
         "sgr_forward": (i, fwd),
         "sgr_forward_ex": (i, fwd + [vp]),
         "sgr_forward_layers": (i, fwd + [vp]),
+        "sgr_layer_alpha_forward": (i, [i, i, i, i, i, vp, vp, vp, vp, vp, vp]),
+        "sgr_layer_alpha_backward": (i, [i, i, i, i, i, vp, vp, f, vp, vp, vp] + [vp] * 11 + [ALLOC_FN, vp, i, vp]),
         "sgr_backward": (i, bwd),
         "sgr_backward_ex": (i, bwd + [vp]),
         "sgr_mark_visible": (i, [i, vp, vp, vp, vp, vp]),

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsgr_hip.so")
-SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_blend_fwd.hip", "sgr_blend_layers.hip", "sgr_blend_bwd.hip", "sgr_gauss_bwd.hip", "sgr_gauss_bwd_strict.hip",
+SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_blend_fwd.hip", "sgr_blend_layers.hip", "sgr_object_alpha.hip", "sgr_blend_bwd.hip", "sgr_gauss_bwd.hip", "sgr_gauss_bwd_strict.hip",
            "sgr_knn.hip", "sgr_multiview.hip", "sgr_scene.hip", "sgr_loss.hip", "sgr_densify.hip", "sgr_densify_scene.hip", "sgr_texture.hip", "sgr_sky.hip", "sgr_optim.hip", "sgr_actor_pose.hip", "sgr_api.hip"]
 # Designs that were built, measured slower on MI355X and kept as A/B records: the scalar-walk blend
 # backward (its own file), and -- behind `#if SGR_WITH_VARIANTS` inside the files above -- the transposed-accumulation
@@ -27,7 +27,7 @@ HEADERS = ["sgr_common.h", "sgr_math.h", "sgr_reduce.h", "sgr_cube.h", "sgr_dens
            os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h"),
-           os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h")]
+           os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_object_alpha.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 ops into v_pk_* and pays for it with v_mov
 # shuffles; measured on MI355X it costs 6 % in the blend backward and 7 % in the per-Gaussian backward.
 # -mllvm -enable-post-misched=0: without the post-RA machine scheduler the blend kernels keep the order they were
@@ -119,7 +119,7 @@ def build_pybind(force: bool = False, verbose: bool = False) -> str:
     src = os.path.join(CSRC, "ext.cpp")
     suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     out = os.path.join(HERE, EXT_NAME + suffix)
-    deps = [src, os.path.join(HERE, "..", "include", "sgr.h")]
+    deps = [src, os.path.join(HERE, "..", "include", "sgr.h"), os.path.join(HERE, "..", "include", "sgr_object_alpha.h")]
     if not force and os.path.exists(out) and os.path.getmtime(out) > _newest(deps) and os.path.getmtime(out) > os.path.getmtime(LIB):
         return out
     torch_lib = os.path.abspath(os.path.join(os.path.dirname(__import__("torch").__file__), "lib"))

@@ -15,6 +15,7 @@
 #include <tuple>
 
 #include "../../include/sgr.h"
+#include "../../include/sgr_object_alpha.h"
 
 namespace {
 
@@ -147,6 +148,61 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                            dL_dsemantic);
 }
 
+// (extension) sgr_layer_alpha_forward (include/sgr_object_alpha.h): the alpha image of Gaussians [split, P) alone, from the
+// buffers of a rasterize_gaussians call of the same frame -> (alpha [1, H, W], last [H, W] int32)
+std::tuple<torch::Tensor, torch::Tensor> layer_alpha_forward(const int P, const int R, const int image_height,
+                                                             const int image_width, const int split,
+                                                             const torch::Tensor& geomBuffer,
+                                                             const torch::Tensor& binningBuffer,
+                                                             const torch::Tensor& imageBuffer) {
+    TORCH_CHECK(geomBuffer.is_cuda(), "geomBuffer must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path");
+    c10::DeviceGuard guard(geomBuffer.device());
+    const int H = image_height, W = image_width;
+    torch::Tensor alpha = torch::empty({1, H, W}, geomBuffer.options().dtype(torch::kFloat32));
+    torch::Tensor last = torch::empty({H, W}, geomBuffer.options().dtype(torch::kInt32));
+    auto bytes = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<const char*>(t.data_ptr()) : nullptr; };
+    check(sgr_layer_alpha_forward(P, R, W, H, split, bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
+                                  alpha.data_ptr<float>(), reinterpret_cast<uint32_t*>(last.data_ptr<int>()),
+                                  stream_of(geomBuffer)));
+    return std::make_tuple(alpha, last);
+}
+
+// (extension) sgr_layer_alpha_backward -> (dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D); dL_dcov3D is an
+// empty tensor when cov3D_precomp is absent
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+layer_alpha_backward(const int R, const int image_height, const int image_width, const int split,
+                     const torch::Tensor& means3D, const torch::Tensor& scales, const torch::Tensor& rotations,
+                     const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& radii,
+                     const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                     const torch::Tensor& layer_alpha, const torch::Tensor& layer_last,
+                     const torch::Tensor& dL_dlayer_alpha, const bool debug) {
+    TORCH_CHECK(means3D.is_cuda(), "means3D must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path");
+    TORCH_CHECK(layer_last.scalar_type() == torch::kInt32, "layer_last must be int32");
+    c10::DeviceGuard guard(means3D.device());
+    const int P = means3D.size(0);
+    auto fo = means3D.options().dtype(torch::kFloat32);
+    const bool with_cov = cov3D_precomp.defined() && cov3D_precomp.numel() != 0;
+    auto mk = [&](std::initializer_list<int64_t> shape) { return P ? torch::empty(shape, fo) : torch::zeros(shape, fo); };
+    torch::Tensor dL_dmeans3D = mk({P, 3}), dL_dopacity = mk({P, 1}), dL_dscales = mk({P, 3}), dL_drotations = mk({P, 4});
+    torch::Tensor dL_dcov3D = with_cov ? mk({P, 6}) : torch::empty({0}, fo);
+    if (P != 0) {
+        torch::Tensor scratch = torch::empty({0}, means3D.options().dtype(torch::kByte));
+        auto c = [](const torch::Tensor& t) { return t.defined() && t.numel() ? t.contiguous() : t; };
+        const torch::Tensor m3 = c(means3D), sc = c(scales), rot = c(rotations), cov = c(cov3D_precomp), rd = c(radii),
+                            la = c(layer_alpha), ll = c(layer_last), ga = c(dL_dlayer_alpha);
+        auto bytes = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; };
+        check(sgr_layer_alpha_backward(P, R, image_width, image_height, split, fp(m3), fp(sc), scale_modifier, fp(rot), fp(cov),
+                                       rd.numel() ? rd.data_ptr<int>() : nullptr, bytes(geomBuffer), bytes(binningBuffer),
+                                       bytes(imageBuffer), fp(la),
+                                       ll.numel() ? reinterpret_cast<const uint32_t*>(ll.data_ptr<int>()) : nullptr, fp(ga),
+                                       dL_dmeans3D.data_ptr<float>(), dL_dopacity.data_ptr<float>(),
+                                       dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
+                                       with_cov ? dL_dcov3D.data_ptr<float>() : nullptr, grow, &scratch, debug ? 1 : 0,
+                                       stream_of(means3D)));
+    }
+    return std::make_tuple(dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D);
+}
+
 // markVisible (rasterize_points.cu:222-241)
 torch::Tensor mark_visible(torch::Tensor& means3D, torch::Tensor& viewmatrix, torch::Tensor& projmatrix) {
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a HIP (cuda) tensor: street_gaussians_amd has no CPU path");
@@ -213,6 +269,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("dL_dout_alpha"), py::arg("dL_dout_semantic"),
           py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"),
           py::arg("imageBuffer"), py::arg("alphas"), py::arg("semantics"), py::arg("debug"), py::arg("skip_cov3d_grad") = false);
+    m.def("layer_alpha_forward", &layer_alpha_forward);
+    m.def("layer_alpha_backward", &layer_alpha_backward);
     m.def("mark_visible", &mark_visible);
     m.def("rasterize_gaussians_filter", &rasterize_gaussians_filter);
     m.def("distCUDA2", &distCUDA2);

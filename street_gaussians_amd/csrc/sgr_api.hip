@@ -14,6 +14,7 @@
 
 #include "../../include/sgr.h"
 #include "../../include/sgr_layers.h"
+#include "../../include/sgr_object_alpha.h"
 #include "sgr_math.h"
 
 // launchers implemented in the kernel translation units
@@ -39,6 +40,12 @@ void sgr_launch_blend_layers(bool exact, int gx, int gy, const uint2* ranges, co
                              const float4* rec, int split, int P, const float* bg, int clamp, float* const color[2],
                              float* const alpha[2], hipStream_t s);
 void sgr_launch_layers_fill(int W, int H, const float* bg, int clamp, float* const color[2], float* const alpha[2], hipStream_t s);
+void sgr_launch_object_alpha_fwd(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
+                                 const float4* rec, int split, float* out_alpha, uint32_t* out_last, hipStream_t s);
+void sgr_launch_object_alpha_bwd(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
+                                 const float4* rec, const uint32_t* u0, const uint64_t* tmask, int split, const float* layer_alpha,
+                                 const uint32_t* layer_last, const float* dL_dlayer_alpha, float* partials, int row_stride,
+                                 uint8_t* touched, uint32_t row_limit, hipStream_t s);
 int sgr_partial_row_stride(int S);
 void sgr_launch_blend_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W,
                           int H, int S, const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* semantics, const float* alphas,
@@ -415,7 +422,7 @@ SgrFlagBlock sgr_acquire_flag_block() {
 extern "C" {
 
 const char* sgr_last_error(void) { return g_err.c_str(); }
-int sgr_version(void) { return 104; }  // 104: sgr_forward_ex, sgr_backward_extras gained skip_cov3d_grad; 103: sgr_forward_layers (include/sgr_layers.h); 102: sgr_backward_extras gained masked_color_out + skip_sh_grad (101: color_ready_event + rows)
+int sgr_version(void) { return 105; }  // 105: sgr_layer_alpha_forward / _backward (include/sgr_object_alpha.h); 104: sgr_forward_ex, sgr_backward_extras gained skip_cov3d_grad; 103: sgr_forward_layers (include/sgr_layers.h); 102: sgr_backward_extras gained masked_color_out + skip_sh_grad (101: color_ready_event + rows)
 
 size_t sgr_geometry_bytes(int P) {
     return sgr_required([&](char* b, char** e) { sgr_geom_carve(b, (size_t)P, e); });
@@ -909,6 +916,107 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
     prof_end(stream);
     if (ev_failed) return fail(SGR_E_HIP, "hipEventRecord(color_ready_event) failed: is it a valid event of this device?");
     if (touched && odd_set) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
+    return 0;
+}
+
+// ---- the object-alpha head (include/sgr_object_alpha.h, sgr_object_alpha.hip) -------------------------------------------
+// argument errors common to the two calls; 0 = fine
+static int layer_alpha_check(int P, int R, int width, int height, int split, const void* geom, const void* binning,
+                             const void* image) {
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(SGR_E_INVALID, "layer alpha: P, R must not be negative, width and height positive");
+    if (split < 0 || split > P) return fail(SGR_E_INVALID, "layer alpha: split must lie in [0, P]");
+    const int gx = (width + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (height + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
+    if (gx > SGR_MAX_GRID_DIM || gy > SGR_MAX_GRID_DIM) return fail(SGR_E_INVALID, "layer alpha: image larger than 16368 px per side is not supported");
+    if (P > 0 && (!geom || !image || (R > 0 && !binning)))
+        return fail(SGR_E_INVALID, "layer alpha: the buffers produced by sgr_forward are required");
+    return 0;
+}
+
+int sgr_layer_alpha_forward(int P, int R, int width, int height, int split, const char* geom_buffer,
+                            const char* binning_buffer, const char* image_buffer, float* out_alpha, uint32_t* out_last,
+                            void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (const int rc = layer_alpha_check(P, R, width, height, split, geom_buffer, binning_buffer, image_buffer)) return rc;
+    if (!out_alpha || !out_last) return fail(SGR_E_INVALID, "layer alpha: out_alpha and out_last are required");
+    const Switches sw = resolve_switches();
+    const int W = width, H = height;
+    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
+    const size_t N = (size_t)W * H, T = (size_t)gx * gy;
+    if (P == 0 || split == P || R == 0) {  // an empty layer (or an empty frame): zeros without a walk
+        SGR_HIP(hipMemsetAsync(out_alpha, 0, N * sizeof(float), stream));
+        SGR_HIP(hipMemsetAsync(out_last, 0, N * sizeof(uint32_t), stream));
+        return 0;
+    }
+    const SgrGeomView gv = sgr_geom_carve(const_cast<char*>(geom_buffer), (size_t)P);
+    const SgrImgView iv = sgr_img_carve(const_cast<char*>(image_buffer), N, T);
+    const SgrBinView bv = sgr_bin_carve(const_cast<char*>(binning_buffer), (size_t)R);
+    // (-gy: the tiles in the frame's order, the flag word behind the ranges -- as the backwards walk them)
+    sgr_launch_object_alpha_fwd(sw.exact, gx, -gy, iv.ranges, bv.vals[list_index(W, H, sw)], W, H, gv.rec, split, out_alpha,
+                                out_last, stream);
+    SGR_STAGE("object_alpha_fwd");
+    return 0;
+}
+
+int sgr_layer_alpha_backward(int P, int R, int width, int height, int split, const float* means3D, const float* scales,
+                             float scale_modifier, const float* rotations, const float* cov3D_precomp, const int* radii,
+                             char* geom_buffer, char* binning_buffer, char* image_buffer, const float* layer_alpha,
+                             const uint32_t* layer_last, const float* dL_dlayer_alpha, float* dL_dmean3D,
+                             float* dL_dopacity, float* dL_dscale, float* dL_drot, float* dL_dcov3D, sgr_alloc_fn scratch,
+                             void* scratch_user, int debug, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    (void)scale_modifier;  // already resident in the geometry buffer's camera block
+    if (const int rc = layer_alpha_check(P, R, width, height, split, geom_buffer, binning_buffer, image_buffer)) return rc;
+    if (P == 0) return 0;
+    if (!means3D || !layer_alpha || !layer_last || !dL_dlayer_alpha)
+        return fail(SGR_E_INVALID, "layer alpha: means3D, layer_alpha, layer_last and dL_dlayer_alpha are required");
+    if (((scales == nullptr) || (rotations == nullptr)) == (cov3D_precomp == nullptr))
+        return fail(SGR_E_INVALID, "layer alpha: provide exactly one of scales+rotations / cov3D_precomp");
+    if (!dL_dmean3D || !dL_dopacity || !dL_dscale || !dL_drot)
+        return fail(SGR_E_INVALID, "layer alpha: dL_dmean3D, dL_dopacity, dL_dscale and dL_drot are required");
+    if (!scratch) return fail(SGR_E_INVALID, "layer alpha: the scratch callback is required");
+    const Switches sw = resolve_switches();
+    const int W = width, H = height;
+    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
+    const size_t N = (size_t)W * H, T = (size_t)gx * gy;
+    const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
+    const SgrImgView iv = sgr_img_carve(image_buffer, N, T);
+    const int* radii_ptr = radii ? radii : gv.internal_radii;
+    const int stride = sgr_partial_row_stride(0);
+    // scratch = [P float4: conic + depth terms between the two per-Gaussian stages][R partial rows][the two outputs of the
+    // row sum this head has no receiver for: dL/dmean2D and dL/dcolour, 3 P floats each]
+    const size_t cd_bytes = sgr_align_up((size_t)P * sizeof(float4), 256);
+    const size_t row_bytes = sgr_align_up((size_t)R * stride * sizeof(float), 256);
+    const size_t p3_bytes = sgr_align_up((size_t)P * 3 * sizeof(float), 256);
+    char* sbase = scratch(cd_bytes + row_bytes + 2 * p3_bytes, scratch_user);
+    if (!sbase) return fail(SGR_E_ALLOC, "layer alpha: backward scratch allocation failed");
+    float4* cd = reinterpret_cast<float4*>(sbase);
+    float* partials = reinterpret_cast<float*>(sbase + cd_bytes);
+    float* dL_dmean2D = reinterpret_cast<float*>(sbase + cd_bytes + row_bytes);
+    float* dL_dcolor = reinterpret_cast<float*>(sbase + cd_bytes + row_bytes + p3_bytes);
+    // The rows this walk writes are not the set the composite's backward marks (behind an opaque wall it writes rows the
+    // composite never does; in front of one, fewer): the bytes are cleared before and after, like sgr_backward_ex does for
+    // its own odd sets, so that either backward finds them as the forward left them.
+    uint8_t* touched = nullptr;
+    if (R > 0) {
+        const SgrBinView bv = sgr_bin_carve(binning_buffer, (size_t)R);
+        touched = bv.touched;
+        SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
+        if (split < P) {
+            sgr_launch_object_alpha_bwd(sw.exact, gx, -gy, iv.ranges, bv.vals[list_index(W, H, sw)], W, H, gv.rec, gv.u0, gv.tmask,
+                                        split, layer_alpha, layer_last, dL_dlayer_alpha, partials, stride, touched, (uint32_t)R,
+                                        stream);
+            SGR_STAGE("object_alpha_bwd");
+        }
+    }
+    // S = 0, no SH (neither a read of the rows nor of the stored colour Jacobian, no dL/dSH), an empty statistics sink, no
+    // colour event, no masked colour output
+    (sw.exact ? sgr_launch_gauss_bwd_strict : sgr_launch_gauss_bwd)(
+        P, 0, 0, 0, means3D, radii_ptr, nullptr, scales, rotations, cov3D_precomp, cam_slot(gv), gv, partials, stride, touched, cd,
+        dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, nullptr, dL_dscale, dL_drot, nullptr, SgrStatSink(), 0,
+        sw.exact ? 1 : 0, W, H, nullptr, sw.rs_wave ? 1 : 0, (uint32_t)R, nullptr, 1, dL_dcov3D ? 0 : 1, stream);
+    SGR_STAGE("object_alpha gauss_bwd");
+    if (touched) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
     return 0;
 }
 

@@ -87,7 +87,7 @@ def _color_event(device):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, stats=None, grad_mode=True):
+                raster_settings, stats=None, grad_mode=True, frame=None):
         # argument order of the native entry point (reference __init__.py:62-83)
         args = (raster_settings.bg, means3D, colors_precomp, semantics, opacities, scales, rotations,
                 raster_settings.scale_modifier, cov3Ds_precomp, raster_settings.viewmatrix, raster_settings.projmatrix,
@@ -119,6 +119,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.opacities_key = (opacities.data_ptr(), tuple(opacities.shape)) if isinstance(opacities, torch.Tensor) else None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                               binningBuffer, imgBuffer, alpha, semantics)
+        if frame is not None:
+            # (extension) the frame's finished buffers, handed to a second head over the same lists
+            # (GaussianRasterizer.forward_with_object_alpha); nothing of this call changes
+            frame.update(num_rendered=num_rendered, radii=radii, geomBuffer=geomBuffer, binningBuffer=binningBuffer,
+                         imgBuffer=imgBuffer)
         ctx.mark_non_differentiable(radii)
         # autograd would otherwise hand the backward a zero-filled gradient for EVERY output it has none for, radii
         # included (a P-element fill kernel per step); the backward below fills in only the ones it reads
@@ -190,9 +195,43 @@ class _RasterizeGaussians(torch.autograd.Function):
         # autograd (None / empty placeholders) are dropped instead of returned and ignored
         need = ctx.needs_input_grad
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_semantics, grad_opacities,
-                 grad_scales, grad_rotations, grad_cov3Ds_precomp, None, None, None)
+                 grad_scales, grad_rotations, grad_cov3Ds_precomp, None, None, None, None)
         grads = tuple(g if (g is not None and need[i]) else None for i, g in enumerate(grads[:len(need)]))
-        return grads  # (one per argument apply() was given: stats and grad_mode are optional)
+        return grads  # (one per argument apply() was given: stats, grad_mode and frame are optional)
+
+
+class _ObjectAlpha(torch.autograd.Function):
+    """The object-alpha head (include/sgr_object_alpha.h): the alpha image of Gaussians [split, P) blended alone, over the
+    finished buffers of a _RasterizeGaussians forward of the same frame (``frame``).  A second autograd function on the same
+    input tensors, so autograd adds its gradients to the composite's.  It has no gradient for means2D, colours, SH or
+    semantics and never updates a statistics sink."""
+
+    @staticmethod
+    def forward(ctx, means3D, opacities, scales, rotations, cov3Ds_precomp, raster_settings, frame, split):
+        P = means3D.shape[0]
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        acc, last = _C.layer_alpha_forward(P, frame["num_rendered"], H, W, split, frame["geomBuffer"],
+                                           frame["binningBuffer"], frame["imgBuffer"])
+        ctx.raster_settings = raster_settings
+        ctx.num_rendered = frame["num_rendered"]
+        ctx.split = split
+        ctx.save_for_backward(means3D, scales, rotations, cov3Ds_precomp, frame["radii"], frame["geomBuffer"],
+                              frame["binningBuffer"], frame["imgBuffer"], acc, last)
+        ctx.set_materialize_grads(False)
+        return acc
+
+    @staticmethod
+    def backward(ctx, grad_acc):
+        need = ctx.needs_input_grad
+        if grad_acc is None:
+            return (None,) * 8
+        means3D, scales, rotations, cov3Ds_precomp, radii, geomBuffer, binningBuffer, imgBuffer, acc, last = ctx.saved_tensors
+        st = ctx.raster_settings
+        g_means3D, g_opacity, g_scales, g_rotations, g_cov3D = _C.layer_alpha_backward(
+            ctx.num_rendered, st.image_height, st.image_width, ctx.split, means3D, scales, rotations, st.scale_modifier,
+            cov3Ds_precomp, radii, geomBuffer, binningBuffer, imgBuffer, acc, last, grad_acc, st.debug)
+        grads = (g_means3D, g_opacity, g_scales, g_rotations, g_cov3D, None, None, None)
+        return tuple(g if (g is not None and need[i]) else None for i, g in enumerate(grads))
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -310,6 +349,48 @@ class GaussianRasterizer(nn.Module):
         num_rendered, color, depth, alpha, semantic, radii = out[:6]
         _LAST["num_rendered"] = num_rendered
         return color, radii, depth, alpha, semantic, LayerImages(*out[9:13])
+
+    def forward_with_object_alpha(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
+                                  rotations=None, cov3D_precomp=None, semantics=None, *, split):
+        """Extension (not in the reference): ``forward`` plus ``acc_object`` [1, H, W], the accumulated alpha of Gaussians
+        [split, P) blended alone -- what the reference's training loop gets from a second whole render, render_object
+        (train.py:114-122, lib/models/street_gaussian_renderer.py:58-72) -- from the frame's finished tile lists
+        (include/sgr_object_alpha.h).
+
+        Returns ``(color, radii, depth, alpha, semantics, acc_object)``.  The first five are ``forward``'s, bit for bit and
+        with its autograd behaviour (means2D.grad, ``stats_sink``, the backward sinks of multiview).  ``acc_object`` equals
+        ``forward``'s alpha over the subset alone and is differentiable with respect to rows [split, P) of means3D, opacities
+        and scales / rotations (or cov3D_precomp); autograd adds its gradients to the composite's.  It never touches
+        means2D, the statistics sink, colours or SH.  ``split`` outside [0, P] raises ValueError."""
+        raster_settings = self.raster_settings
+
+        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+        split = int(split)
+        P = means3D.shape[0]
+        if split < 0 or split > P:
+            raise ValueError(f"split must lie in [0, {P}], got {split}")
+
+        e = torch.Tensor([])
+        z = lambda t: e if t is None else t
+        shs, colors_precomp, scales, rotations, cov3D_precomp = z(shs), z(colors_precomp), z(scales), z(rotations), z(cov3D_precomp)
+        if semantics is None:
+            semantics = torch.zeros(P, 0, dtype=torch.float32, device=means3D.device)
+
+        frame = {}
+        color, radii, depth, alpha, semantic = _RasterizeGaussians.apply(
+            means3D, means2D, shs, colors_precomp, semantics, opacities, scales, rotations, cov3D_precomp, raster_settings,
+            self.stats_sink, torch.is_grad_enabled(), frame)
+        if P == 0 or split == P:  # no objects: zeros, no launch, nothing to differentiate
+            acc_object = torch.zeros_like(alpha)
+        else:
+            acc_object = _ObjectAlpha.apply(means3D, opacities, scales, rotations, cov3D_precomp, raster_settings, frame, split)
+        return color, radii, depth, alpha, semantic, acc_object
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
         raster_settings = self.raster_settings
