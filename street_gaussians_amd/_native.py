@@ -86,6 +86,13 @@ def _signatures():
         "sgr_lidar_work_bytes": (sz, [i]),
         "sgr_lidar_depth_forward": (i, [i, vp, vp, vp, vp, d, vp, vp, vp]),
         "sgr_lidar_depth_backward": (i, [i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_frame_loss_saved_bytes": (sz, [i, i, i]),
+        "sgr_frame_loss_workspace_floats": (sz, [i, i, i]),
+        "sgr_frame_loss_finish_span": (i, []),
+        "sgr_frame_loss_forward": (i, [i, i, i, vp, vp, vp, vp, vp]),
+        "sgr_frame_loss_backward": (i, [i, i, i] + [vp] * 10),
+        "sgr_mse_workspace_floats": (sz, [i, i, i]),
+        "sgr_mse_forward": (i, [i, i, i, vp, vp, vp, vp, vp, vp]),
         "sgr_densify_work_bytes": (sz, [i]),
         "sgr_densify_plan": (i, [i, vp, vp, vp, vp, vp, vp, i64p, vp]),
         "sgr_densify_map": (i, [i, vp, vp, vp, vp, vp, vp]),

@@ -12,31 +12,7 @@
 
 #include "../../include/sgr_loss.h"
 #include "sgr_common.h"
-
-#define SGR_LS_T 16           // output tile edge
-#define SGR_LS_R 5            // window radius (window_size 11)
-#define SGR_LS_IN (SGR_LS_T + 2 * SGR_LS_R)  // 26
-
-struct SgrGauss11 { float w[11]; };
-// gaussian(11, 1.5) of loss_utils.py:70-72, evaluated like the reference: exp() in double, float32 tensor, / sum
-static SgrGauss11 make_window() {
-    SgrGauss11 g;
-    float v[11], s = 0.f;
-    for (int x = 0; x < 11; x++) {
-        v[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
-        s += v[x];
-    }
-    for (int x = 0; x < 11; x++) g.w[x] = v[x] / s;
-    return g;
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float* lds4) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-}
+#include "sgr_loss_internal.h"  // the window, tile geometry, block sum and per-pixel terms shared with sgr_frame_loss.hip
 
 template <bool WITH_PARTIALS>
 __global__ void __launch_bounds__(256)
@@ -208,18 +184,13 @@ sgr_l1_bwd_kernel(int C, size_t plane, const float* __restrict__ a, const float*
 }
 
 // ---- accumulation terms (train.py:106-121) --------------------------------------------------------------------------
-__device__ __forceinline__ float bce_term(int mode, float a, bool m) {
-    if (mode == SGR_BCE_SKY) return m ? -logf(1.0f - a) : -logf(a);
-    return m ? -(a * logf(a) + (1.0f - a) * logf(1.0f - a)) : -logf(1.0f - a);
-}
 __global__ void __launch_bounds__(256)
 sgr_bce_fwd_kernel(int n, int mode, const float* __restrict__ acc, const uint8_t* __restrict__ mask,
                    float* __restrict__ sums) {
     __shared__ float lds4[4];
     float s = 0.f;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)n; i += (size_t)gridDim.x * 256) {
-        const float a = fminf(fmaxf(acc[i], 1e-6f), 1.0f - 1e-6f);  // torch.clamp(acc, min=1e-6, max=1.-1e-6)
-        s += bce_term(mode, a, mask && mask[i]);
+        s += bce_term(mode, bce_clamp(acc[i]), mask && mask[i]);
     }
     const float t = block_sum_256(s, lds4);
     if (threadIdx.x == 0) sums[blockIdx.x] = t;
@@ -231,32 +202,12 @@ sgr_bce_bwd_kernel(int n, int mode, const float* __restrict__ acc, const uint8_t
     if (i >= (size_t)n) return;
     const float x = acc[i];
     float g = 0.f;
-    if (x >= 1e-6f && x <= 1.0f - 1e-6f) {  // clamp passes the gradient on [min, max]
-        const bool m = mask && mask[i];
-        if (mode == SGR_BCE_SKY) g = m ? 1.0f / (1.0f - x) : -1.0f / x;
-        else g = m ? (logf(1.0f - x) - logf(x)) : 1.0f / (1.0f - x);
-        g *= upstream[0] / (float)n;
-    }
+    if (bce_clamp_passes(x)) g = bce_grad(mode, x, mask && mask[i]) * (upstream[0] / (float)n);
     dacc[i] = g;
 }
 
 // ---- LiDAR depth term with top-95 % selection (train.py:124-131) ---------------------------------------------------
-struct LdWork {
-    uint32_t* key;    // [n] float bits of the error (>= 0, so unsigned order == float order); 0xffffffff = not selected
-    uint32_t* hist;   // [4][256]
-    uint32_t* state;  // [0] count  [1] k  [2] prefix  [3] k remaining  [4] count below threshold  [5] ties
-    float* sums;      // [SGR_L1_BLOCKS]
-};
-#define SGR_L1_BLOCKS_ 1024
-static LdWork ld_carve(char* base, size_t n) {
-    LdWork w;
-    char* p = base;
-    sgr_carve(p, w.key, n ? n : 1);
-    sgr_carve(p, w.hist, 4 * 256);
-    sgr_carve(p, w.state, 16);
-    sgr_carve(p, w.sums, SGR_L1_BLOCKS_);
-    return w;
-}
+// (LdWork, its carve and the per-pixel key / gradient: sgr_loss_internal.h)
 __global__ void __launch_bounds__(256)
 sgr_lidar_err_kernel(int n, const float* __restrict__ depth, const float* __restrict__ acc, const float* __restrict__ lidar,
                      const uint8_t* __restrict__ mask, LdWork w) {
@@ -266,8 +217,7 @@ sgr_lidar_err_kernel(int n, const float* __restrict__ depth, const float* __rest
         const float l = lidar[i];
         uint32_t key = 0xffffffffu;
         if (l > 0.f && (!mask || mask[i])) {  // depth_mask = (lidar_depth > 0) & mask
-            const float e = fabsf(depth[i] / (acc[i] + 1e-10f) - l);
-            key = (e == e) ? __float_as_uint(e) : 0x7fc00000u;  // NaN sorts last among the selected, like topk
+            key = lidar_key(depth[i], acc[i], l);
             c++;
         }
         w.key[i] = key;
@@ -353,24 +303,22 @@ sgr_lidar_bwd_kernel(int n, const float* __restrict__ depth, const float* __rest
                      float* __restrict__ ddepth, float* __restrict__ dacc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)n) return;
-    const uint32_t key = w.key[i], t = __float_as_uint(out[2]);
-    float wgt = 0.f;
-    if (out[1] > 0.f && key != 0xffffffffu) wgt = key < t ? 1.0f : (key == t ? out[3] : 0.f);
-    float gd = 0.f, ga = 0.f;
-    if (wgt > 0.f) {
-        const float den = acc[i] + 1e-10f, diff = depth[i] / den - lidar[i];
-        const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-        const float g = upstream[0] * wgt * sgn / out[1];
-        gd = g / den;
-        ga = -g * depth[i] / (den * den);
-    }
+    float gd, ga;
+    lidar_grad(w.key[i], out, depth[i], acc[i], lidar[i], upstream[0], gd, ga);
     ddepth[i] = gd;
     dacc[i] = ga;
 }
 
-static inline dim3 tile_grid(int C, int H, int W) {
-    return dim3((W + SGR_LS_T - 1) / SGR_LS_T, (H + SGR_LS_T - 1) / SGR_LS_T, C);
+void sgr_lidar_select_launch(int n, const LdWork& w, double keep, float* out, hipStream_t stream) {
+    sgr_lidar_k_kernel<<<1, 1, 0, stream>>>(w, keep);
+    for (int pass = 3; pass >= 0; pass--) {
+        sgr_lidar_hist_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, pass, w);
+        sgr_lidar_select_kernel<<<1, 1, 0, stream>>>(pass, w);
+    }
+    sgr_lidar_sum_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, w);
+    sgr_lidar_final_kernel<<<1, 256, 0, stream>>>(w, out);
 }
+
 #define SGR_L1_BLOCKS 1024
 
 extern "C" {
@@ -471,9 +419,7 @@ int sgr_bce_backward(int n, int mode, const float* acc, const uint8_t* mask, con
 }
 
 size_t sgr_lidar_work_bytes(int n) {
-    char* base = (char*)4096;
-    LdWork w = ld_carve(base, (size_t)(n > 0 ? n : 1));
-    return (size_t)((char*)(w.sums + SGR_L1_BLOCKS_) - base) + 512;
+    return ld_work_bytes((size_t)(n > 0 ? n : 1));
 }
 
 int sgr_lidar_depth_forward(int n, const float* depth, const float* acc, const float* lidar_depth, const uint8_t* mask,
@@ -485,13 +431,7 @@ int sgr_lidar_depth_forward(int n, const float* depth, const float* acc, const f
     SGR_HIP(hipMemsetAsync(w.hist, 0, 4 * 256 * sizeof(uint32_t), stream));
     SGR_HIP(hipMemsetAsync(w.state, 0, 16 * sizeof(uint32_t), stream));
     sgr_lidar_err_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, depth, acc, lidar_depth, mask, w);
-    sgr_lidar_k_kernel<<<1, 1, 0, stream>>>(w, keep);
-    for (int pass = 3; pass >= 0; pass--) {
-        sgr_lidar_hist_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, pass, w);
-        sgr_lidar_select_kernel<<<1, 1, 0, stream>>>(pass, w);
-    }
-    sgr_lidar_sum_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, w);
-    sgr_lidar_final_kernel<<<1, 256, 0, stream>>>(w, out);
+    sgr_lidar_select_launch(n, w, keep, out, stream);
     SGR_HIP(hipGetLastError());
     return 0;
 }

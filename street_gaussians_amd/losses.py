@@ -4,10 +4,14 @@ of ~30 MIOpen / elementwise launches.  `train.py:100-104` keeps its two lines; o
 
     from street_gaussians_amd.losses import l1_loss, ssim
 
+`frame_loss` is all of `train.py:100-133` as one op (csrc/sgr_frame_loss.hip): one backward kernel for the four image
+gradients and one device tensor with every scalar the loop logs; `psnr` is loss_utils.py:61-78 without its host wait.
+
 Tensors must live on the GPU; there is no CPU implementation in the product."""
 from __future__ import annotations
 
-from typing import Optional
+import ctypes as C
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -233,3 +237,125 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_ave
     if a.shape != b.shape:
         raise RuntimeError("img1 and img2 must have the same shape")
     return _SSIM.apply(a, b.detach(), _prep_mask(mask, a.shape[1], a.shape[2]))
+
+
+# ---- every image-space term of a training step in one op (include/sgr_frame_loss.h) -----------------------------------
+class _FrameLossArgs(C.Structure):
+    """sgr_frame_loss_args: host memory read during the call."""
+    _fields_ = [(n, C.c_void_p) for n in ("image", "gt", "mask", "acc", "sky_mask", "acc_obj", "obj_bound", "depth",
+                                          "lidar_depth")] + \
+               [(n, C.c_float) for n in ("w_l1", "lambda_dssim", "lambda_sky", "sky_scale", "lambda_reg",
+                                         "lambda_depth_lidar")] + [("keep", C.c_double)]
+
+
+class FrameTerms(NamedTuple):
+    """The scalars train.py logs, as 0-dim views of ``values`` (8 floats on the device, include/sgr_frame_loss.h's
+    enum order): ``values.tolist()`` is the one read-back a logger needs.  A term that is off reads 0."""
+    l1: torch.Tensor
+    ssim: torch.Tensor
+    sky: torch.Tensor
+    obj: torch.Tensor
+    lidar: torch.Tensor
+    mse: torch.Tensor
+    psnr: torch.Tensor
+    loss: torch.Tensor
+    values: torch.Tensor
+
+
+class _FrameLoss(torch.autograd.Function):
+    """train.py:100-133 as one op: the map kernel, the LiDAR select and one finishing workgroup forward, ONE kernel
+    backward that writes dL/dimage, dL/dacc, dL/ddepth and dL/dacc_obj -- the four images the rasterizer's backward
+    reads -- for whichever of the inputs require grad."""
+
+    @staticmethod
+    def forward(ctx, image, acc, depth, acc_obj, gt, mask, sky_mask, obj_bound, lidar, scalars):
+        L = _native.lib()
+        Cc, H, W = image.shape
+        dev = image.device
+        tensors = (image, gt, mask, acc, sky_mask, acc_obj, obj_bound, depth, lidar)
+        args = _FrameLossArgs(*[None if t is None else t.data_ptr() for t in tensors], *scalars)
+        values = torch.empty(8, dtype=torch.float32, device=dev)
+        saved = torch.empty(L.sgr_frame_loss_saved_bytes(Cc, H, W), dtype=torch.uint8, device=dev)
+        ws = torch.empty(L.sgr_frame_loss_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
+        call("sgr_frame_loss_forward", dev, Cc, H, W, C.addressof(args), values, saved, ws)
+        ctx.save_for_backward(*tensors, saved, values)
+        ctx.scalars = scalars
+        ctx.mark_non_differentiable(values)
+        return values[7], values
+
+    @staticmethod
+    def backward(ctx, upstream, _unused):
+        *tensors, saved, values = ctx.saved_tensors
+        image, gt, mask, acc, sky_mask, acc_obj, obj_bound, depth, lidar = tensors
+        Cc, H, W = image.shape
+        dev = image.device
+        args = _FrameLossArgs(*[None if t is None else t.data_ptr() for t in tensors], *ctx.scalars)
+        up = upstream.reshape(1).to(torch.float32).contiguous()
+        need = ctx.needs_input_grad
+        grads = [torch.empty_like(t) if n and t is not None else None for t, n in zip((image, acc, depth, acc_obj), need)]
+        call("sgr_frame_loss_backward", dev, Cc, H, W, C.addressof(args), values, saved, None, up, grads[0],
+             grads[1], grads[2], grads[3])
+        return (*grads, None, None, None, None, None, None)
+
+
+def _pair(a, b, names):
+    if (a is None) != (b is None):
+        raise ValueError(f"{names[0]} and {names[1]} go together: pass both or neither")
+    return a is not None
+
+
+def frame_loss(image: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None, *, lambda_dssim: float = 0.2,
+               lambda_l1: float = 1.0, acc: Optional[torch.Tensor] = None, sky_mask: Optional[torch.Tensor] = None,
+               lambda_sky: float = 0.0, sky_scale: float = 1.0, acc_obj: Optional[torch.Tensor] = None,
+               obj_bound: Optional[torch.Tensor] = None, lambda_reg: float = 0.0, depth: Optional[torch.Tensor] = None,
+               lidar_depth: Optional[torch.Tensor] = None, lambda_depth_lidar: float = 0.0, keep: float = 0.95):
+    """train.py:100-133 in one op -> ``(loss, terms)``.
+
+    ``loss`` (0-dim) = ``(1 - lambda_dssim) * lambda_l1 * l1 + lambda_dssim * (1 - ssim)`` ``+ lambda_sky * sky``
+    (``acc`` with ``sky_mask``; ``sky_scale`` = ``lambda_sky_scale[cam]``) ``+ lambda_reg * obj`` (``acc_obj`` with
+    ``obj_bound``) ``+ lambda_depth_lidar * lidar`` (``depth`` with ``lidar_depth``; needs ``acc``, read unclamped).  A
+    term is on exactly when both tensors of its pair are passed.  It is differentiable with respect to ``image``,
+    ``acc``, ``depth`` and ``acc_obj``; ``loss.backward()`` is one kernel.  ``terms`` (FrameTerms) holds the scalars
+    train.py logs, plus mse and psnr, on the device: nothing here waits on the host."""
+    obj = _pair(acc_obj, obj_bound, ("acc_obj", "obj_bound"))
+    lidar = _pair(depth, lidar_depth, ("depth", "lidar_depth"))
+    if lidar and acc is None:
+        raise ValueError("depth and lidar_depth need acc: the LiDAR term divides by it")
+    # acc serves the sky term and the LiDAR term: alone it is half a pair
+    sky = sky_mask is not None if lidar and acc is not None else _pair(acc, sky_mask, ("acc", "sky_mask"))
+    a, b = _prep(image, "image"), _prep(gt, "gt")
+    if a.shape != b.shape:
+        raise RuntimeError("image and gt must have the same shape")
+    H, W = a.shape[1], a.shape[2]
+    like = a[0]
+    m = _prep_mask(mask, H, W)
+    t_acc = _flat(acc, "acc", like) if acc is not None else None
+    t_sky = _flat_mask(sky_mask, like) if sky else None
+    t_obj = _flat(acc_obj, "acc_obj", like) if obj else None
+    t_bound = _flat_mask(obj_bound, like) if obj else None
+    t_depth = _flat(depth, "depth", like) if lidar else None
+    t_lidar = _flat(lidar_depth, "lidar_depth", like).detach() if lidar else None
+    for name, t in (("mask", m), ("sky_mask", t_sky), ("obj_bound", t_bound)):
+        if t is not None:
+            require_hip(f"{name} must be a HIP (cuda) tensor: there is no CPU path", t)
+    scalars = ((1.0 - float(lambda_dssim)) * float(lambda_l1), float(lambda_dssim), float(lambda_sky), float(sky_scale),
+               float(lambda_reg), float(lambda_depth_lidar), float(keep))
+    loss, values = _FrameLoss.apply(a, t_acc, t_depth, t_obj, b.detach(), m, t_sky, t_bound, t_lidar, scalars)
+    return loss, FrameTerms(*values.unbind(0), values)
+
+
+def psnr(img1: torch.Tensor, img2: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """loss_utils.py:61-78: ``20 * log10(1 / sqrt(mean((img1 - img2) ** 2)))`` over the C values of the pixels selected
+    by mask (1, H, W), as a 0-dim tensor -- without the host wait of the reference's ``img[mask]``.  A metric, not a
+    loss: with grad mode on, an input that requires grad is refused instead of silently dropping its graph."""
+    if torch.is_grad_enabled() and (img1.requires_grad or img2.requires_grad):
+        raise ValueError("psnr is not differentiable: call it under torch.no_grad() or detach its inputs")
+    a, b = _prep(img1, "img1"), _prep(img2, "img2")
+    if a.shape != b.shape:
+        raise RuntimeError("img1 and img2 must have the same shape")
+    Cc, H, W = a.shape
+    dev = a.device
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = torch.empty(_native.lib().sgr_mse_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
+    call("sgr_mse_forward", dev, Cc, H, W, a, b, _prep_mask(mask, H, W), out, ws)
+    return out[1]
