@@ -48,10 +48,11 @@ enum {
     SGR_SKY_WHITE = 2, /* cfg.model.sky.white_background: fill 1 instead of 0 */
     SGR_SKY_CLAMP = 4, /* clamp the output to [0, 1] (cfg.mode != 'train') */
 };
-enum { SGR_SKY_SAVED = 0, SGR_SKY_SCRATCH = 1 };
+enum { SGR_SKY_SAVED = 0, SGR_SKY_SCRATCH = 1, SGR_SKY_SCRATCH_DEFERRED = 2 };
 
-/* bytes of the state the forward saves for the backward (part SGR_SKY_SAVED) or of the backward's scratch
- * (SGR_SKY_SCRATCH); 0 when the arguments are invalid.  C = 3 only. */
+/* bytes of the state the forward saves for the backward (part SGR_SKY_SAVED), of the backward's scratch
+ * (SGR_SKY_SCRATCH) or of the deferred backward's (SGR_SKY_SCRATCH_DEFERRED, include/sgr_sky_step.h: without the
+ * texture stages' buffers); 0 when the arguments are invalid.  C = 3 only. */
 size_t sgr_sky_workspace_bytes(int H, int W, int R, int C, int part);
 
 /* out [3, H, W]; saved: sgr_sky_workspace_bytes(.., SGR_SKY_SAVED), kept untouched until the backward. */

@@ -117,6 +117,10 @@ def _signatures():
         "sgr_sky_workspace_bytes": (sz, [i, i, i, i, i]),
         "sgr_sky_forward": (i, [i, i, i, i] + [vp] * 9 + [i, vp, vp, vp]),
         "sgr_sky_backward": (i, [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_sky_step_block_texels": (i, []),
+        "sgr_sky_step_workspace_bytes": (sz, [i, i, i]),
+        "sgr_sky_backward_deferred": (i, [i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgr_sky_adam_step": (i, [i, vp, vp, vp, vp, vp, f, f, f, d, d, vp]),
         "sgr_sky_test_rays": (i, [i, i, vp, vp, vp, vp, i, vp, vp, vp]),
         "sgr_actor_pose_forward": (i, [i, vp, i] + [vp] * 7 + [vp]),
         "sgr_actor_pose_backward_max_blocks": (i, []),

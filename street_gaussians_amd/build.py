@@ -23,11 +23,12 @@ SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_
 # `python tools/build_variant.py <name> -DSGR_WITH_VARIANTS=1` builds a library that contains them (sgr_has_variants() = 1),
 # and the tests of those paths run only against such a build.
 VARIANT_SOURCES = [os.path.join("variants", "sgr_blend_bwd_sw.hip")]
-HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_math.h", "sgr_reduce.h", "sgr_cube.h", "sgr_densify_rules.h", os.path.join("..", "..", "include", "sgr.h"),
+HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_math.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", os.path.join("..", "..", "include", "sgr.h"),
            os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h"),
-           os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_object_alpha.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h"), os.path.join("..", "..", "include", "sgr_frame_loss.h")]
+           os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_object_alpha.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h"), os.path.join("..", "..", "include", "sgr_frame_loss.h"),
+           os.path.join("..", "..", "include", "sgr_sky_step.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 ops into v_pk_* and pays for it with v_mov
 # shuffles; measured on MI355X it costs 6 % in the blend backward and 7 % in the per-Gaussian backward.
 # -mllvm -enable-post-misched=0: without the post-RA machine scheduler the blend kernels keep the order they were
@@ -38,7 +39,8 @@ HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_math.h", "sgr_reduce.h", 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fno-slp-vectorize", "-mllvm",
          "-enable-post-misched=0", "-mllvm", "-amdgpu-use-amdgpu-trackers=1", "-Wall", "-Wno-unused-function"]
 # sgr_optim.hip and sgr_actor_pose.hip declare their arithmetic op by op (include/sgr_optim.h, sgr_actor_pose.h): no fused
-# multiply-adds.
+# multiply-adds.  (sgr_texture.hip keeps the default: its Adam flavour of the gather takes the op-by-op arithmetic from
+# the pragma inside csrc/sgr_adam_math.h, and the gather's own roundings must stay the dense gather's.)
 PER_FILE_FLAGS = {"sgr_scan_sort.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "sgr_optim.hip": ["-ffp-contract=off"],
                   "sgr_actor_pose.hip": ["-ffp-contract=off"]}
 # sources that #include another source (a second instantiation under other names / other FP settings)

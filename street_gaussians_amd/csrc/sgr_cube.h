@@ -128,3 +128,17 @@ const SgrCubeSeam* sgr_cube_seam();
 // the count.  workspace: sgr_texture_cube_workspace_bytes(Bt, B, R, C, n).
 int sgr_texture_cube_backward_impl(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
                                    float* dL_dtex, void* workspace, const uint32_t* dev_n, hipStream_t stream);
+
+// The backward in two halves, for include/sgr_sky_step.h (C = 3, Bt = B = 1, a device-side count).  A block is
+// SGR_TX_STEP_BLOCK consecutive texels of the flat [6, R, R] index.
+#define SGR_TX_STEP_BLOCK 256
+// bytes of the deferred workspace (0 when the arguments are invalid)
+size_t sgr_texture_cube_deferred_bytes(int R, int64_t n);
+// key, sort, records and starts into `work`, and active[b] = 1 for every block that holds a tap texel of a sample
+int sgr_texture_cube_deferred_impl(int R, int64_t n, const float* uv, const float* dL_dout, void* work,
+                                   const uint32_t* dev_n, uint8_t* active, hipStream_t stream);
+// one launch over all blocks: the gather's sum of every texel of an active block, then adam1 on its three elements of
+// p / m / v; work == nullptr: no samples (g = 0)
+int sgr_texture_cube_adam_step_impl(int R, float* p, float* m, float* v, const void* work, const uint8_t* active,
+                                    float step_size, float bc2_sqrt, float eps, double beta1, double beta2,
+                                    hipStream_t stream);

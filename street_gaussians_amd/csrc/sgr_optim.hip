@@ -14,6 +14,7 @@
 #include <string>
 
 #include "../../include/sgr_optim.h"
+#include "sgr_adam_math.h"  // AdamConsts, adam1: the per-element arithmetic
 #include "sgr_common.h"
 
 #pragma clang fp contract(off)
@@ -26,19 +27,6 @@ static constexpr int SGR_ADAM_BLOCKS_PER_CU = 4;
 static constexpr int SGR_ADAM_CUS = 256;
 
 static_assert(sizeof(sgr_adam_chunk) == 32 && sizeof(sgr_adam_record) == 32, "table layout of include/sgr_optim.h");
-
-struct AdamConsts {
-    float c1, beta2, c2;
-};
-
-__device__ __forceinline__ void adam1(float& p, const float g, float& m, float& v, const AdamConsts k, const float ss,
-                                      const float bc2s, const float eps) {
-    m = m + k.c1 * (g - m);
-    v = v * k.beta2;
-    v = v + k.c2 * (g * g);
-    const float d = sqrtf(v) / bc2s + eps;
-    p = p + ss * (m / d);
-}
 
 __global__ void __launch_bounds__(SGR_ADAM_THREADS)
 sgr_adam_step_kernel(const sgr_adam_chunk* __restrict__ chunks, const sgr_adam_record* __restrict__ records,
@@ -135,7 +123,7 @@ int sgr_adam_step(const sgr_adam_chunk* chunks, int n_chunks, const sgr_adam_rec
     if (!chunks || !records || n_chunks == 0 || n_records == 0)
         return sgr_set_error(SGR_E_INVALID, "adam: n_spans > 0 needs the chunk and record tables");
     if (n_spans > (int64_t)INT32_MAX) return sgr_set_error(SGR_E_INVALID, "adam: more than 2^31 - 1 spans");
-    const AdamConsts k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2)};
+    const AdamConsts k = adam_consts(beta1, beta2);
     const int64_t cap = sgr_adam_max_blocks();
     const unsigned grid = (unsigned)(n_spans < cap ? n_spans : cap);
     sgr_adam_step_kernel<<<grid, SGR_ADAM_THREADS, (size_t)n_records * sizeof(int32_t), (hipStream_t)stream_>>>(

@@ -17,9 +17,13 @@
 //   5. affine  one block: the partials summed in double in a fixed order
 //   6. cube    the texture backward (sgr_texture_cube_backward_impl) on the compacted rays and upstreams, with the count
 //              read on the device: the sort never touches the non-sky pixels.
+// With the cube map's own optimiser (include/sgr_sky_step.h) stage 6 stops before its gather and leaves the sorted
+// records in a workspace (sgr_sky_backward_deferred); the gather then happens inside the Adam step, per texel of the
+// blocks that have ever been touched (sgr_sky_adam_step; the kernel is sgr_texture.hip's).
 #include <string>
 
 #include "../../include/sgr_sky.h"
+#include "../../include/sgr_sky_step.h"
 #include "../../include/sgr_texture.h"
 #include "sgr_common.h"
 #include "sgr_cube.h"
@@ -313,6 +317,8 @@ size_t sgr_sky_workspace_bytes(int H, int W, int R, int C, int part) {
         if (!tb) return 0;
         return sgr_required([&](char* base, char** end) { carve_scratch(base, HW, tb, end); });
     }
+    if (part == SGR_SKY_SCRATCH_DEFERRED)  // the texture stages work in the deferred workspace instead
+        return sgr_required([&](char* base, char** end) { carve_scratch(base, HW, 0, end); });
     return 0;
 }
 
@@ -335,16 +341,22 @@ int sgr_sky_forward(int H, int W, int R, int C, const float* rgb, const float* a
     return 0;
 }
 
-int sgr_sky_backward(int H, int W, int R, int C, const float* dL_dout, const float* rgb, const float* acc,
-                     const float* affine, int flags, const void* saved, float* dL_drgb, float* dL_dacc, float* dL_dcube,
-                     float* dL_daffine, void* scratch, void* stream_) {
+namespace {
+
+// Stages 4 and 5 of the backward, then stage 6 in one of its two forms: the whole texture backward into dL_dcube
+// (sgr_sky_backward), or without the gather, into the deferred workspace and the activity bytes
+// (sgr_sky_backward_deferred, include/sgr_sky_step.h).
+int backward(int H, int W, int R, int C, const float* dL_dout, const float* rgb, const float* acc, const float* affine,
+             int flags, const void* saved, float* dL_drgb, float* dL_dacc, float* dL_dcube, void* cube_work,
+             uint8_t* active, float* dL_daffine, void* scratch, hipStream_t s) {
     if (const int rc = check(H, W, R, C)) return rc;
-    if (!dL_dout || !rgb || !acc || !saved || !dL_drgb || !dL_dacc || !dL_dcube || !scratch || (affine && !dL_daffine))
+    const bool deferred = dL_dcube == nullptr;
+    if (!dL_dout || !rgb || !acc || !saved || !dL_drgb || !dL_dacc || !scratch || (affine && !dL_daffine) ||
+        (deferred && (!cube_work || !active)))
         return sgr_set_error(SGR_E_INVALID, "sky: a required pointer of the backward is missing");
-    hipStream_t s = (hipStream_t)stream_;
     const int64_t HW = (int64_t)H * W;
     const SkySaved v = carve_saved((char*)sgr_align_up((size_t)saved, 256), HW);
-    const SkyScratch w = carve_scratch((char*)sgr_align_up((size_t)scratch, 256), HW, tex_bytes(H, W, R));
+    const SkyScratch w = carve_scratch((char*)sgr_align_up((size_t)scratch, 256), HW, deferred ? 0 : tex_bytes(H, W, R));
     const SkyArgs a{H, W, R, HW, flags, rgb, acc, nullptr, nullptr, nullptr, nullptr, nullptr, affine, nullptr};
     const unsigned nb = blocks(HW);
     if (affine) {
@@ -354,7 +366,41 @@ int sgr_sky_backward(int H, int W, int R, int C, const float* dL_dout, const flo
         sgr_sky_bwd_kernel<false><<<nb, kBlock, 0, s>>>(a, dL_dout, v.flag, v.sky, dL_drgb, dL_dacc, w.up, w.part);
     }
     SGR_HIP(hipGetLastError());
+    if (deferred) return sgr_texture_cube_deferred_impl(R, HW, v.rays, w.up, cube_work, v.count, active, s);
     return sgr_texture_cube_backward_impl(1, 1, R, 3, HW, v.rays, w.up, dL_dcube, w.tex_work, v.count, s);
+}
+
+}  // namespace
+
+int sgr_sky_backward(int H, int W, int R, int C, const float* dL_dout, const float* rgb, const float* acc,
+                     const float* affine, int flags, const void* saved, float* dL_drgb, float* dL_dacc, float* dL_dcube,
+                     float* dL_daffine, void* scratch, void* stream_) {
+    if (!dL_dcube) return sgr_set_error(SGR_E_INVALID, "sky: a required pointer of the backward is missing");
+    return backward(H, W, R, C, dL_dout, rgb, acc, affine, flags, saved, dL_drgb, dL_dacc, dL_dcube, nullptr, nullptr,
+                    dL_daffine, scratch, (hipStream_t)stream_);
+}
+
+// ---- the cube map's optimiser step (include/sgr_sky_step.h) -----------------------------------------------------------
+int sgr_sky_step_block_texels(void) { return SGR_TX_STEP_BLOCK; }
+
+size_t sgr_sky_step_workspace_bytes(int H, int W, int R) {
+    if (check(H, W, R, 3) < 0) return 0;
+    return sgr_texture_cube_deferred_bytes(R, (int64_t)H * W);
+}
+
+int sgr_sky_backward_deferred(int H, int W, int R, int C, const float* dL_dout, const float* rgb, const float* acc,
+                              const float* affine, int flags, const void* saved, float* dL_drgb, float* dL_dacc,
+                              void* cube_work, uint8_t* active, float* dL_daffine, void* scratch, void* stream_) {
+    if (!cube_work || !active) return sgr_set_error(SGR_E_INVALID, "sky: cube_work and active are required");
+    return backward(H, W, R, C, dL_dout, rgb, acc, affine, flags, saved, dL_drgb, dL_dacc, nullptr, cube_work, active,
+                    dL_daffine, scratch, (hipStream_t)stream_);
+}
+
+int sgr_sky_adam_step(int R, float* cube, float* exp_avg, float* exp_avg_sq, const void* cube_work, const uint8_t* active,
+                      float step_size, float bc2_sqrt, float eps, double beta1, double beta2, void* stream_) {
+    if (R < 1) return sgr_set_error(SGR_E_INVALID, "sky: need R >= 1");
+    return sgr_texture_cube_adam_step_impl(R, cube, exp_avg, exp_avg_sq, cube_work, active, step_size, bc2_sqrt, eps,
+                                           beta1, beta2, (hipStream_t)stream_);
 }
 
 int sgr_sky_test_rays(int H, int W, const float* K, const float* w2c, const float* perturb_x, const float* perturb_y,

@@ -17,9 +17,16 @@
 //              lands on it; a fixed order, so the sums are bit-reproducible.
 // With a device-side sample count (sgr_texture_cube_backward_impl, the fused sky composite's compacted sky pixels), the
 // key, sort, starts and record stages stop at that count; their grids stay sized by the host's upper bound.
+//
+// The sky cube map's optimiser (include/sgr_sky_step.h) splits the backward in two: the deferred backward runs stages
+// 1-4 and marks the blocks of 256 texels its samples touch (sgr_texture_cube_deferred_impl); the step is stage 5's
+// kernel in a second flavour that applies Adam to the texel's sum instead of storing it, over the blocks ever marked
+// (sgr_texture_cube_adam_step_impl).  The flavour lives in this file so that the sum is compiled with the gather's
+// floating-point settings; the Adam arithmetic carries its own (sgr_adam_math.h).
 #include <string>
 
 #include "../../include/sgr_texture.h"
+#include "sgr_adam_math.h"
 #include "sgr_common.h"
 #include "sgr_cube.h"
 
@@ -123,10 +130,40 @@ __device__ __forceinline__ void tx_walk_cell(const TxGrid& g, const SgrCubeSeam&
     }
 }
 
-template <int CT>
+// The deferred backward (include/sgr_sky_step.h) leaves its key, sort, starts and record stages in a workspace that the
+// optimiser step reads later knowing only R: the first 256 bytes say where starts, rec and gs lie (byte offsets from
+// the workspace's aligned base), written on the device by the mark kernel.
+struct TxDeferredHeader {
+    uint64_t starts_off, rec_off, gs_off;
+};
+
+// The step flavour's arguments: the parameter and its moments [6 R R 3], the activity bytes (one per 256 texels), the
+// deferred workspace (nullptr: no samples) and Adam's scalars (sgr_adam_math.h).
+struct TxStep {
+    float *p, *m, *v;
+    const uint8_t* active;
+    const char* work;
+    AdamConsts k;
+    float ss, bc2s, eps;
+};
+
+// STEP = false: the gather, dL/dtex written once per element.  STEP = true (CT = 3, Bt = 1): the same sum in the same
+// order for the texels of the active blocks only, rounded to f32 once and consumed by adam1 in place of a stored
+// gradient; starts / rec / gs come from the deferred workspace's header, dtex is not used.
+template <int CT, bool STEP = false>
 __global__ void __launch_bounds__(256)
 sgr_texture_cube_gather_kernel(TxGrid g, SgrCubeSeam sm, int Crt, const uint32_t* __restrict__ starts,
-                               const float2* __restrict__ rec, const float* __restrict__ gs, float* __restrict__ dtex) {
+                               const float2* __restrict__ rec, const float* __restrict__ gs, float* __restrict__ dtex,
+                               TxStep st) {
+    if constexpr (STEP) {
+        if (!st.active[blockIdx.x]) return;  // one byte per workgroup, the same address in every lane
+        if (st.work) {
+            const TxDeferredHeader h = *reinterpret_cast<const TxDeferredHeader*>(st.work);
+            starts = reinterpret_cast<const uint32_t*>(st.work + h.starts_off);
+            rec = reinterpret_cast<const float2*>(st.work + h.rec_off);
+            gs = reinterpret_cast<const float*>(st.work + h.gs_off);
+        }
+    }
     const int C = CT > 0 ? CT : Crt;
     const int R = g.R;
     const int64_t per = 6 * (int64_t)R * R;
@@ -141,31 +178,74 @@ sgr_texture_cube_gather_kernel(TxGrid g, SgrCubeSeam sm, int Crt, const uint32_t
     double acc[CT > 0 ? CT : 1];  // double sums: a texel of a small map collects thousands of samples
 #pragma unroll
     for (int c = 0; c < (CT > 0 ? CT : 1); c++) acc[c] = 0.0;
-    // own cells: the texel is tap (x - x0, y - y0) of cells x0 in {x-1, x}, y0 in {y-1, y}
+    if (!STEP || st.work) {  // a step without a workspace: no samples, every gradient is +0
+        // own cells: the texel is tap (x - x0, y - y0) of cells x0 in {x-1, x}, y0 in {y-1, y}
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-        tx_walk_cell<CT>(g, sm, starts, rec, gs, C, ch, bt, f, x - 1 + (k & 1), y - 1 + (k >> 1), t, acc);
-    // a texel on edge e of its face is the outside tap of the two border cells of the neighbouring face next to it
-    for (int e = 0; e < 4; e++) {
-        const bool on = e == 0 ? x == 0 : e == 1 ? x == R - 1 : e == 2 ? y == 0 : y == R - 1;
-        if (!on) continue;
-        const int k = e < 2 ? y : x;
-        const int gf = sm.g[f][e], be = sm.back[f][e];
-        const int gc = sm.c0[f][e] * (R - 1) + sm.c1[f][e] * k, gr = sm.r0[f][e] * (R - 1) + sm.r1[f][e] * k;
-        for (int j = 0; j < 2; j++) {
-            int cx, cy;
-            if (be < 2) { cx = be == 0 ? -1 : R - 1; cy = gr - 1 + j; }
-            else { cy = be == 2 ? -1 : R - 1; cx = gc - 1 + j; }
-            tx_walk_cell<CT>(g, sm, starts, rec, gs, C, ch, bt, gf, cx, cy, t, acc);
+        for (int k = 0; k < 4; k++)
+            tx_walk_cell<CT>(g, sm, starts, rec, gs, C, ch, bt, f, x - 1 + (k & 1), y - 1 + (k >> 1), t, acc);
+        // a texel on edge e of its face is the outside tap of the two border cells of the neighbouring face next to it
+        for (int e = 0; e < 4; e++) {
+            const bool on = e == 0 ? x == 0 : e == 1 ? x == R - 1 : e == 2 ? y == 0 : y == R - 1;
+            if (!on) continue;
+            const int k = e < 2 ? y : x;
+            const int gf = sm.g[f][e], be = sm.back[f][e];
+            const int gc = sm.c0[f][e] * (R - 1) + sm.c1[f][e] * k, gr = sm.r0[f][e] * (R - 1) + sm.r1[f][e] * k;
+            for (int j = 0; j < 2; j++) {
+                int cx, cy;
+                if (be < 2) { cx = be == 0 ? -1 : R - 1; cy = gr - 1 + j; }
+                else { cy = be == 2 ? -1 : R - 1; cx = gc - 1 + j; }
+                tx_walk_cell<CT>(g, sm, starts, rec, gs, C, ch, bt, gf, cx, cy, t, acc);
+            }
         }
     }
-    if constexpr (CT > 0) {
+    if constexpr (STEP) {
+        static_assert(CT == 3, "the step flavour is the sky cube map's: three channels");
+        // the texel's 12 bytes of p, m and v, as the gather writes dtex: consecutive lanes, consecutive texels
+        float* __restrict__ p = st.p + tg * 3;
+        float* __restrict__ m = st.m + tg * 3;
+        float* __restrict__ v = st.v + tg * 3;
+        float P[3], M[3], V[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) { P[c] = p[c]; M[c] = m[c]; V[c] = v[c]; }
+#pragma unroll
+        for (int c = 0; c < 3; c++) adam1(P[c], (float)acc[c], M[c], V[c], st.k, st.ss, st.bc2s, st.eps);
+        // array by array: three neighbouring stores merge into one 12-byte store per lane
+#pragma unroll
+        for (int c = 0; c < 3; c++) p[c] = P[c];
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[c] = M[c];
+#pragma unroll
+        for (int c = 0; c < 3; c++) v[c] = V[c];
+    } else if constexpr (CT > 0) {
 #pragma unroll
         for (int c = 0; c < CT; c++) dtex[tg * CT + c] = (float)acc[c];
     } else {
         dtex[tg * C + ch] = (float)acc[0];
     }
 }
+
+// Deferred backward: the activity bytes of this backward's samples.  One lane per sorted position below the device
+// count: every texel that is a tap of the sample's cell (tx_cell_taps: seam taps on the neighbouring face included, a
+// missing corner tap not) marks its block of 256 texels.  Many lanes store the same byte value: plain stores.  Lane 0
+// also writes the workspace's header.
+__global__ void __launch_bounds__(256)
+sgr_texture_cube_mark_kernel(TxGrid g, SgrCubeSeam sm, const uint32_t* __restrict__ keys,
+                             const uint32_t* __restrict__ dev_n, uint8_t* __restrict__ active,
+                             TxDeferredHeader* __restrict__ hdr, TxDeferredHeader h) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *hdr = h;
+    if (i >= g.total || (dev_n && i >= (int64_t)*dev_n)) return;
+    const uint32_t key = keys[i];
+    if (key >= g.ncells) return;  // the sentinel: no footprint
+    const uint32_t E = (uint32_t)g.R + 1u;
+    const int x0 = (int)(key % E) - 1, y0 = (int)((key / E) % E) - 1, f = (int)(key / (E * E));
+    int64_t idx[4];
+    tx_cell_taps(sm, g.R, f, x0, y0, idx);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (idx[k] >= 0) active[idx[k] / SGR_TX_STEP_BLOCK] = 1;
+}
+static_assert(SGR_TX_STEP_BLOCK == 256, "one workgroup of the gather is one activity block");
 
 // ---- host -----------------------------------------------------------------------------------------------------------
 namespace {
@@ -317,15 +397,11 @@ int sgr_texture_cube_forward(int Bt, int B, int R, int C, int64_t n, const float
     return 0;
 }
 
-int sgr_texture_cube_backward_impl(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
-                                   float* dL_dtex, void* workspace, const uint32_t* dev_n, hipStream_t s) {
-    TxGrid g;
-    if (const int rc = check_args(Bt, B, R, C, n, g)) return rc;
-    if (!uv || !dL_dout || !dL_dtex || !workspace)
-        return sgr_set_error(SGR_E_INVALID, "texture: uv, dL_dout, dL_dtex and workspace are required");
-    if (dev_n && (Bt != 1 || B != 1)) return sgr_set_error(SGR_E_INVALID, "texture: a device-side count needs Bt = B = 1");
-    const SgrCubeSeam& sm = *sgr_cube_seam();
-    TxWork w = carve((char*)sgr_align_up((size_t)workspace, 256), g, C);
+namespace {
+
+// stages 1-4 of the backward: key, sort, records, starts; returns which of w.keys holds the sorted keys
+int sort_stages(const TxGrid& g, int C, const float* uv, const float* dL_dout, const TxWork& w, const uint32_t* dev_n,
+                hipStream_t s) {
     int cur = 0;
     if (g.total) {
         sgr_texture_cube_key_kernel<<<blocks(g.total), 256, 0, s>>>(g, uv, w.keys[0], dev_n);
@@ -338,11 +414,67 @@ int sgr_texture_cube_backward_impl(int Bt, int B, int R, int C, int64_t n, const
     }
     sgr_texture_cube_starts_kernel<<<blocks((uint64_t)g.ncells + 1), 256, 0, s>>>(g.ncells, (uint32_t)g.total, w.keys[cur],
                                                                                   w.starts, dev_n);
+    return cur;
+}
+
+constexpr size_t kDeferredHeaderBytes = 256;
+
+}  // namespace
+
+int sgr_texture_cube_backward_impl(int Bt, int B, int R, int C, int64_t n, const float* uv, const float* dL_dout,
+                                   float* dL_dtex, void* workspace, const uint32_t* dev_n, hipStream_t s) {
+    TxGrid g;
+    if (const int rc = check_args(Bt, B, R, C, n, g)) return rc;
+    if (!uv || !dL_dout || !dL_dtex || !workspace)
+        return sgr_set_error(SGR_E_INVALID, "texture: uv, dL_dout, dL_dtex and workspace are required");
+    if (dev_n && (Bt != 1 || B != 1)) return sgr_set_error(SGR_E_INVALID, "texture: a device-side count needs Bt = B = 1");
+    const SgrCubeSeam& sm = *sgr_cube_seam();
+    TxWork w = carve((char*)sgr_align_up((size_t)workspace, 256), g, C);
+    sort_stages(g, C, uv, dL_dout, w, dev_n, s);
     const uint64_t texels = (uint64_t)Bt * 6 * R * R;
     if (C == 3)
-        sgr_texture_cube_gather_kernel<3><<<blocks(texels), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
+        sgr_texture_cube_gather_kernel<3><<<blocks(texels), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex, TxStep{});
     else
-        sgr_texture_cube_gather_kernel<0><<<blocks(texels * C), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex);
+        sgr_texture_cube_gather_kernel<0><<<blocks(texels * C), 256, 0, s>>>(g, sm, C, w.starts, w.rec, w.gs, dL_dtex,
+                                                                             TxStep{});
+    SGR_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t sgr_texture_cube_deferred_bytes(int R, int64_t n) {
+    const size_t tb = sgr_texture_cube_workspace_bytes(1, 1, R, 3, n);
+    return tb ? tb + kDeferredHeaderBytes : 0;
+}
+
+int sgr_texture_cube_deferred_impl(int R, int64_t n, const float* uv, const float* dL_dout, void* work,
+                                   const uint32_t* dev_n, uint8_t* active, hipStream_t s) {
+    TxGrid g;
+    if (const int rc = check_args(1, 1, R, 3, n, g)) return rc;
+    if (!uv || !dL_dout || !work || !active || !dev_n)
+        return sgr_set_error(SGR_E_INVALID, "texture: uv, dL_dout, the workspace, active and the count are required");
+    char* base = (char*)sgr_align_up((size_t)work, 256);
+    TxWork w = carve(base + kDeferredHeaderBytes, g, 3);
+    const int cur = sort_stages(g, 3, uv, dL_dout, w, dev_n, s);
+    const TxDeferredHeader h{(uint64_t)((char*)w.starts - base), (uint64_t)((char*)w.rec - base),
+                             (uint64_t)((char*)w.gs - base)};
+    sgr_texture_cube_mark_kernel<<<blocks(g.total ? g.total : 1), 256, 0, s>>>(g, *sgr_cube_seam(), w.keys[cur], dev_n,
+                                                                               active, (TxDeferredHeader*)base, h);
+    SGR_HIP(hipGetLastError());
+    return 0;
+}
+
+int sgr_texture_cube_adam_step_impl(int R, float* p, float* m, float* v, const void* work, const uint8_t* active,
+                                    float step_size, float bc2_sqrt, float eps, double beta1, double beta2, hipStream_t s) {
+    TxGrid g;
+    if (const int rc = check_args(1, 1, R, 3, 0, g)) return rc;
+    if (!p || !m || !v || !active) return sgr_set_error(SGR_E_INVALID, "texture: p, m, v and active are required");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return sgr_set_error(SGR_E_INVALID, "adam: betas must lie in [0, 1)");
+    const TxStep st{p, m, v, active, work ? (const char*)sgr_align_up((size_t)work, 256) : nullptr,
+                    adam_consts(beta1, beta2), step_size, bc2_sqrt, eps};
+    const uint64_t texels = (uint64_t)6 * R * R;
+    sgr_texture_cube_gather_kernel<3, true><<<blocks(texels), 256, 0, s>>>(g, *sgr_cube_seam(), 3, nullptr, nullptr, nullptr,
+                                                                          nullptr, st);
     SGR_HIP(hipGetLastError());
     return 0;
 }
