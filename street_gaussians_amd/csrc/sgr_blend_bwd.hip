@@ -15,7 +15,7 @@
 //     unlike the reference's unordered atomics.
 // Row layout (stride = the instantiation's 12 + SMAX floats rounded up to float4s, 16-B aligned): [0..2] dL/dmean2D (x, y, |x|+|y|),
 // [3..5] dL/dconic (x, y, w), [6] dL/dopacity, [7..9] dL/drgb, [10] dL/ddepth, [11..11+S) dL/dsemantic.
-#include "sgr_math.h"
+#include "sgr_tile_walk.h"
 #include "sgr_reduce.h"
 
 #include <type_traits>
@@ -24,7 +24,6 @@
 #define SGR_WITH_VARIANTS 0  // 1: also build the designs that were measured slower and kept as A/Bs (tools/build_variant.py)
 #endif
 
-#define SGR_TILE_THREADS 256
 typedef float sgr_f2 __attribute__((ext_vector_type(2)));
 // list entries staged in LDS per round.  128 (not 256) keeps the S = 0 workgroup at 20 KB of LDS so that occupancy is
 // set by registers instead of LDS: measured +11 % time at 3 workgroups / CU vs 4.  The instantiations with more than 8
@@ -52,26 +51,9 @@ struct SgrBwdBatch { static constexpr int value = SMAX <= 8 ? SGR_BWD_BATCH : SG
 #ifndef SGR_FACTORED
 #define SGR_FACTORED 1
 #endif
-// parity mode: 1 = expf / division written out without their range handling (sgr_math.h: sgr_expf_ref, sgr_div_by; same
-// bits for the operands of this kernel), 0 = the library's expf and the compiler's IEEE `/` (A/B: tools/build_variant.py)
-// Parity mode, backward (round 5).  What north_star asks of the gradients is rel 1e-4, not the reference's bits -- those are
-// asked of the tile / bin indices and met by the forward, whose alpha test decides them.  SGR_EXACT_BWD_FAST=1: the backward
-// of the parity mode keeps the reference's own power expression (cancellation in it is what can cost digits) but takes
-// G = exp(power) from v_exp_f32 and T / (1 - alpha) from the Newton-refined reciprocal, like the default mode -- EXCEPT that a
-// visit with any pixel whose alpha lands within 4e-6 (relative) of the 1/255 threshold recomputes G with the accurate expf for
-// the whole wave (a wave-uniform branch, taken about once in 10^4 visits): every blend / skip decision is therefore the
-// forward's, and what differs from the all-exact backward is rounding-level (<= 4e-7 relative in G, <= 1 ulp per layer in T).
-#ifndef SGR_EXACT_BWD_FAST
-#define SGR_EXACT_BWD_FAST 1  // 0: every function of the backward with the reference's bits (A/B: tools/build_variant.py)
-#endif
+// (SGR_EXACT_TRIM, SGR_EXACT_BWD_FAST and SGR_EXACT_BWD_GUARD, the parity mode's switches, live in sgr_tile_walk.h)
 #ifndef SGR_BWD_NEWTON
 #define SGR_BWD_NEWTON 0  // 1: a Newton step on v_rcp_f32(1 - alpha) before the T recovery (rounds 1-4; measured in round 5: no parity figure moves without it)
-#endif
-#ifndef SGR_EXACT_BWD_GUARD
-#define SGR_EXACT_BWD_GUARD 1  // 0 only for tools/valu_model.py (a static count of the loop without its rare branch)
-#endif
-#ifndef SGR_EXACT_TRIM
-#define SGR_EXACT_TRIM 1
 #endif
 #ifndef SGR_FOLD
 #define SGR_FOLD 1
@@ -171,15 +153,6 @@ void sgr_launch_wave_sum_test(const float* in, float* out_dpp, float* out_shfl, 
     sgr_wave_sum_test_kernel<<<nwaves, 64, 0, s>>>(in, out_dpp, out_shfl);
 }
 
-// __syncthreads() preceded by an explicit LDS drain.  hipcc (ROCm 7.2, gfx950) emits the post-walk barrier of this
-// kernel as a bare s_barrier at a branch target: the last trip's ds_add_f32 / ds_write_b32 of a wave may still be in
-// flight when the other waves are released and flush the rows (seen on MI355X as a rare wrong row with 64-entry
-// rounds; every other barrier of the library has hipcc's own s_waitcnt lgkmcnt(0) in front of it).
-__device__ __forceinline__ void sgr_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
 // byte address inside the workgroup's LDS allocation of a pointer into a __shared__ array (for ds_* written as asm)
 __device__ __forceinline__ uint32_t sgr_lds_addr(const float* p) {
     return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const float*)p;
@@ -238,17 +211,14 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     __shared__ __attribute__((aligned(16))) float sAcc[(CAP + XROWS) * ACCW];
     __shared__ __attribute__((aligned(16))) float sSem[SMAX > 0 ? BATCH * SMAX : 4];  // zero-padded to SMAX
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t tx, ty;
-    if (!sgr_wg_tile(blockIdx.x, gx, gy, ranges, tx, ty)) return;  // whole workgroup: padding block
-    const uint32_t tile = ty * (uint32_t)gx + tx;
-    const uint32_t px = tx * SGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const uint32_t py = ty * SGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < (uint32_t)W && py < (uint32_t)H;
-    const float pxf = (float)px, pyf = (float)py;
-    const size_t pix_id = (size_t)W * py + px;
+    SgrTilePixel tp;
+    if (!sgr_tile_pixel(tp, gx, gy, ranges)) return;
+    const int tid = tp.tid, lane = tp.lane, wave = tp.wave;
+    const uint32_t tx = tp.tx, ty = tp.ty;
+    const bool inside = tp.inside(W, H);
+    const size_t pix_id = (size_t)W * tp.py + tp.px;
     const size_t plane = (size_t)H * W;
-    const uint2 range = ranges[tile];
+    const uint2 range = ranges[tp.tile];
 
     // backward.cu:466-500
     const float T_final = inside ? (1.0f - alphas[pix_id]) : 0.0f;
@@ -314,7 +284,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     if (lane == 0) sMax[wave] = mx;
     sgr_lds_barrier();
     const int maxc = max(max(sMax[0], sMax[1]), max(sMax[2], sMax[3]));
-    const float tx0 = (float)(tx * SGR_BLOCK_X), ty0 = (float)(ty * SGR_BLOCK_Y);
+    const float tx0 = tp.tx0(), ty0 = tp.ty0();
     // LDS row of this lane's 16-lane group inside a slot (see the reduce-scatter layout below)
     const int acc_lane_off = (DET ? (wave >> 1) : 0) * BATCH * ACCW + (lane >> 4);
     // folded reduction (sgr_wave_reduce_fold): the bank (4 lanes) this lane sits in holds, in result register i,
@@ -368,8 +338,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
             const float4 a = r[0];
             const float4 b = r[1];
             const float4 d4 = r[3];
-            sB[tid] = EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w)
-                            : sgr_stage_conic(b);
+            sB[tid] = sgr_stage_conic_mode<EXACT>(b);
             sC[tid] = r[2];
             const uint32_t dy_ = __float_as_uint(d4.y);
             // first row of the Gaussian (compact array, L2-resident) + rank of this tile among the tiles it is emitted for:
@@ -396,13 +365,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                 if (CULL && hit4 != nullptr) h_pre = hit4[range.x + lp];
             }
         }
-        if (stager) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint64_t m = __ballot((mask4 >> q) & 1u);
-                if (lane == 0) sBits[q][wave] = m;
-            }
-        }
+        if (stager) sgr_store_cull_ballots(mask4, lane, wave, sBits);
         sgr_lds_barrier();
 
         // VROWS: the survivor masks of all four quadrants (wave-uniform: scalar registers), how many slots of this round are
@@ -453,8 +416,10 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
 
         uint64_t vis = 0;  // VROWS: the slots of the current chunk this wave gave a row (scalar)
         // VROWS: a visit with at least one hitting pixel takes the wave's next row (`rown`, wave-uniform) and sets its bit in `vis`
-        auto process = [&](const int j, const float4 q, const float dx, const float dy, const float power2, const float G,
-                           const float alpha) __attribute__((always_inline)) {
+        auto process = [&](const SgrVisit& vt) __attribute__((always_inline)) {
+                const int j = vt.j;
+                const float4 q = vt.q;
+                const float dx = vt.dx, dy = vt.dy, power2 = vt.power, G = vt.G, alpha = vt.alpha;
                 const int posj = hi - j;  // 0-based list position == `contributor` after its decrement
                 // backward.cu:527-545
                 // (pixels outside the image have lastc = 0).  The wave-wide "any hit" is taken from the three compare
@@ -679,17 +644,6 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                     for (int t = 0; t < NVAL / 4; t++) atomicAdd(&dst[4 * t], r[t]);
                 }
         };
-        // parity mode: G = exp(power), power in natural-log units (see SGR_EXACT_BWD_FAST)
-        auto exactG = [&](const float pw, const float opac) __attribute__((always_inline)) -> float {
-            if constexpr (SGR_EXACT_BWD_FAST != 0) {
-                float g = __builtin_amdgcn_exp2f(pw * SGR_LOG2E);
-                const bool near = fabsf(opac * g - SGR_ALPHA_MIN) <= 4.0e-6f * SGR_ALPHA_MIN;
-                if (SGR_EXACT_BWD_GUARD && __builtin_amdgcn_ballot_w64(near) != 0) g = SGR_EXACT_TRIM ? sgr_expf_ref(pw) : expf(pw);
-                return g;
-            } else {
-                return SGR_EXACT_TRIM ? sgr_expf_ref(pw) : expf(pw);
-            }
-        };
         for (int chunk = 0; chunk < BATCH / 64; chunk++) {
             uint64_t m;
             m = sBits[wave][chunk];
@@ -698,31 +652,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                 const int nb = lim - 64 * chunk;
                 m = nb >= 64 ? m : (nb <= 0 ? 0ull : (m & ((1ull << nb) - 1ull)));
             }
-            // scalar bookkeeping kept short (SALU issues once per four cycles per SIMD): s_ff1 + s_bitset0 per survivor, and
-            // the odd survivor is taken first so that the loop is pairs only
-            if (__builtin_popcountll(m) & 1) {
-                const int j0 = chunk * 64 + sgr_pop_lowest(m);
-                const float4 a0 = sA[j0], q0 = sB[j0];
-                const float dx0 = a0.x - pxf, dy0 = a0.y - pyf;
-                const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, dx0, dy0) : sgr_power2(q0.x, q0.y, q0.z, dx0, dy0);
-                const float G0 = EXACT ? exactG(pw0, q0.w) : __builtin_amdgcn_exp2f(pw0);
-                process(j0, q0, dx0, dy0, pw0, G0, fminf(0.99f, q0.w * G0));
-            }
-            while (m) {
-                // two survivors per trip: LDS reads and exp() of both are independent of each other; only the
-                // per-pixel recurrences (process) are ordered
-                const int j0 = chunk * 64 + sgr_pop_lowest(m);
-                const int j1 = chunk * 64 + sgr_pop_lowest(m);
-                const float4 a0 = sA[j0], q0 = sB[j0];
-                const float4 a1 = sA[j1], q1 = sB[j1];
-                const float dx0 = a0.x - pxf, dy0 = a0.y - pyf, dx1 = a1.x - pxf, dy1 = a1.y - pyf;
-                const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, dx0, dy0) : sgr_power2(q0.x, q0.y, q0.z, dx0, dy0);
-                const float pw1 = EXACT ? sgr_power_ref_staged(q1.x, q1.y, q1.z, dx1, dy1) : sgr_power2(q1.x, q1.y, q1.z, dx1, dy1);
-                const float G0 = EXACT ? exactG(pw0, q0.w) : __builtin_amdgcn_exp2f(pw0), G1 = EXACT ? exactG(pw1, q1.w) : __builtin_amdgcn_exp2f(pw1);
-                const float al0 = fminf(0.99f, q0.w * G0), al1 = fminf(0.99f, q1.w * G1);
-                process(j0, q0, dx0, dy0, pw0, G0, al0);
-                process(j1, q1, dx1, dy1, pw1, G1, al1);
-            }
+            sgr_walk_pairs<EXACT, true>(m, chunk, sA, sB, tp.pxf, tp.pyf, process);
             if constexpr (VROWS) {
                 if (lane == 0) sVis[wave][chunk] = vis;
                 vis = 0;

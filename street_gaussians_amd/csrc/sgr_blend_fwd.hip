@@ -1,33 +1,18 @@
 // sgr_blend_fwd.hip -- K10: front-to-back alpha compositing of one 16x16 tile per workgroup on
 // gfx950.  Replaces renderCUDA<3> of the reference (forward.cu:340-467).
 //
-// CDNA4 mapping: 256 lanes = 4 wave64; each wave owns one 8x8 pixel QUADRANT of the tile (compact
-// footprint, so a whole wave can skip a splat).  The tile's depth-sorted instance list is staged
-// through LDS 256 instances at a time: every lane gathers one instance (three 16-byte loads),
-// pre-scales the conic (so exp() is one v_exp_f32), and tests the splat's conservative alpha>=1/255
-// bounding box (recA.zw) against the four quadrants.  Four wave ballots turn those tests into one
-// 64-bit survivor mask per (quadrant, 64-instance chunk); each wave then walks only the set bits of
-// its own masks (s_ff1 loop) and reads the survivor's record from LDS as a broadcast.  Semantic
-// channels accumulate in registers (the reference does a global read-modify-write per pair,
+// CDNA4 mapping: the quadrant-per-wave, LDS-staged, ballot-culled walk of sgr_tile_walk.h, 256 instances per batch
+// (three 16-byte loads per staging lane; the cull tests the splat's conservative alpha>=1/255 bounding box, recA.zw).
+// Semantic channels accumulate in registers (the reference does a global read-modify-write per pair,
 // forward.cu:442-444).  Results are identical to walking the full list: a culled instance can only
 // fail the alpha test for every pixel of the quadrant.
-#include "sgr_math.h"
+#include "sgr_tile_walk.h"
 
-#define SGR_TILE_THREADS 256
 #ifndef SGR_FWD_SEL
 #define SGR_FWD_SEL 1  // selects of the blend step on an SGPR-pair lane mask (0: plain ?: -- the compiler's v_cndmask on VCC)
 #endif
-// lane in m ? a : b, the lane mask in a scalar register pair
-__device__ __forceinline__ float sgr_sel_mask(uint64_t m, float a, float b) {
-    float r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
 #ifndef SGR_EXACT_COLOR_FUSED
-#define SGR_EXACT_COLOR_FUSED 1  // parity mode: the three colour sums as FMAs (see blend_one); 0: unfused like depth (A/B)
-#endif
-#ifndef SGR_EXACT_TRIM
-#define SGR_EXACT_TRIM 1  // parity mode: sgr_expf_ref instead of the library's expf (same bits, sgr_math.h)
+#define SGR_EXACT_COLOR_FUSED 1  // parity mode: the three colour sums as FMAs (see the walk's step); 0: unfused like depth (A/B)
 #endif
 
 // Register budget (tools/occupancy_audit.py).  Left alone the allocator lands a few registers past an occupancy step
@@ -60,30 +45,21 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
     __shared__ uint32_t sCnt[SGR_TILE_THREADS];  // per slot of the batch store_hits last saw: its index in the compact hit list + 1
     __shared__ __attribute__((aligned(16))) float sSem[SMAX > 0 ? SGR_TILE_THREADS * SMAX : 4];  // zero-padded to SMAX
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t tx, ty;
-    if (!sgr_wg_tile(blockIdx.x, gx, gy, ranges, tx, ty)) return;  // whole workgroup: padding block
-    const uint32_t tile = ty * (uint32_t)gx + tx;
-    const uint32_t px = tx * SGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const uint32_t py = ty * SGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < (uint32_t)W && py < (uint32_t)H;
-    const float pxf = (float)px, pyf = (float)py;
-    const uint2 range = ranges[tile];
+    SgrTilePixel tp;
+    if (!sgr_tile_pixel(tp, gx, gy, ranges)) return;
+    const int tid = tp.tid, lane = tp.lane, wave = tp.wave;
+    const bool inside = tp.inside(W, H);
+    const uint2 range = ranges[tp.tile];
 
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f, Wt = 0.f;
     float sem[SMAX > 0 ? SMAX : 1];
 #pragma unroll
     for (int i = 0; i < (SMAX > 0 ? SMAX : 1); i++) sem[i] = 0.f;
     uint32_t last = 0;
-    // Finished pixels (outside the image, or T exhausted) are tracked twice: `done_mask` is the wave's scalar lane mask
-    // (tile-/wave-wide exits are scalar compares), and `thr`, the per-lane alpha threshold, becomes +inf so that a
-    // finished lane fails the alpha test without a separate predicate (hipcc turns ballot(compound bool) and
-    // __any/__all into v_cndmask + v_cmp pairs; direct compares combined with scalar ANDs cost no VALU).
+    // finished pixels: the wave's scalar lane mask and the per-lane alpha threshold (sgr_blend_begin)
     uint64_t done_mask = sgr_uniform_u64(__builtin_amdgcn_ballot_w64(!inside));
     float thr = inside ? SGR_ALPHA_MIN : __builtin_inff();
-
-    // quadrant bounds (pixel centres) used by the staging lanes for the cull test
-    const float tx0 = (float)(tx * SGR_BLOCK_X), ty0 = (float)(ty * SGR_BLOCK_Y);
+    const float tx0 = tp.tx0(), ty0 = tp.ty0();  // the staging lanes' cull test
 
     // One byte per instance of the batch that starts at list index b0 (after the barrier that follows its walk) ... and the
     // COMPACT list of the instances that have a hit byte at all (SgrBinView::hlist: positions relative to the tile's range,
@@ -150,9 +126,7 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
             const float4 a = r[0];
             const float4 b = r[1];
             sA[tid] = a;
-            // EXACT (parity mode): exact power-of-two scalings only -- the walk evaluates the reference's own power
-            // expression on the staged triple (sgr_power_ref_staged)
-            sB[tid] = EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w) : sgr_stage_conic(b);
+            sB[tid] = sgr_stage_conic_mode<EXACT>(b);
             sC[tid] = r[2];
             if (SMAX > 0) {  // channels S..SMAX-1 are staged as zeros so the walk needs no per-channel test
 #pragma unroll
@@ -160,11 +134,7 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
             }
             mask4 = CULL ? sgr_quadrant_mask(a, b, tx0, ty0) : 0xFu;
         }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint64_t m = __ballot((mask4 >> q) & 1u);
-            if (lane == 0) sBits[q][wave] = m;
-        }
+        sgr_store_cull_ballots(mask4, lane, wave, sBits);
         if (hl && tid < 4) sAny[par][tid] = 0ull;  // last read one batch ago, two barriers back
         __syncthreads();
         if (hl) take_lastk();
@@ -175,41 +145,25 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
 
         if (done_mask != ~0ull) {
             const uint32_t pos0 = base - range.x;  // list position of slot 0 of this batch
-            bool stop = false;
-            for (int chunk = 0; chunk < 4 && !stop; chunk++) {
+            for (int chunk = 0; chunk < 4 && done_mask != ~0ull; chunk++) {
                 uint64_t m = sBits[wave][chunk];
                 m = sgr_uniform_u64(m);
                 uint64_t hb = 0;  // wave-uniform (scalar registers)
-                // One blend step (forward.cu:425-445) of list slot j = chunk * 64 + bit.  The walk's bookkeeping is scalar
-                // (SALU issues once per four cycles per SIMD, and this kernel issues about as many scalar as vector
-                // instructions): bits are taken with s_ff1 + s_bitset0, the hit record is one s_bitset1.
-                auto blend_one = [&](const int j, const int bit, const float power2, const float alpha) __attribute__((always_inline)) {
-                    // skip if power > 0 or alpha < 1/255 (or the pixel is finished: thr = inf)
-                    const bool k1 = !(power2 > 0.0f), k2 = !(alpha < thr);
-                    const uint64_t hm = __builtin_amdgcn_ballot_w64(k1) & __builtin_amdgcn_ballot_w64(k2);
-                    if (hm == 0) return;
-                    const float test_T = T * (1.0f - alpha);
-                    const bool k3 = test_T < 0.0001f;  // forward.cu:431-436
-#if SGR_FWD_SEL
-                    // the three selects on "this lane blends" take their lane mask from a scalar register pair
-                    // (v_cndmask_b32_e64 with an SGPR-pair mask: 4.6 cycles per wave instruction measured, against 23 for
-                    // back-to-back selects on VCC, tools/ubench/valu_rates.hip): the mask is a by-product of the ballots
-                    // the walk needs anyway
-                    const uint64_t k3m = __builtin_amdgcn_ballot_w64(k3);
-                    const uint64_t bm = hm & ~k3m;
-#define SGR_BLEND_SEL(a, b) sgr_sel_mask(bm, (a), (b))
-#else
-                    const bool blend = k1 && k2 && !k3;
-#define SGR_BLEND_SEL(a, b) (blend ? (a) : (b))
-#endif
+                // This kernel's sums on top of one blend step of list slot v.j.  The walk's bookkeeping is scalar (SALU issues
+                // once per four cycles per SIMD, and this kernel issues about as many scalar as vector instructions): bits are
+                // taken with s_ff1 + s_bitset0, the hit record is one s_bitset1.
+                sgr_walk_pairs<EXACT, false>(m, chunk, sA, sB, tp.pxf, tp.pyf, [&](const SgrVisit& v) __attribute__((always_inline)) {
+                    SgrBlendStep<SGR_FWD_SEL != 0> b;
+                    if (!sgr_blend_begin(b, T, thr, v.power, v.alpha)) return;
+                    const int j = v.j;
+                    const float alpha = v.alpha, w = b.w;
                     const float4 c = sC[j];
-                    const float w = SGR_BLEND_SEL(alpha * T, 0.0f);
                     if (EXACT) {
                         // the reference's association, unfused: C[ch] += features[ch] * alpha * T (forward.cu:438-441) -- for the
                         // DEPTH (and semantic) sums, whose images the parity mode reproduces bit for bit.  The colour sums take the
                         // fused form (SGR_EXACT_COLOR_FUSED): their inputs already differ from the reference's in the last bit
                         // (the SH evaluation), the image is held to rel 1e-4, and no gradient depends on it
-                        const float ae = SGR_BLEND_SEL(alpha, 0.0f);
+                        const float ae = b.sel(alpha, 0.0f);
                         if (SGR_EXACT_COLOR_FUSED) {
                             C0 = fmaf(c.x, w, C0);
                             C1 = fmaf(c.y, w, C1);
@@ -229,7 +183,7 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
                     Wt += w;
                     if (SMAX > 0) {
                         const float4* sj = reinterpret_cast<const float4*>(&sSem[j * SMAX]);
-                        const float ae = SGR_BLEND_SEL(alpha, 0.0f);
+                        const float ae = b.sel(alpha, 0.0f);
 #pragma unroll
                         for (int c4 = 0; c4 < SMAX / 4; c4++) {
                             const float4 sv = sj[c4];
@@ -246,48 +200,13 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
                             }
                         }
                     }
-                    T = SGR_BLEND_SEL(test_T, T);
-                    last = __float_as_uint(SGR_BLEND_SEL(__uint_as_float(pos0 + (uint32_t)j + 1u), __uint_as_float(last)));
-#undef SGR_BLEND_SEL
+                    sgr_blend_end(b, T, thr, done_mask, m);
+                    last = b.sel(pos0 + (uint32_t)j + 1u, last);
                     // Some lane passed the alpha test: the backward has to visit (quadrant, instance).  (A superset of
                     // the visits that blend: if every passing lane finishes on this very instance nothing is blended, and
                     // the backward's own per-pixel test -- list position < n_contrib -- skips it.)
-                    hb = sgr_bitset1(hb, bit);
-#if SGR_FWD_SEL
-                    const uint64_t sm = hm & k3m;
-#else
-                    const uint64_t sm = hm & __builtin_amdgcn_ballot_w64(k3);
-#endif
-                    if (sm != 0) {
-                        thr = (k1 && k2 && k3) ? __builtin_inff() : thr;
-                        done_mask |= sm;
-                        if (done_mask == ~0ull) { m = 0; stop = true; }
-                    }
-                };
-                if (__builtin_popcountll(m) & 1) {  // odd one out first, so that the loop below is pairs only
-                    const int b0 = sgr_pop_lowest(m);
-                    const int j0 = chunk * 64 + b0;
-                    const float4 a0 = sA[j0], q0 = sB[j0];
-                    const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf)
-                                            : sgr_power2(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf);
-                    blend_one(j0, b0, pw0, fminf(0.99f, q0.w * (EXACT ? (SGR_EXACT_TRIM ? sgr_expf_ref(pw0) : expf(pw0)) : __builtin_amdgcn_exp2f(pw0))));
-                }
-                while (m) {
-                    // two survivors per trip: their LDS reads and exp() are independent, only the blend is ordered
-                    const int b0 = sgr_pop_lowest(m);
-                    const int b1 = sgr_pop_lowest(m);
-                    const int j0 = chunk * 64 + b0, j1 = chunk * 64 + b1;
-                    const float4 a0 = sA[j0], q0 = sB[j0];
-                    const float4 a1 = sA[j1], q1 = sB[j1];
-                    const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf)
-                                            : sgr_power2(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf);
-                    const float pw1 = EXACT ? sgr_power_ref_staged(q1.x, q1.y, q1.z, a1.x - pxf, a1.y - pyf)
-                                            : sgr_power2(q1.x, q1.y, q1.z, a1.x - pxf, a1.y - pyf);
-                    const float al0 = fminf(0.99f, q0.w * (EXACT ? (SGR_EXACT_TRIM ? sgr_expf_ref(pw0) : expf(pw0)) : __builtin_amdgcn_exp2f(pw0)));
-                    const float al1 = fminf(0.99f, q1.w * (EXACT ? (SGR_EXACT_TRIM ? sgr_expf_ref(pw1) : expf(pw1)) : __builtin_amdgcn_exp2f(pw1)));
-                    blend_one(j0, b0, pw0, al0);
-                    blend_one(j1, b1, pw1, al1);  // if the wave finished on j0 every lane's threshold is +inf: a no-op
-                }
+                    hb = sgr_bitset1(hb, v.bit);
+                });
                 if (lane == 0) {
                     sHit[wave][chunk] = hb;
                     if (hl && hb) __hip_atomic_fetch_or(&sAny[par][chunk], hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -305,7 +224,7 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
     }
 
     if (inside) {
-        const size_t pix_id = (size_t)W * py + px;
+        const size_t pix_id = (size_t)W * tp.py + tp.px;
         const size_t plane = (size_t)H * W;
         n_contrib[pix_id] = last;
         if (hl) n_contrib_k[pix_id] = lastk;

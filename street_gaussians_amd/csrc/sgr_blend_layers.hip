@@ -9,126 +9,70 @@
 // survivors in list order -- two straight copies of the forward's walk, each on its own accumulator set, picked by a scalar
 // test on one more ballot mask per chunk (entry g >= split).
 //
-// Shape: that of sgr_blend_fwd.hip -- one 16x16 tile per 256-thread workgroup, one wave64 per 8x8 quadrant, the list staged
-// through LDS 256 entries at a time with the conservative quadrant cull, grid / padding blocks / tile order from
-// sgr_xcd_grid_blocks and sgr_wg_tile.  Per pixel and layer: T, three colour sums, the alpha sum, the alpha threshold that
-// becomes +inf once the pixel is finished, and the wave's scalar mask of finished pixels.  No depth, semantics, n_contrib or
-// hit record: nothing of the composite's buffers is written.
-//
-// Arithmetic: the expressions of sgr_blend_fwd.hip, in its order, so that a layer image is bit for bit the image of a
-// forward over that subset alone -- blend step :186-250 (alpha test, test_T < 0.0001, w = alpha * T, the colour sums as FMAs
-// in both modes, Wt += w), power and alpha :267-290 (fast: sgr_power2 on the staged conic + v_exp_f32; EXACT:
-// sgr_power_ref_staged + sgr_expf_ref), store :312-315 (C + T * bg, contraction off).
+// Shape and arithmetic: sgr_tile_walk.h -- the forward's staging, cull, walk and blend step, on T, three colour sums and the
+// alpha sum per pixel and layer (no depth, semantics, n_contrib or hit record: nothing of the composite's buffers is
+// written).  A layer image is therefore bit for bit the image of a forward over that subset alone: the colour sums are
+// FMAs in both modes, the store is C + T * bg with contraction off, as the forward's.
 //
 // Termination is per layer (forward.cu:394-396, 431-436): a pixel's layer stops at its own test_T < 0.0001; a wave drops
 // the entries of a layer all its 64 pixels have finished; a wave stops when both layers are finished; the tile stops when
 // its four waves have.  The composite's transmittance plays no part.  A layer that all FOUR waves have finished is not
 // staged any more either: its entries are treated like dead ones (no record fetch), which is what keeps the walk behind an
 // opaque background wall cheap while the object layer is still looking for its splats.
-#include "sgr_math.h"
+#include "sgr_tile_walk.h"
 
-#define SGR_LAYER_THREADS 256
-
-// lane in m ? a : b, the lane mask in a scalar register pair (sgr_blend_fwd.hip: 4.6 instead of 23 cycles per select)
-__device__ __forceinline__ float sgr_layer_sel(uint64_t m, float a, float b) {
-    float r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
 __device__ __forceinline__ float sgr_layer_out(float v, int clamp) {  // NaN stays NaN, as torch.clamp
     return clamp ? (v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v)) : v;
 }
 
 template <bool EXACT>
-__global__ void __launch_bounds__(SGR_LAYER_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
+__global__ void __launch_bounds__(SGR_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
 sgr_blend_layers_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H, int gx, int gy,
                         const float4* __restrict__ rec, uint32_t split, uint32_t P, const float* __restrict__ bg_color,
                         int clamp, float* __restrict__ color0, float* __restrict__ alpha0, float* __restrict__ color1,
                         float* __restrict__ alpha1) {
     // fused multiply-adds are written out (fmaf), as in the forward whose bits this kernel reproduces
 #pragma clang fp contract(off)
-    __shared__ float4 sA[SGR_LAYER_THREADS];  // {x, y, -, -}
-    __shared__ float4 sB[SGR_LAYER_THREADS];  // {qa, qb, qc, opacity}
-    __shared__ float4 sC[SGR_LAYER_THREADS];  // {r, g, b, -}
+    __shared__ float4 sA[SGR_TILE_THREADS];  // {x, y, -, -}
+    __shared__ float4 sB[SGR_TILE_THREADS];  // {qa, qb, qc, opacity}
+    __shared__ float4 sC[SGR_TILE_THREADS];  // {r, g, b, -}
     __shared__ uint64_t sBits[4][4];          // [quadrant][chunk of 64 entries]: survivors of the cull
     __shared__ uint64_t sLayer[4];            // [chunk]: entries of layer 1 (g >= split)
     __shared__ uint32_t sDone[4];             // [wave]: bit l = layer l is finished for all 64 pixels
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t tx, ty;
-    if (!sgr_wg_tile(blockIdx.x, gx, gy, ranges, tx, ty)) return;  // whole workgroup: padding block
-    const uint32_t tile = ty * (uint32_t)gx + tx;
-    const uint32_t px = tx * SGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const uint32_t py = ty * SGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < (uint32_t)W && py < (uint32_t)H;
-    const float pxf = (float)px, pyf = (float)py;
-    const uint2 range = ranges[tile];
+    SgrTilePixel tp;
+    if (!sgr_tile_pixel(tp, gx, gy, ranges)) return;
+    const int tid = tp.tid, lane = tp.lane, wave = tp.wave;
+    const bool inside = tp.inside(W, H);
+    const uint2 range = ranges[tp.tile];
 
     float Ta = 1.0f, Ca0 = 0.f, Ca1 = 0.f, Ca2 = 0.f, Wa = 0.f;  // layer 0
     float Tb = 1.0f, Cb0 = 0.f, Cb1 = 0.f, Cb2 = 0.f, Wb = 0.f;  // layer 1
     // finished pixels (outside the image, or the layer's T exhausted): the wave's scalar lane mask and the per-lane alpha
-    // threshold that becomes +inf (sgr_blend_fwd.hip:78-83), once per layer
+    // threshold that becomes +inf (sgr_blend_begin), once per layer
     // (an EMPTY layer -- split == 0 or split == P -- starts finished: it keeps T = 1, sums 0, and does not hold the tile)
     const uint64_t outside = sgr_uniform_u64(__builtin_amdgcn_ballot_w64(!inside));
     uint64_t done_a = split == 0u ? ~0ull : outside, done_b = split >= P ? ~0ull : outside;
     float thr_a = inside ? SGR_ALPHA_MIN : __builtin_inff(), thr_b = thr_a;
 
-    const float tx0 = (float)(tx * SGR_BLOCK_X), ty0 = (float)(ty * SGR_BLOCK_Y);
+    const float tx0 = tp.tx0(), ty0 = tp.ty0();
 
     // The forward's walk of the set bits of m (list slots chunk * 64 + bit) on one layer's accumulators.
     auto walk = [&](uint64_t m, const int chunk, float& T, float& C0, float& C1, float& C2, float& Wt, float& thr,
                     uint64_t& done_mask) __attribute__((always_inline)) {
-        // one blend step (forward.cu:425-445; sgr_blend_fwd.hip:186-250 without depth, semantics, n_contrib and hits)
-        auto blend_one = [&](const int j, const float power2, const float alpha) __attribute__((always_inline)) {
-            // skip if power > 0 or alpha < 1/255 (or the pixel is finished: thr = inf)
-            const bool k1 = !(power2 > 0.0f), k2 = !(alpha < thr);
-            const uint64_t hm = __builtin_amdgcn_ballot_w64(k1) & __builtin_amdgcn_ballot_w64(k2);
-            if (hm == 0) return;
-            const float test_T = T * (1.0f - alpha);
-            const bool k3 = test_T < 0.0001f;  // forward.cu:431-436
-            const uint64_t k3m = __builtin_amdgcn_ballot_w64(k3);
-            const uint64_t bm = hm & ~k3m;  // the lanes that blend
-            const float4 c = sC[j];
-            const float w = sgr_layer_sel(bm, alpha * T, 0.0f);
-            C0 = fmaf(c.x, w, C0);
-            C1 = fmaf(c.y, w, C1);
-            C2 = fmaf(c.z, w, C2);
-            Wt += w;
-            T = sgr_layer_sel(bm, test_T, T);
-            const uint64_t sm = hm & k3m;
-            if (sm != 0) {
-                thr = (k1 && k2 && k3) ? __builtin_inff() : thr;
-                done_mask |= sm;
-                if (done_mask == ~0ull) m = 0;
-            }
-        };
-        if (__builtin_popcountll(m) & 1) {  // odd one out first, so that the loop below is pairs only
-            const int b0 = sgr_pop_lowest(m);
-            const int j0 = chunk * 64 + b0;
-            const float4 a0 = sA[j0], q0 = sB[j0];
-            const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf)
-                                    : sgr_power2(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf);
-            blend_one(j0, pw0, fminf(0.99f, q0.w * (EXACT ? sgr_expf_ref(pw0) : __builtin_amdgcn_exp2f(pw0))));
-        }
-        while (m) {
-            // two survivors per trip: their LDS reads and exp() are independent, only the blend is ordered
-            const int b0 = sgr_pop_lowest(m);
-            const int b1 = sgr_pop_lowest(m);
-            const int j0 = chunk * 64 + b0, j1 = chunk * 64 + b1;
-            const float4 a0 = sA[j0], q0 = sB[j0];
-            const float4 a1 = sA[j1], q1 = sB[j1];
-            const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf)
-                                    : sgr_power2(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf);
-            const float pw1 = EXACT ? sgr_power_ref_staged(q1.x, q1.y, q1.z, a1.x - pxf, a1.y - pyf)
-                                    : sgr_power2(q1.x, q1.y, q1.z, a1.x - pxf, a1.y - pyf);
-            const float al0 = fminf(0.99f, q0.w * (EXACT ? sgr_expf_ref(pw0) : __builtin_amdgcn_exp2f(pw0)));
-            const float al1 = fminf(0.99f, q1.w * (EXACT ? sgr_expf_ref(pw1) : __builtin_amdgcn_exp2f(pw1)));
-            blend_one(j0, pw0, al0);
-            blend_one(j1, pw1, al1);  // if the wave finished on j0 every lane's threshold is +inf: a no-op
-        }
+        sgr_walk_pairs<EXACT, false>(m, chunk, sA, sB, tp.pxf, tp.pyf, [&](const SgrVisit& v) __attribute__((always_inline)) {
+            SgrBlendStep<true> b;
+            if (!sgr_blend_begin(b, T, thr, v.power, v.alpha)) return;
+            const float4 c = sC[v.j];
+            C0 = fmaf(c.x, b.w, C0);
+            C1 = fmaf(c.y, b.w, C1);
+            C2 = fmaf(c.z, b.w, C2);
+            Wt += b.w;
+            sgr_blend_end(b, T, thr, done_mask, m);
+        });
     };
 
-    for (uint32_t base = range.x; base < range.y; base += SGR_LAYER_THREADS) {
+    for (uint32_t base = range.x; base < range.y; base += SGR_TILE_THREADS) {
         // tile-wide state of the two layers; also the barrier that protects LDS reuse
         if (lane == 0) sDone[wave] = (done_a == ~0ull ? 1u : 0u) | (done_b == ~0ull ? 2u : 0u);
         __syncthreads();
@@ -146,15 +90,11 @@ sgr_blend_layers_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
             const float4 a = r[0];
             const float4 b = r[1];
             sA[tid] = a;
-            sB[tid] = EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w) : sgr_stage_conic(b);
+            sB[tid] = sgr_stage_conic_mode<EXACT>(b);
             sC[tid] = r[2];
             mask4 = sgr_quadrant_mask(a, b, tx0, ty0);
         }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint64_t m = __ballot((mask4 >> q) & 1u);
-            if (lane == 0) sBits[q][wave] = m;
-        }
+        sgr_store_cull_ballots(mask4, lane, wave, sBits);
         {
             const uint64_t m = __ballot(upper);
             if (lane == 0) sLayer[wave] = m;
@@ -175,7 +115,7 @@ sgr_blend_layers_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
     }
 
     if (inside) {
-        const size_t pix_id = (size_t)W * py + px;
+        const size_t pix_id = (size_t)W * tp.py + tp.px;
         const size_t plane = (size_t)H * W;
         const float b0 = bg_color[0], b1 = bg_color[1], b2 = bg_color[2];
         color0[pix_id] = sgr_layer_out(Ca0 + Ta * b0, clamp);
@@ -211,10 +151,10 @@ void sgr_launch_blend_layers(bool exact, int gx, int gy, const uint2* ranges, co
     if (gx <= 0 || gy == 0) return;
     const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
     if (exact)
-        sgr_blend_layers_kernel<true><<<tiles, SGR_LAYER_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, (uint32_t)P, bg,
+        sgr_blend_layers_kernel<true><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, (uint32_t)P, bg,
                                                                            clamp, color[0], alpha[0], color[1], alpha[1]);
     else
-        sgr_blend_layers_kernel<false><<<tiles, SGR_LAYER_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, (uint32_t)P, bg,
+        sgr_blend_layers_kernel<false><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, (uint32_t)P, bg,
                                                                             clamp, color[0], alpha[0], color[1], alpha[1]);
 }
 

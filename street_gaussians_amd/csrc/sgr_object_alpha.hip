@@ -4,61 +4,55 @@
 // lib/models/street_gaussian_renderer.py:58-72, called from train.py:114-122) is two launches beside the shipped path here;
 // the shipped row sum and per-Gaussian backward (sgr_gauss_bwd.hip) consume the rows unchanged.
 //
-// Why the lists can be shared: see sgr_blend_layers.hip.  Both kernels have its shape -- one 16x16 tile per 256-thread
-// workgroup, one wave64 per 8x8 quadrant, the list staged through LDS with the conservative quadrant cull, grid / padding
-// blocks / tile order from sgr_xcd_grid_blocks and sgr_wg_tile -- and walk only the entries with g >= split that are not
-// marked dead: the others are skipped without a record fetch.
+// Why the lists can be shared: see sgr_blend_layers.hip.  Both kernels have the shape of sgr_tile_walk.h and take their
+// arithmetic from it, and walk only the entries with g >= split that are not marked dead: the others are skipped without
+// a record fetch.
 //
 // FORWARD (sgr_object_alpha_fwd_kernel): layer 1 of sgr_blend_layers_kernel without colour (no r[2] fetch, no background)
-// -- the same expressions in the same order (sgr_blend_layers.hip:81-128), so the alpha image is bit for bit the layer
-// kernel's acc_rest, i.e. the alpha of a forward over the subset alone -- plus, per pixel, the 1-based position inside the
-// tile's range of the last entry that was blended: the layer's n_contrib (forward.cu:431-445).
+// -- the same sgr_walk_pairs and blend step, so the alpha image is bit for bit the layer kernel's acc_rest, i.e. the alpha
+// of a forward over the subset alone -- plus, per pixel, the 1-based position inside the tile's range of the last entry
+// that was blended: the layer's n_contrib (forward.cu:431-445).
 //
 // BACKWARD (sgr_object_alpha_bwd_kernel): the alpha part of backward.cu:505-640, back to front over the positions below
-// the tile's largest recorded position, 128 per round.  Per visit the expressions of sgr_blend_bwd.hip in the same mode
-// (power, G with the parity mode's guard at the 1/255 threshold, v_rcp_f32 for T / (1 - alpha), the moments of G * dL/dopa);
-// which quadrants visit an entry is the geometric cull, redone (the shipped kernel's NO_HITS path: the lanes that take part
+// the tile's largest recorded position, 128 per round.  Per visit the blend backward's power, G (sgr_G_bwd: with the parity
+// mode's guard at the 1/255 threshold) and alpha from sgr_walk_pairs, and its expressions for the rest (v_rcp_f32 for
+// T / (1 - alpha), the moments of G * dL/dopa); which quadrants visit an entry is the geometric cull, redone (the shipped kernel's NO_HITS path: the lanes that take part
 // are decided per pixel, so the cull only removes visits without any).  No global atomics and no LDS float atomics: a
 // visit's seven sums are reduced across the wave (sgr_wave_reduce_fold) and stored into the slot's row OF THAT QUADRANT
 // (one writer per element); after the round one thread per slot adds the rows of the quadrants that visited it, in
 // quadrant order, turns the moments into gradients exactly as the shipped flush does and writes the row once.
-#include "sgr_math.h"
+#include "sgr_tile_walk.h"
 #include "sgr_reduce.h"
 
-#define SGR_OA_THREADS 256
 #define SGR_OA_BATCH 128  // list positions per round of the backward (20 KB of LDS: occupancy is set by registers)
 
 template <bool EXACT>
-__global__ void __launch_bounds__(SGR_OA_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
+__global__ void __launch_bounds__(SGR_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
 sgr_object_alpha_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H, int gx, int gy,
                             const float4* __restrict__ rec, uint32_t split, float* __restrict__ out_alpha,
                             uint32_t* __restrict__ out_last) {
     // fused multiply-adds are written out (fmaf), as in the forward whose bits this kernel reproduces
 #pragma clang fp contract(off)
-    __shared__ float4 sA[SGR_OA_THREADS];  // {x, y, -, -}
-    __shared__ float4 sB[SGR_OA_THREADS];  // {qa, qb, qc, opacity}
+    __shared__ float4 sA[SGR_TILE_THREADS];  // {x, y, -, -}
+    __shared__ float4 sB[SGR_TILE_THREADS];  // {qa, qb, qc, opacity}
     __shared__ uint64_t sBits[4][4];       // [quadrant][chunk of 64 entries]: survivors of the cull
     __shared__ uint32_t sDone[4];          // [wave]: all 64 pixels are finished
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t tx, ty;
-    if (!sgr_wg_tile(blockIdx.x, gx, gy, ranges, tx, ty)) return;  // whole workgroup: padding block
-    const uint32_t tile = ty * (uint32_t)gx + tx;
-    const uint32_t px = tx * SGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const uint32_t py = ty * SGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < (uint32_t)W && py < (uint32_t)H;
-    const float pxf = (float)px, pyf = (float)py;
-    const uint2 range = ranges[tile];
+    SgrTilePixel tp;
+    if (!sgr_tile_pixel(tp, gx, gy, ranges)) return;
+    const int tid = tp.tid, lane = tp.lane, wave = tp.wave;
+    const bool inside = tp.inside(W, H);
+    const uint2 range = ranges[tp.tile];
 
     float T = 1.0f, Wt = 0.f;
     uint32_t last = 0;
     // finished pixels (outside the image, or T exhausted): the wave's scalar lane mask and the per-lane alpha threshold that
-    // becomes +inf (sgr_blend_layers.hip:69-74)
+    // becomes +inf (sgr_blend_begin)
     uint64_t done_mask = sgr_uniform_u64(__builtin_amdgcn_ballot_w64(!inside));
     float thr = inside ? SGR_ALPHA_MIN : __builtin_inff();
-    const float tx0 = (float)(tx * SGR_BLOCK_X), ty0 = (float)(ty * SGR_BLOCK_Y);
+    const float tx0 = tp.tx0(), ty0 = tp.ty0();
 
-    for (uint32_t base = range.x; base < range.y; base += SGR_OA_THREADS) {
+    for (uint32_t base = range.x; base < range.y; base += SGR_TILE_THREADS) {
         // tile-wide state; also the barrier that protects LDS reuse
         if (lane == 0) sDone[wave] = done_mask == ~0ull ? 1u : 0u;
         __syncthreads();
@@ -73,81 +67,37 @@ sgr_object_alpha_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             const float4 a = r[0];
             const float4 b = r[1];
             sA[tid] = a;
-            sB[tid] = EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w) : sgr_stage_conic(b);
+            sB[tid] = sgr_stage_conic_mode<EXACT>(b);
             mask4 = sgr_quadrant_mask(a, b, tx0, ty0);
         }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint64_t m = __ballot((mask4 >> q) & 1u);
-            if (lane == 0) sBits[q][wave] = m;
-        }
+        sgr_store_cull_ballots(mask4, lane, wave, sBits);
         __syncthreads();
 
         const uint32_t pos0 = base - range.x + 1u;  // 1-based position of slot 0 inside the tile's range
-        // one blend step (forward.cu:425-445; sgr_blend_layers.hip:82-104 without the colour sums)
-        auto blend_one = [&](uint64_t& m, const int j, const float power2, const float alpha) __attribute__((always_inline)) {
-            const bool k1 = !(power2 > 0.0f), k2 = !(alpha < thr);
-            const uint64_t hm = __builtin_amdgcn_ballot_w64(k1) & __builtin_amdgcn_ballot_w64(k2);
-            if (hm == 0) return;
-            const float test_T = T * (1.0f - alpha);
-            const bool k3 = test_T < 0.0001f;  // forward.cu:431-436
-            const uint64_t k3m = __builtin_amdgcn_ballot_w64(k3);
-            const bool blends = k1 && k2 && !k3;
-            const float w = blends ? alpha * T : 0.0f;
-            Wt += w;
-            T = blends ? test_T : T;
-            last = blends ? pos0 + (uint32_t)j : last;
-            const uint64_t sm = hm & k3m;
-            if (sm != 0) {
-                thr = (k1 && k2 && k3) ? __builtin_inff() : thr;
-                done_mask |= sm;
-                if (done_mask == ~0ull) m = 0;
-            }
-        };
         if (done_mask != ~0ull) {
             for (int chunk = 0; chunk < 4; chunk++) {
                 uint64_t m = sgr_uniform_u64(sBits[wave][chunk]);
-                if (__builtin_popcountll(m) & 1) {  // odd one out first, so that the loop below is pairs only
-                    const int j0 = chunk * 64 + sgr_pop_lowest(m);
-                    const float4 a0 = sA[j0], q0 = sB[j0];
-                    const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf)
-                                            : sgr_power2(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf);
-                    blend_one(m, j0, pw0, fminf(0.99f, q0.w * (EXACT ? sgr_expf_ref(pw0) : __builtin_amdgcn_exp2f(pw0))));
-                }
-                while (m) {
-                    const int j0 = chunk * 64 + sgr_pop_lowest(m);
-                    const int j1 = chunk * 64 + sgr_pop_lowest(m);
-                    const float4 a0 = sA[j0], q0 = sB[j0];
-                    const float4 a1 = sA[j1], q1 = sB[j1];
-                    const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf)
-                                            : sgr_power2(q0.x, q0.y, q0.z, a0.x - pxf, a0.y - pyf);
-                    const float pw1 = EXACT ? sgr_power_ref_staged(q1.x, q1.y, q1.z, a1.x - pxf, a1.y - pyf)
-                                            : sgr_power2(q1.x, q1.y, q1.z, a1.x - pxf, a1.y - pyf);
-                    const float al0 = fminf(0.99f, q0.w * (EXACT ? sgr_expf_ref(pw0) : __builtin_amdgcn_exp2f(pw0)));
-                    const float al1 = fminf(0.99f, q1.w * (EXACT ? sgr_expf_ref(pw1) : __builtin_amdgcn_exp2f(pw1)));
-                    blend_one(m, j0, pw0, al0);
-                    blend_one(m, j1, pw1, al1);  // if the wave finished on j0 every lane's threshold is +inf: a no-op
-                }
+                sgr_walk_pairs<EXACT, false>(m, chunk, sA, sB, tp.pxf, tp.pyf, [&](const SgrVisit& v) __attribute__((always_inline)) {
+                    SgrBlendStep<true> b;
+                    if (!sgr_blend_begin(b, T, thr, v.power, v.alpha)) return;
+                    Wt += b.w;
+                    sgr_blend_end(b, T, thr, done_mask, m);
+                    last = b.sel(pos0 + (uint32_t)v.j, last);
+                });
                 if (done_mask == ~0ull) break;
             }
         }
     }
 
     if (inside) {
-        const size_t pix_id = (size_t)W * py + px;
+        const size_t pix_id = (size_t)W * tp.py + tp.px;
         out_alpha[pix_id] = Wt;
         out_last[pix_id] = last;
     }
 }
 
-// __syncthreads() preceded by an explicit LDS drain (sgr_blend_bwd.hip: sgr_lds_barrier)
-__device__ __forceinline__ void sgr_oa_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
 template <bool EXACT>
-__global__ void __launch_bounds__(SGR_OA_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
+__global__ void __launch_bounds__(SGR_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
 sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H, int gx, int gy,
                             const float4* __restrict__ rec, const uint32_t* __restrict__ u0, const uint64_t* __restrict__ tmask,
                             uint32_t split, const float* __restrict__ layer_alpha, const uint32_t* __restrict__ layer_last,
@@ -164,16 +114,13 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
     // [quadrant][slot][S gx, S gy, S abs, S gxx, S gxy, S gyy, S Gd, -]: one writer per element, read only where sVis says so
     __shared__ __attribute__((aligned(16))) float sAcc[4][BATCH][8];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t tx, ty;
-    if (!sgr_wg_tile(blockIdx.x, gx, gy, ranges, tx, ty)) return;  // whole workgroup: padding block
-    const uint32_t tile = ty * (uint32_t)gx + tx;
-    const uint32_t px = tx * SGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const uint32_t py = ty * SGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < (uint32_t)W && py < (uint32_t)H;
-    const float pxf = (float)px, pyf = (float)py;
-    const size_t pix_id = (size_t)W * py + px;
-    const uint2 range = ranges[tile];
+    SgrTilePixel tp;
+    if (!sgr_tile_pixel(tp, gx, gy, ranges)) return;
+    const int tid = tp.tid, lane = tp.lane, wave = tp.wave;
+    const uint32_t tx = tp.tx, ty = tp.ty;
+    const bool inside = tp.inside(W, H);
+    const size_t pix_id = (size_t)W * tp.py + tp.px;
+    const uint2 range = ranges[tp.tile];
     const int len = (int)(range.y - range.x);
 
     // backward.cu:466-500 for the layer: T_final = 1 - alpha, the layer's own last contributor
@@ -189,9 +136,9 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
     if (lane == 0) sMax[wave] = mx;
-    sgr_oa_barrier();
+    sgr_lds_barrier();
     const int maxc = max(max(sMax[0], sMax[1]), max(sMax[2], sMax[3]));
-    const float tx0 = (float)(tx * SGR_BLOCK_X), ty0 = (float)(ty * SGR_BLOCK_Y);
+    const float tx0 = tp.tx0(), ty0 = tp.ty0();
     // sgr_wave_reduce_fold<8>: the first lane of banks 0 and 2 of every 16-lane row k holds the wave total of value
     // 4 t + {0, 2, 1, 3}[k], t = 0 for bank 0 and 1 for bank 2 -- eight lanes, eight values
     const int fold_bank = (lane >> 2) & 3;
@@ -200,7 +147,7 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
 
     for (int hi = maxc - 1; hi >= 0; hi -= BATCH) {
         // slot t of this round holds list position hi - t (descending: back to front)
-        sgr_oa_barrier();  // previous round fully consumed before LDS is overwritten
+        sgr_lds_barrier();  // previous round fully consumed before LDS is overwritten
         const bool stager = tid < BATCH;  // whole waves
         const int pos = stager ? hi - tid : -1;
         uint32_t mask4 = 0;
@@ -210,25 +157,21 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             const float4 a = r[0];
             const float4 b = r[1];
             const float4 d4 = r[3];
-            sB[tid] = EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w) : sgr_stage_conic(b);
+            sB[tid] = sgr_stage_conic_mode<EXACT>(b);
             const uint32_t urow = sgr_row_of(__float_as_uint(d4.y), tx, ty, u0, tmask, g);
             sA[tid] = make_float4(a.x, a.y, __uint_as_float(urow), 0.0f);
             mask4 = sgr_quadrant_mask(a, b, tx0, ty0);
             // lazy forward whose frame had more instances than the list capacity: rows past the array are not visited
             if (urow >= row_limit) mask4 = 0;
         }
-        if (stager) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint64_t m = __ballot((mask4 >> q) & 1u);
-                if (lane == 0) sBits[q][wave] = m;
-            }
-        }
-        sgr_oa_barrier();
+        if (stager) sgr_store_cull_ballots(mask4, lane, wave, sBits);
+        sgr_lds_barrier();
 
         uint64_t vis = 0;  // the slots of the current chunk this wave wrote a row for (scalar)
-        auto process = [&](const int j, const float4 q, const float dx, const float dy, const float power2, const float G,
-                           const float alpha) __attribute__((always_inline)) {
+        auto process = [&](const SgrVisit& vt) __attribute__((always_inline)) {
+            const int j = vt.j;
+            const float4 q = vt.q;
+            const float dx = vt.dx, dy = vt.dy, power2 = vt.power, G = vt.G, alpha = vt.alpha;
             const int posj = hi - j;  // 0-based list position
             // backward.cu:527-545 (pixels outside the image have lastc = 0)
             const bool k0 = posj < lastc, k1 = !(power2 > 0.0f), k2 = !(alpha < SGR_ALPHA_MIN);
@@ -238,7 +181,7 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             float Gd = 0.0f;  // G * dL/dopa: zero off the hit lanes
             if (k0 && k1 && k2) {
                 const float oma = 1.0f - alpha;
-                T = T * __builtin_amdgcn_rcpf(oma);  // T = T / (1 - alpha) (backward.cu:547), as sgr_blend_bwd.hip
+                T = T * __builtin_amdgcn_rcpf(oma);  // T = T / (1 - alpha) (backward.cu:547), as the blend backward
                 accA = fmaf(1.0f - last_alpha, accA, last_alpha);
                 last_alpha = alpha;
                 Gd = G * (((1.0f - accA) * dLdA) * T);
@@ -263,41 +206,13 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             sgr_wave_reduce_fold<8>(v, r);
             if (fold_writer) sAcc[wave][j][fold_val] = r[0];
         };
-        // parity mode: G = exp(power), power in natural-log units, with the guard of sgr_blend_bwd.hip (SGR_EXACT_BWD_FAST): a
-        // visit with any pixel whose alpha lands within 4e-6 (relative) of 1/255 takes the accurate expf for the whole wave
-        auto exactG = [&](const float pw, const float opac) __attribute__((always_inline)) -> float {
-            float gg = __builtin_amdgcn_exp2f(pw * SGR_LOG2E);
-            const bool near = fabsf(opac * gg - SGR_ALPHA_MIN) <= 4.0e-6f * SGR_ALPHA_MIN;
-            if (__builtin_amdgcn_ballot_w64(near) != 0) gg = sgr_expf_ref(pw);
-            return gg;
-        };
         for (int chunk = 0; chunk < NCH; chunk++) {
             uint64_t m = sgr_uniform_u64(sBits[wave][chunk]);
-            if (__builtin_popcountll(m) & 1) {
-                const int j0 = chunk * 64 + sgr_pop_lowest(m);
-                const float4 a0 = sA[j0], q0 = sB[j0];
-                const float dx0 = a0.x - pxf, dy0 = a0.y - pyf;
-                const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, dx0, dy0) : sgr_power2(q0.x, q0.y, q0.z, dx0, dy0);
-                const float G0 = EXACT ? exactG(pw0, q0.w) : __builtin_amdgcn_exp2f(pw0);
-                process(j0, q0, dx0, dy0, pw0, G0, fminf(0.99f, q0.w * G0));
-            }
-            while (m) {
-                const int j0 = chunk * 64 + sgr_pop_lowest(m);
-                const int j1 = chunk * 64 + sgr_pop_lowest(m);
-                const float4 a0 = sA[j0], q0 = sB[j0];
-                const float4 a1 = sA[j1], q1 = sB[j1];
-                const float dx0 = a0.x - pxf, dy0 = a0.y - pyf, dx1 = a1.x - pxf, dy1 = a1.y - pyf;
-                const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, dx0, dy0) : sgr_power2(q0.x, q0.y, q0.z, dx0, dy0);
-                const float pw1 = EXACT ? sgr_power_ref_staged(q1.x, q1.y, q1.z, dx1, dy1) : sgr_power2(q1.x, q1.y, q1.z, dx1, dy1);
-                const float G0 = EXACT ? exactG(pw0, q0.w) : __builtin_amdgcn_exp2f(pw0);
-                const float G1 = EXACT ? exactG(pw1, q1.w) : __builtin_amdgcn_exp2f(pw1);
-                process(j0, q0, dx0, dy0, pw0, G0, fminf(0.99f, q0.w * G0));
-                process(j1, q1, dx1, dy1, pw1, G1, fminf(0.99f, q1.w * G1));
-            }
+            sgr_walk_pairs<EXACT, true>(m, chunk, sA, sB, tp.pxf, tp.pyf, process);
             if (lane == 0) sVis[wave][chunk] = vis;
             vis = 0;
         }
-        sgr_oa_barrier();
+        sgr_lds_barrier();
         // One row per (tile, instance) some quadrant was asked to visit, written exactly once (a row of zeros when every
         // visit found no pixel): the rows of the quadrants that visited the slot, added in quadrant order
         if (mask4 != 0) {
@@ -311,7 +226,7 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
                     s[4] += t1.x; s[5] += t1.y; s[6] += t1.z;
                 }
             }
-            // moments -> gradients, the shipped flush (sgr_blend_bwd.hip:784-794): dL_dG = opacity * dL/dopa is constant per
+            // moments -> gradients as the flush of sgr_blend_bwd_body does it: dL_dG = opacity * dL/dopa is constant per
             // instance (backward.cu:616-635)
             const float4 qq = sB[tid];
             const float qw = qq.w, hq = -0.5f * qq.w;
@@ -333,9 +248,9 @@ void sgr_launch_object_alpha_fwd(bool exact, int gx, int gy, const uint2* ranges
     if (gx <= 0 || gy == 0) return;
     const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
     if (exact)
-        sgr_object_alpha_fwd_kernel<true><<<tiles, SGR_OA_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, out_alpha, out_last);
+        sgr_object_alpha_fwd_kernel<true><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, out_alpha, out_last);
     else
-        sgr_object_alpha_fwd_kernel<false><<<tiles, SGR_OA_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, out_alpha, out_last);
+        sgr_object_alpha_fwd_kernel<false><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, out_alpha, out_last);
 }
 
 // row_stride: sgr_partial_row_stride(0) = 12 floats (three float4 stores per row)
@@ -346,9 +261,9 @@ void sgr_launch_object_alpha_bwd(bool exact, int gx, int gy, const uint2* ranges
     if (gx <= 0 || gy == 0) return;
     const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);
     if (exact)
-        sgr_object_alpha_bwd_kernel<true><<<tiles, SGR_OA_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, u0, tmask, (uint32_t)split,
+        sgr_object_alpha_bwd_kernel<true><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, u0, tmask, (uint32_t)split,
                                                                            layer_alpha, layer_last, dL_dlayer_alpha, partials, row_stride, touched, row_limit);
     else
-        sgr_object_alpha_bwd_kernel<false><<<tiles, SGR_OA_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, u0, tmask, (uint32_t)split,
+        sgr_object_alpha_bwd_kernel<false><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, u0, tmask, (uint32_t)split,
                                                                             layer_alpha, layer_last, dL_dlayer_alpha, partials, row_stride, touched, row_limit);
 }
