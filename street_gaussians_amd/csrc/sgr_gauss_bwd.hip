@@ -21,12 +21,30 @@
 #ifndef SGR_RS_LANES
 #define SGR_RS_LANES 4  // lanes that share one Gaussian's partial rows in the row-sum stage (4 or 8)
 #endif
+#ifndef SGR_RS_INFLIGHT
+#define SGR_RS_INFLIGHT 3  // rows a lane has in flight per Gaussian in the row-sum stage (S = 0): 3 fit the 64 registers of eight
+                           // waves / SIMD, 4 spill; 2: the flag -> row pairs of before
+#endif
+#ifndef SGR_RS_WAVES
+#define SGR_RS_WAVES 8  // waves / SIMD the register allocation of that instantiation is held to (1: no bound)
+#endif
+#ifndef SGR_RS_PAIR
+#define SGR_RS_PAIR 0  // 1: a quad walks TWO Gaussians (2k, 2k + 1) side by side in the row-sum stage (S = 0)
+#endif
+// Gaussians per quad / rows in flight of one instantiation: the channel-carrying ones (SMAX > 0, up to 44 registers per
+// row) and the QUAD form keep the two-rows-in-flight walk
+template <int SMAX, bool QUAD> constexpr int sgr_rs_pair = (!QUAD && SMAX == 0) ? SGR_RS_PAIR + 1 : 1;
+template <int SMAX, bool QUAD> constexpr int sgr_rs_inflight = (!QUAD && SMAX == 0) ? SGR_RS_INFLIGHT : 2;
+template <int SMAX, bool QUAD> constexpr int sgr_rs_waves = (!QUAD && SMAX == 0) ? SGR_RS_WAVES : 1;
 
 // ---- stage 1: sum the partial rows ---------------------------------------------------------------------------
 // A latency-bound gather (flag byte -> 48..176-byte row; n rows per Gaussian, n between 1 and hundreds), so it lives
 // in its own kernel with few registers (8 waves / SIMD; the fused kernel had 4 because of the SH arrays) and FOUR
-// LANES PER GAUSSIAN: lane q of a quad sums rows q, q+4, q+8, ... (two in flight), then the quad's four partial sums
-// are combined with two quad_perm DPP steps.  The order of the additions is fixed -> deterministic.
+// LANES PER GAUSSIAN: lane q of a quad sums rows q, q+4, q+8, ... (S = 0: three in flight behind one request of their flag
+// bytes; otherwise flag -> row pairs, two in flight), then the quad's four partial sums are combined with two quad_perm
+// DPP steps.  The order of the additions is fixed and the same in every form -> deterministic, bit-identical.
+// A/B forms (tools/build_variant.py): -DSGR_RS_INFLIGHT=2 the walk before, =4 -DSGR_RS_WAVES=7 four in
+// flight at seven waves, -DSGR_RS_PAIR=1 two Gaussians per quad (measured slower in every combination).
 // Writes the outputs that come straight from the blend backward (backward.cu:568-638) and hands the conic / depth
 // terms to stage 2 through `cd`.
 // QUAD: the rows of the scalar-walk blend backward (sgr_blend_bwd_sw.hip) -- FOUR rows per (tile, instance), one per
@@ -36,26 +54,108 @@
 // kx, ky = 0.5 * W / lsc, 0.5 * H / lsc with lsc = log2(e), or 1 in parity mode (`exact`: the staged conic is then
 // (-0.5 cx, -cy, -0.5 cz) instead of the log2(e)-scaled one in rec[3]).
 template <int SMAX, bool QUAD>
-__global__ void __launch_bounds__(SGR_GB_THREADS)
+__global__ void __launch_bounds__(SGR_GB_THREADS) __attribute__((amdgpu_waves_per_eu(sgr_rs_waves<SMAX, QUAD>)))
 sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, const float* __restrict__ partials,
                    int row_stride, const uint8_t* __restrict__ touched, float* __restrict__ dL_dmean2D,
                    float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ dL_dsemantic,
                    float4* __restrict__ cd, SgrStatSink sink, float kx, float ky, int exact, uint32_t row_limit,
                    float* __restrict__ masked_out) {
     constexpr int NV = (SGR_ROW_BASE_N + SMAX + 3) / 4;
+    constexpr int G = sgr_rs_pair<SMAX, QUAD>, R = sgr_rs_inflight<SMAX, QUAD>;
     const int gtid = blockIdx.x * SGR_GB_THREADS + threadIdx.x;
-    const int idx = gtid / SGR_RS_LANES, q = gtid % SGR_RS_LANES;
-    float acc[4 * NV];
-#pragma unroll
-    for (int k = 0; k < 4 * NV; k++) acc[k] = 0.f;
-    const bool live = idx < P;  // P need not be a multiple of 16: keep whole quads alive for the DPP steps
-    // tiles_touched is 0 for a culled Gaussian, so the row walk needs no look at the radius: the two loads below go out
+    const int idx0 = (gtid / SGR_RS_LANES) * G, q = gtid % SGR_RS_LANES;
+    float accs[G][4 * NV];
+    bool lives[G];
+    uint32_t ns[G], u0s[G];
+    // tiles_touched is 0 for a culled Gaussian, so the row walk needs no look at the radius: the loads below go out
     // together and the dependent chain is {u0, n} -> flag -> row
-    uint32_t n = live ? gv.aux[idx].x : 0u;
-    const uint32_t u0 = live ? gv.u0[idx] : 0u;  // defined for every Gaussian (exclusive scan)
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+#pragma unroll
+        for (int k = 0; k < 4 * NV; k++) accs[g][k] = 0.f;
+        lives[g] = idx0 + g < P;  // P need not be a multiple of 16: keep whole quads alive for the DPP steps
+        ns[g] = lives[g] ? gv.aux[idx0 + g].x : 0u;
+        u0s[g] = lives[g] ? gv.u0[idx0 + g] : 0u;  // defined for every Gaussian (exclusive scan)
+    }
     // rows past the array's end exist only after a lazy forward that overflowed its list capacity (sgr_set_lazy): the
     // blend backward did not write them and they are not read (that frame's results are discarded, one call later)
-    n = min(n, row_limit - min(u0, row_limit));
+#pragma unroll
+    for (int g = 0; g < G; g++) ns[g] = min(ns[g], row_limit - min(u0s[g], row_limit));
+    float (&acc)[4 * NV] = accs[0];  // (the two-in-flight forms: one Gaussian per quad)
+    const int idx = idx0;
+    const uint32_t n = ns[0], u0 = u0s[0];
+    if constexpr (G > 1 || R != 2) {
+        // Flags first, rows together: a lane asks for the flag bytes of its next R rows (q, q + 4, ...) of each Gaussian in one go,
+        // then for every touched row among them, and adds them in ascending order -- the additions of the two-in-flight walk.
+        // Three trips to memory for a Gaussian of up to 4 R rows ({u0, n} -> flags -> rows); longer ones loop, the next
+        // trip's flags riding with this trip's rows.  Rows never written by the blend backward hold garbage: load under the flag.
+        // Registers (64 = eight waves / SIMD): a trip's flags are one bit each of a word per Gaussian, and the last float4 of a
+        // row is asked for without the words no accumulator takes (11 floats at S = 0: 8 + 3 words).
+        constexpr int TAIL = (SGR_ROW_BASE_N + SMAX) - 4 * (NV - 1);  // floats used of a row's last float4 (1..4)
+        const uint8_t* flag[G];
+        const float* rows[G];
+        uint32_t f[G], nmax = 0;
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            flag[g] = touched + u0s[g];
+            rows[g] = partials + (size_t)u0s[g] * row_stride;
+            nmax = max(nmax, ns[g]);
+        }
+        // the flag bytes of the trip that starts at row i, all requested before the first is looked at
+        auto trip_flags = [&](uint32_t i, uint32_t (&out)[G]) __attribute__((always_inline)) {
+            uint8_t b[G][R];
+#pragma unroll
+            for (int g = 0; g < G; g++)
+#pragma unroll
+                for (int k = 0; k < R; k++) {
+                    b[g][k] = 0;
+                    if (i + SGR_RS_LANES * k < ns[g]) b[g][k] = flag[g][i + SGR_RS_LANES * k];
+                }
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+                out[g] = 0u;
+#pragma unroll
+                for (int k = 0; k < R; k++) out[g] |= b[g][k] ? 1u << k : 0u;
+            }
+        };
+        trip_flags((uint32_t)q, f);
+        for (uint32_t i = (uint32_t)q; i < nmax; i += R * SGR_RS_LANES) {
+            float4 t[G][R][NV];
+            uint32_t fn[G];
+#pragma unroll
+            for (int g = 0; g < G; g++)
+#pragma unroll
+                for (int k = 0; k < R; k++)
+                    if ((f[g] >> k) & 1u) {
+                        const float* rf = rows[g] + (size_t)(i + SGR_RS_LANES * k) * row_stride;
+                        const float4* r = reinterpret_cast<const float4*>(rf);
+#pragma unroll
+                        for (int k4 = 0; k4 < NV - 1; k4++) t[g][k][k4] = r[k4];
+                        if constexpr (TAIL == 3) {
+                            const float2 lo = *reinterpret_cast<const float2*>(rf + 4 * (NV - 1));
+                            t[g][k][NV - 1] = make_float4(lo.x, lo.y, rf[4 * (NV - 1) + 2], 0.f);
+                        } else t[g][k][NV - 1] = r[NV - 1];
+                    }
+            trip_flags(i + R * SGR_RS_LANES, fn);  // (none for a Gaussian of up to 4 R rows)
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+#pragma unroll
+                for (int k = 0; k < R; k++)
+                    if ((f[g] >> k) & 1u) {
+#pragma unroll
+                        for (int e = 0; e < SGR_ROW_BASE_N + SMAX; e++) {
+                            const float4& v = t[g][k][e >> 2];
+                            accs[g][e] += (e & 3) == 0 ? v.x : (e & 3) == 1 ? v.y : (e & 3) == 2 ? v.z : v.w;
+                        }
+                    }
+                f[g] = fn[g];
+            }
+            // nothing is in flight past this point (the next trip's flags are needed now): said out loud, because the
+            // compiler's wait-count bookkeeping otherwise carries this trip's conditional loads around the loop as "maybe
+            // pending" and drains the queue in front of every row request of the next trip -- one row in flight
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        }
+    } else
     if (n && QUAD) {
         const uint8_t* flag = touched + u0;
         const float* rows = partials + (size_t)u0 * 4u * row_stride;
@@ -109,14 +209,17 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
             add_row(t);
         }
     }
-    // (q0 + q1) + (q2 + q3) in every lane of the quad
+    // (q0 + q1) + (q2 + q3) in every lane of the quad (every lane of the wave is still here), each Gaussian on its own
 #pragma unroll
-    for (int k = 0; k < 4 * NV; k++) {
-        acc[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc[k]), 0xB1, 0xF, 0xF, false));
-        acc[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc[k]), 0x4E, 0xF, 0xF, false));
-        if (SGR_RS_LANES == 8)  // row_half_mirror: lane i <-> 7 - i, i.e. the other quad of the 8-lane group
-            acc[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc[k]), 0x141, 0xF, 0xF, false));
-    }
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int k = 0; k < 4 * NV; k++) {
+            float& a = accs[g][k];
+            a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0xB1, 0xF, 0xF, false));
+            a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0x4E, 0xF, 0xF, false));
+            if (SGR_RS_LANES == 8)  // row_half_mirror: lane i <-> 7 - i, i.e. the other quad of the 8-lane group
+                a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0x141, 0xF, 0xF, false));
+        }
     if (QUAD && n) {
         // moments -> gradients (sgr_blend_bwd.hip's flush, per Gaussian instead of per (tile, instance))
 #pragma clang fp contract(off)
@@ -131,56 +234,62 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
         acc[4] = hq * acc[4];                             // dL/dconic.y
         acc[5] = hq * acc[5];                             // dL/dconic.w
     }
-    if (!live) return;
-    // the quad shares the stores
-    if (q == 0) {
-        dL_dmean2D[3 * idx + 0] = acc[0];
-        dL_dmean2D[3 * idx + 1] = acc[1];
-        dL_dmean2D[3 * idx + 2] = acc[2];
-        // densification statistics of this view (set_max_radii2D + add_densification_stats,
-        // street_gaussian_model.py:551-571) while dL/dmean2D and the radius are in registers: visibility = radii > 0
-        const int r = radii[idx];
-        if (sink.accum != nullptr && r > 0) {
-#pragma clang fp contract(off)
-            // persistent row of this Gaussian: identity, or through the frame's segment map (binary search over the
-            // segment starts, kernel arguments -> scalar loads)
-            long row = idx;
-            if (sink.nseg > 0) {
-                int lo = 0, hi = sink.nseg - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (sink.start[mid] <= idx) lo = mid; else hi = mid - 1;
-                }
-                row = (idx >= sink.start[lo] && idx < sink.start[lo] + sink.count[lo]) ? (long)idx + sink.shift[lo] : -1;
-            }
-            if (row >= 0) {
-                sink.accum[2 * (size_t)row] += sqrtf(acc[0] * acc[0] + acc[1] * acc[1]);  // norm of grad[:, :2]
-                sink.accum[2 * (size_t)row + 1] += fabsf(acc[2]);                          // norm of grad[:, 2:]
-                sink.denom[row] += 1.0f;
-                sink.max_radii[row] = fmaxf(sink.max_radii[row], (float)r);
-            }
-        }
-    } else if (q == 1) {
-        dL_dopacity[idx] = acc[6];
-        dL_dcolor[3 * idx + 0] = acc[7];
-        dL_dcolor[3 * idx + 1] = acc[8];
-        dL_dcolor[3 * idx + 2] = acc[9];
-        if (masked_out != nullptr) {
-            // sgr_backward_extras.masked_color_out: the colour gradient that reaches the SH coefficients (backward.cu:40-44:
-            // channels the forward clamped at zero get none) -- the payload of the view-sharded exchange, written here
-            // instead of by a launch of its own (sgr_masked_color_grad)
-            const uint32_t cl = n ? gv.clamped[idx] : 0u;  // (culled Gaussians: acc = 0 anyway, `clamped` is not written for them)
-            masked_out[3 * idx + 0] = (cl & 1u) ? 0.f : acc[7];
-            masked_out[3 * idx + 1] = (cl & 2u) ? 0.f : acc[8];
-            masked_out[3 * idx + 2] = (cl & 4u) ? 0.f : acc[9];
-        }
-    } else if (q == 2) {
-        cd[idx] = make_float4(acc[3], acc[4], acc[5], acc[10]);
-    }
-    if (SMAX > 0) {
 #pragma unroll
-        for (int ch = 0; ch < SMAX; ch++)
-            if (ch < S && (ch & 3) == (q & 3) && q < 4) dL_dsemantic[(size_t)idx * S + ch] = acc[SGR_ROW_BASE_N + ch];
+    for (int g = 0; g < G; g++) {
+        if (!lives[g]) continue;
+        const int idx = idx0 + g;
+        const uint32_t n = ns[g];
+        const float (&acc)[4 * NV] = accs[g];
+        // the quad shares the stores
+        if (q == 0) {
+            dL_dmean2D[3 * idx + 0] = acc[0];
+            dL_dmean2D[3 * idx + 1] = acc[1];
+            dL_dmean2D[3 * idx + 2] = acc[2];
+            // densification statistics of this view (set_max_radii2D + add_densification_stats,
+            // street_gaussian_model.py:551-571) while dL/dmean2D and the radius are in registers: visibility = radii > 0
+            const int r = radii[idx];
+            if (sink.accum != nullptr && r > 0) {
+#pragma clang fp contract(off)
+                // persistent row of this Gaussian: identity, or through the frame's segment map (binary search over the
+                // segment starts, kernel arguments -> scalar loads)
+                long row = idx;
+                if (sink.nseg > 0) {
+                    int lo = 0, hi = sink.nseg - 1;
+                    while (lo < hi) {
+                        const int mid = (lo + hi + 1) >> 1;
+                        if (sink.start[mid] <= idx) lo = mid; else hi = mid - 1;
+                    }
+                    row = (idx >= sink.start[lo] && idx < sink.start[lo] + sink.count[lo]) ? (long)idx + sink.shift[lo] : -1;
+                }
+                if (row >= 0) {
+                    sink.accum[2 * (size_t)row] += sqrtf(acc[0] * acc[0] + acc[1] * acc[1]);  // norm of grad[:, :2]
+                    sink.accum[2 * (size_t)row + 1] += fabsf(acc[2]);                          // norm of grad[:, 2:]
+                    sink.denom[row] += 1.0f;
+                    sink.max_radii[row] = fmaxf(sink.max_radii[row], (float)r);
+                }
+            }
+        } else if (q == 1) {
+            dL_dopacity[idx] = acc[6];
+            dL_dcolor[3 * idx + 0] = acc[7];
+            dL_dcolor[3 * idx + 1] = acc[8];
+            dL_dcolor[3 * idx + 2] = acc[9];
+            if (masked_out != nullptr) {
+                // sgr_backward_extras.masked_color_out: the colour gradient that reaches the SH coefficients (backward.cu:40-44:
+                // channels the forward clamped at zero get none) -- the payload of the view-sharded exchange, written here
+                // instead of by a launch of its own (sgr_masked_color_grad)
+                const uint32_t cl = n ? gv.clamped[idx] : 0u;  // (culled Gaussians: acc = 0 anyway, `clamped` is not written for them)
+                masked_out[3 * idx + 0] = (cl & 1u) ? 0.f : acc[7];
+                masked_out[3 * idx + 1] = (cl & 2u) ? 0.f : acc[8];
+                masked_out[3 * idx + 2] = (cl & 4u) ? 0.f : acc[9];
+            }
+        } else if (q == 2) {
+            cd[idx] = make_float4(acc[3], acc[4], acc[5], acc[10]);
+        }
+        if (SMAX > 0) {
+#pragma unroll
+            for (int ch = 0; ch < SMAX; ch++)
+                if (ch < S && (ch & 3) == (q & 3) && q < 4) dL_dsemantic[(size_t)idx * S + ch] = acc[SGR_ROW_BASE_N + ch];
+        }
     }
 }
 
@@ -329,6 +438,9 @@ sgr_row_sum_wave_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView
 #ifndef SGR_GB_WAVES
 #define SGR_GB_WAVES 1
 #endif
+#ifndef SGR_GB_HOIST
+#define SGR_GB_HOIST 1  // 1: what stage 2 reads per Gaussian is requested together with the radius; 0: behind `radius > 0`
+#endif
 __global__ void __launch_bounds__(SGR_GB_THREADS) __attribute__((amdgpu_waves_per_eu(SGR_GB_WAVES)))
 sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, const int* __restrict__ radii,
                      const float* __restrict__ shs, const float* __restrict__ scales,
@@ -342,7 +454,11 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
     const int gidx = blockIdx.x * SGR_GB_THREADS + threadIdx.x;
     const bool live = gidx < P;
     const int idx = live ? gidx : P - 1;
-    const bool visible = live && radii[idx] > 0;
+    constexpr bool hoist = SGR_GB_HOIST != 0;
+    // (hoist: the radius of the clamped index without a branch around it, so that nothing waits for it before the requests
+    // below have gone out)
+    const int rad_top = hoist ? radii[idx] : 0;
+    const bool visible = hoist ? (live & (rad_top > 0)) : (live && radii[idx] > 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // SH rows of 48 floats (M = 16): the 64 rows of a wave are one contiguous 12 KB block.  Per-lane float4 loads at
     // a 192-byte stride touch 64 cache lines per instruction and were issue-bound (SQ_WAIT_INST_ANY 70 % of the
@@ -362,7 +478,13 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
     float acc[SGR_ROW_BASE_N];
 #pragma unroll
     for (int k = 0; k < SGR_ROW_BASE_N; k++) acc[k] = 0.f;
-    if (visible) {
+    // Stage 1 wrote cd, dL/dmean2D and dL/dcolour for EVERY Gaussian (zeros for culled ones) and scales / rotations are inputs,
+    // so they are requested together with the radius and the mean -- one trip to memory per round of workgroups instead of
+    // two -- and only USED behind `visible` (`clamped` is not written for culled Gaussians: its word is read and dropped;
+    // `jac` and cov3D_precomp stay behind the test).
+    float sc_top[3] = {0.f, 0.f, 0.f}, rot_top[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t cl_top = 0u;
+    if (visible || hoist) {
         const float4 c = cd[idx];
         acc[0] = dL_dmean2D[3 * idx];
         acc[1] = dL_dmean2D[3 * idx + 1];
@@ -371,12 +493,22 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         acc[8] = dL_dcolor[3 * idx + 1];
         acc[9] = dL_dcolor[3 * idx + 2];
     }
+    if (hoist) {
+        if (scales != nullptr) {
+            sc_top[0] = scales[3 * idx]; sc_top[1] = scales[3 * idx + 1]; sc_top[2] = scales[3 * idx + 2];
+            const float4 q = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)idx);
+            rot_top[0] = q.x; rot_top[1] = q.y; rot_top[2] = q.z; rot_top[3] = q.w;
+        }
+        if (shs != nullptr) cl_top = gv.clamped[idx];
+    }
 
     float dmean[3] = {0.f, 0.f, 0.f};
     float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float dscale[3] = {0.f, 0.f, 0.f};
     float drot[4] = {0.f, 0.f, 0.f, 0.f};
-    const float p[3] = {means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]};
+    float p[3] = {means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]};
+    // (the mean is used behind `visible` only and the compiler moves its load there, behind the radius: pinned in front)
+    if (hoist) asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]));
     float dRGB[3] = {0.f, 0.f, 0.f};
     float dir[3] = {0.f, 0.f, 1.f}, dir_orig[3] = {0.f, 0.f, 1.f};
 
@@ -384,7 +516,12 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         // K12: conic -> cov3D and the covariance part of dL/dmean (assigned)
         float cov3D[6];
         float sc[3] = {0.f, 0.f, 0.f}, rot[4] = {0.f, 0.f, 0.f, 0.f};
-        if (scales != nullptr) {
+        if (hoist) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) sc[i] = sc_top[i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) rot[i] = rot_top[i];
+        } else if (scales != nullptr) {
             sc[0] = scales[3 * idx]; sc[1] = scales[3 * idx + 1]; sc[2] = scales[3 * idx + 2];
             const float4 q = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)idx);
             rot[0] = q.x; rot[1] = q.y; rot[2] = q.z; rot[3] = q.w;
@@ -402,7 +539,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         sgr_proj_depth_backward(p, cam, acc[0], acc[1], acc[10], dmean);
         if (scales != nullptr) sgr_cov3d_backward(sc, cam.scale_modifier, rot, dcov, dscale, drot);
         if (shs != nullptr) {
-            const uint32_t cl = gv.clamped[idx];
+            const uint32_t cl = hoist ? cl_top : gv.clamped[idx];
             dRGB[0] = (cl & 1u) ? 0.f : acc[7];
             dRGB[1] = (cl & 2u) ? 0.f : acc[8];
             dRGB[2] = (cl & 4u) ? 0.f : acc[9];
@@ -547,12 +684,12 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
     const float lsc = exact ? 1.0f : SGR_LOG2E;
     const float kx = (0.5f * (float)W) / lsc, ky = (0.5f * (float)H) / lsc;
     const unsigned nb = (P + SGR_GB_THREADS - 1) / SGR_GB_THREADS;
-    const unsigned nb4 = (unsigned)(((size_t)P * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
     // switch bit 9 / SGR_RS_WAVE=1: the wave-cooperative row sum instead of the four-lanes-per-Gaussian one (A/B: measured SLOWER on MI355X --
     // per-Gaussian backward stage 0.258 vs 0.213 ms at 1 M Gaussians, 1.14 vs 0.76 ms at 5 M, 0.83 vs 0.57 ms at 2 M + 19
     // channels: its segmented scan is 13 ds_bpermute per step and row chunk, more than the gather chains it removes)
     // (both A/B forms exist only in a -DSGR_WITH_VARIANTS=1 build: tools/build_variant.py)
 #if SGR_WITH_VARIANTS
+    const unsigned nb4 = (unsigned)(((size_t)P * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
     const bool quads = !rs_wave;  // (sgr_test_switches bit 9)
     const unsigned nbw = (unsigned)((P + 64 * SGR_RSW_WAVES - 1) / (64 * SGR_RSW_WAVES));
     if (quad) {  // the scalar-walk blend backward's rows (S = 0 only)
@@ -568,6 +705,8 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
     (void)quad; (void)rs_wave;
 #endif
     sgr_with_smax(S, [&](auto N) {
+        constexpr int G = sgr_rs_pair<decltype(N)::value, false>;  // Gaussians per quad of this instantiation
+        const unsigned nb4 = (unsigned)((((size_t)P + G - 1) / G * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
         sgr_row_sum_kernel<N, false><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
                                                                    dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink, kx, ky, exact,
                                                                    row_limit, masked_color_out);
