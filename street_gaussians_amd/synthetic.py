@@ -68,6 +68,43 @@ def make_camera(width: int = 1920, height: int = 1280, fx: float = 2050.0, fy: O
     return Camera(height, width, tanfovx, tanfovy, view_t.float(), proj_t.float(), campos.float().contiguous())
 
 
+def projection_matrix_K(K, width: int, height: int, znear: float, zfar: float) -> torch.Tensor:
+    """getProjectionMatrixK of the reference (lib/utils/graphics_utils.py:72-94), column-vector form, float64:
+    off-centre principal point, fx != fy, the skew slot, and an OpenGL-style z row (unlike projection_matrix's)."""
+    K = torch.as_tensor(K, dtype=torch.float64)
+    fx, fy, cx, cy, s = K[0, 0], K[1, 1], K[0, 2], K[1, 2], K[0, 1]
+    P = torch.zeros(4, 4, dtype=torch.float64)
+    P[0, 0] = 2.0 * fx / width
+    P[0, 1] = 2.0 * s / width
+    P[0, 2] = -1.0 + 2.0 * (cx / width)
+    P[1, 1] = 2.0 * fy / height
+    P[1, 2] = -1.0 + 2.0 * (cy / height)
+    P[2, 2] = (zfar + znear) / (zfar - znear)
+    P[2, 3] = -2.0 * zfar * znear / (zfar - znear)
+    P[3, 2] = 1.0
+    return P
+
+
+def make_camera_general(width: int, height: int, K, R_w2c, t_w2c, znear: float = 0.001, zfar: float = 1000.0) -> Camera:
+    """The camera the reference's ``Camera`` hands to the rasterizer (/root/reference/lib/utils/camera_utils.py:50-61) for an
+    arbitrary world-to-camera pose ``x_cam = R_w2c @ x_world + t_w2c`` and intrinsics ``K`` (3x3, pixels):
+    ``world_view_transform = W2C.T``, ``full_proj_transform = W2C.T @ P.T`` with P from K (projection_matrix_K),
+    ``camera_center = inv(W2C)[:3, 3]`` and, as lib/utils/graphics_utils.py:99-100 makes the FoV from the focal lengths,
+    ``tanfov = size / (2 f)`` -- the rasterizer's clamp stays symmetric about the principal point's ray although the image
+    is not.  Restated in float64 with one cast to float32 at the end, as make_camera does."""
+    K = torch.as_tensor(K, dtype=torch.float64)
+    W2C = torch.eye(4, dtype=torch.float64)
+    W2C[:3, :3] = torch.as_tensor(R_w2c, dtype=torch.float64)
+    W2C[:3, 3] = torch.as_tensor(t_w2c, dtype=torch.float64)
+    P = projection_matrix_K(K, width, height, znear, zfar)
+    view_t = W2C.t().contiguous()
+    proj_t = (W2C.t() @ P.t()).contiguous()
+    campos = torch.linalg.inv(W2C)[:3, 3]
+    tanfovx = width / (2.0 * float(K[0, 0]))
+    tanfovy = height / (2.0 * float(K[1, 1]))
+    return Camera(height, width, tanfovx, tanfovy, view_t.float(), proj_t.float(), campos.float().contiguous())
+
+
 @dataclass
 class Scene:
     means3D: torch.Tensor    # [P,3]
@@ -102,6 +139,47 @@ def make_scene(P: int, cam: Camera, sh_degree_max: int = 3, S: int = 0, seed: in
     x = z * cam.tanfovx * ux
     y = z * cam.tanfovy * uy
     means = torch.stack([x, y, z], dim=1).float()
+    logs = torch.log(scale_px * z)[:, None] + scale_sigma * torch.randn(P, 3, generator=g, dtype=torch.float64)
+    scales = torch.exp(logs).float()
+    q = torch.randn(P, 4, generator=g, dtype=torch.float64)
+    q = (q / q.norm(dim=1, keepdim=True)).float()
+    opac = torch.sigmoid(2.0 * torch.randn(P, 1, generator=g, dtype=torch.float64)).float()
+    M = (sh_degree_max + 1) ** 2
+    shs = 0.3 * torch.randn(P, M, 3, generator=g, dtype=torch.float64)
+    if M > 1:
+        shs[:, 1:, :] *= 0.3
+    shs[:, 0, :] += 0.5  # DC offset
+    sem = torch.randn(P, S, generator=g, dtype=torch.float64).float()
+    return Scene(means.contiguous(), scales.contiguous(), q.contiguous(), opac.contiguous(),
+                 shs.float().contiguous(), sem.contiguous())
+
+
+def make_scene_in_view(P: int, cam: Camera, K, R_w2c, t_w2c, sh_degree_max: int = 3, S: int = 0, seed: int = 0,
+                       zmin: float = 1.0, zmax: float = 80.0, scale_px: float = 0.0015, scale_sigma: float = 0.6,
+                       margin: float = 1.1, behind_every: int = 0) -> Scene:
+    """make_scene for a camera of make_camera_general, whose frustum is neither axis-aligned nor centred: pixel positions
+    uniform over the image rectangle enlarged by ``margin`` about the principal point, depths uniform in 1/z over
+    [zmin, zmax]; unprojected through K (skew included) and moved to the world with the float64 inverse of the pose
+    ``x_cam = R_w2c @ x_world + t_w2c``.  Everything else is drawn as make_scene draws it, in the same order from the same
+    generator.  ``behind_every`` = n > 0 mirrors every n-th Gaussian (indices n-1, 2n-1, ...) through the camera centre, so
+    that it lies behind the camera (no further draw is made for it)."""
+    K = torch.as_tensor(K, dtype=torch.float64)
+    R = torch.as_tensor(R_w2c, dtype=torch.float64)
+    t = torch.as_tensor(t_w2c, dtype=torch.float64)
+    W, H = cam.image_width, cam.image_height
+    fx, fy, cx, cy, skew = K[0, 0], K[1, 1], K[0, 2], K[1, 2], K[0, 1]
+    g = torch.Generator().manual_seed(seed)
+    u = torch.rand(P, generator=g, dtype=torch.float64)
+    inv_z = 1.0 / zmax + u * (1.0 / zmin - 1.0 / zmax)
+    z = 1.0 / inv_z
+    px = cx + margin * (torch.rand(P, generator=g, dtype=torch.float64) * W - cx)
+    py = cy + margin * (torch.rand(P, generator=g, dtype=torch.float64) * H - cy)
+    yz = (py - cy) / fy
+    xz = (px - cx - skew * yz) / fx
+    p_cam = torch.stack([xz * z, yz * z, z], dim=1)
+    if behind_every > 0:
+        p_cam[behind_every - 1::behind_every] = -p_cam[behind_every - 1::behind_every]
+    means = ((p_cam - t[None]) @ R).float()  # R^T (x_cam - t), row-vector form
     logs = torch.log(scale_px * z)[:, None] + scale_sigma * torch.randn(P, 3, generator=g, dtype=torch.float64)
     scales = torch.exp(logs).float()
     q = torch.randn(P, 4, generator=g, dtype=torch.float64)

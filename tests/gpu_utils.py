@@ -257,6 +257,33 @@ def exact_mode_against_reference_kernels(kw, wts, S, label, rf=None, gref=None, 
     return res, g
 
 
+def exact_mode_bit_faithful(ref, oracle, kw, wts, S, label=""):
+    """The three-way statement of test_exact_parity_mode_is_bit_faithful_to_the_reference_kernels for one call: the library
+    in its parity mode against oracle/_ref's strict build (`ref`) -- alpha, depth and the semantic image BIT-IDENTICAL,
+    n_contrib identical, colour within rel 1e-6 without an outlier, every gradient inside north_star's gate end to end --
+    and against the C oracle (`oracle`, the host's libm expf): alpha within rel 2e-6 without an outlier."""
+    rf = ref.forward(**kw)
+    gref = ref.backward(rf, wts["color"], wts["depth"], wts["alpha"], wts["semantic"] if S else None)
+    fw = oracle.forward(**kw)
+    with switches(_C.EXACT):
+        res, internal = raw_forward(kw)
+        g = raw_backward(kw, res, wts)
+        torch.cuda.synchronize()
+    for k in ["alpha", "depth"] + (["semantic"] if S else []):
+        assert torch.equal(res[k], getattr(rf, k)), (label, k)
+    b = restrict_oracle(internal, rf, kw)  # (n_contrib counts the instances of the emitted tile rects)
+    assert np.array_equal(npy(internal("n_contrib")).view(np.uint32).reshape(-1), b.n_contrib.reshape(-1)), label
+    image_close(npy(res["color"]), npy(rf.color), rel=1e-6, name=f"exact color vs ref{label}", max_outliers=0)
+    image_close(npy(res["alpha"]), fw.alpha, rel=2e-6, name=f"exact alpha vs oracle{label}", max_outliers=0)
+    for k in GRAD_NAMES:
+        if k == "semantics" and not S:
+            continue
+        strict_gate(npy(g[k]).reshape(-1), npy(gref[k]).reshape(-1), name=f"exact end-to-end {k} vs ref{label}",
+                    allow=conditioned_allowance(k, g[k].numel()))
+    rf.free()
+    fw.free()
+
+
 # Backward on identical inputs (oracle_backward_same_state): |a-b| <= 1e-4*max(|a|,|b|) + 2e-6*max|b|.  The few
 # elements outside are single (pixel, Gaussian) alpha-threshold flips (v_exp_f32 vs expf); measured on MI355X
 # (profiles/r2/parity_measured.jsonl) and gated just above.

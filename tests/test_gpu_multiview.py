@@ -24,11 +24,16 @@ def _views(V):
 
 @pytest.mark.parametrize("deg", [3, 1])
 def test_factored_sh_gradient_equals_sum_over_views(deg):
-    from diff_gaussian_rasterization import GaussianRasterizer
-    V = 3
-    cams = _views(V)
+    cams = _views(3)
     sc = syn.make_scene(20000, cams[0], S=0, seed=11)
     sc.shs[::3, 0, :] -= 2.0  # plenty of clamped channels
+    factored_equals_sum_over_views(cams, sc, deg)
+
+
+def factored_equals_sum_over_views(cams, sc, deg):
+    """The factored exchange over the views `cams` of scene `sc` against plain autograd accumulation over the same views."""
+    from diff_gaussian_rasterization import GaussianRasterizer
+    V = len(cams)
     t = {k: dev(getattr(sc, k)).requires_grad_(True) for k in ["means3D", "scales", "rotations", "opacities", "shs"]}
 
     def run_views():

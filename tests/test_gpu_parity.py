@@ -25,7 +25,8 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_utils import (SAME_STATE_GATE, conditioned_allowance, dev, exact_mode_against_reference_kernels, grad_close,
+from gpu_utils import (SAME_STATE_GATE, conditioned_allowance, dev, exact_mode_against_reference_kernels,
+                       exact_mode_bit_faithful, grad_close,
                        image_close, npy, oracle_backward_same_state, raw_backward, raw_forward, restrict_binning, restrict_oracle,
                        settings, strict_gate, strict_mode_against_reference, switches)
 from street_gaussians_amd import _C
@@ -1258,26 +1259,4 @@ def test_exact_parity_mode_is_bit_faithful_to_the_reference_kernels(S):
     cam = syn.make_camera(320, 208, fx=340.0, yaw_deg=2.0)
     sc = syn.make_scene(15000, cam, S=S, seed=21, scale_px=0.004)
     kw = oracle_kwargs(cam, sc, bg=torch.tensor([0.3, 0.1, 0.2]))
-    wts = syn.loss_weights(cam, S=S)
-    rf = ref.forward(**kw)
-    gref = ref.backward(rf, wts["color"], wts["depth"], wts["alpha"], wts["semantic"] if S else None)
-    fw = oracle.forward(**kw)
-    with switches(_C.EXACT):
-        res, internal = raw_forward(kw)
-        g = raw_backward(kw, res, wts)
-        torch.cuda.synchronize()
-    for k in ["alpha", "depth"] + (["semantic"] if S else []):
-        assert torch.equal(res[k], getattr(rf, k)), k
-    b = restrict_oracle(internal, rf, kw)  # (n_contrib counts the instances of the emitted tile rects)
-    assert np.array_equal(npy(internal("n_contrib")).view(np.uint32).reshape(-1), b.n_contrib.reshape(-1))
-    image_close(npy(res["color"]), npy(rf.color), rel=1e-6, name="exact color vs ref", max_outliers=0)
-    image_close(npy(res["alpha"]), fw.alpha, rel=2e-6, name="exact alpha vs oracle", max_outliers=0)
-    names = {"means2D": "means2D", "colors": "colors", "opacity": "opacity", "means3D": "means3D", "cov3D": "cov3D", "sh": "sh",
-             "scales": "scales", "rotations": "rotations", "semantics": "semantics"}
-    for k in GRAD_KEYS:
-        if k == "semantics" and not S:
-            continue
-        strict_gate(npy(g[k]).reshape(-1), npy(gref[names[k]]).reshape(-1), name=f"exact end-to-end {k} vs ref",
-                    allow=conditioned_allowance(k, g[k].numel()))
-    rf.free()
-    fw.free()
+    exact_mode_bit_faithful(ref, oracle, kw, syn.loss_weights(cam, S=S), S)

@@ -1,6 +1,7 @@
 """The maths header the gfx950 kernels run (street_gaussians_amd/csrc/sgr_math.h), compiled for the
 host, against the oracle: integer outputs and the geometry floats must be BIT-EXACT (contraction is
-off on both sides), per-Gaussian gradients within 1e-4.  No GPU needed."""
+off on both sides), per-Gaussian gradients within 1e-4 -- under the yawed make_camera and under every general camera of
+tests/cameras.py (pitch, roll, off-centre K, z-up basis, skew, a far translation).  No GPU needed."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import cameras
 from helpers import assert_close, oracle_kwargs, small_case
 from oracle import oracle
 from street_gaussians_amd import synthetic as syn
@@ -39,12 +41,8 @@ def _f(t):
     return np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32)
 
 
-@pytest.mark.parametrize("deg,margin,scale_px", [(3, 1.1, 0.01), (1, 1.7, 0.03), (0, 1.1, 0.002)])
-def test_forward_geometry_bit_exact_and_backward_close(hm, deg, margin, scale_px):
-    cam = syn.make_camera(200, 120, fx=210.0, yaw_deg=7.0, translation=(0.1, -0.05, 0.3))
-    sc = syn.make_scene(5000, cam, S=0, seed=11, margin=margin, zmin=0.15, zmax=30.0, scale_px=scale_px)
-    sc.shs[::3, 0, :] -= 2.5  # some clamped colours
-    fw = oracle.forward(**oracle_kwargs(cam, sc, deg=deg))
+def _hm_forward(hm, cam, sc, deg):
+    """hm_forward over a scene -> dict of its output arrays."""
     P, M = sc.P, sc.shs.shape[1]
     W, H = cam.image_width, cam.image_height
     means, scales, rots, opac, shs = map(_f, (sc.means3D, sc.scales, sc.rotations, sc.opacities, sc.shs))
@@ -55,6 +53,35 @@ def test_forward_geometry_bit_exact_and_backward_close(hm, deg, margin, scale_px
     hm.hm_forward(P, deg, M, _p(means), _p(scales), _p(rots), _p(opac), _p(shs), _p(view), _p(proj), _p(campos),
                   C.c_float(cam.tanfovx), C.c_float(cam.tanfovy), W, H, C.c_float(1.0), _p(radii), _p(m2d), _p(depths),
                   _p(conic), _p(cov3D), _p(tiles), _p(rgb), _p(clamped), _p(ext))
+    return dict(radii=radii, m2d=m2d, depths=depths, conic=conic, cov3D=cov3D, tiles=tiles, rgb=rgb, clamped=clamped, ext=ext)
+
+
+GEOMETRY = [(3, 1.1, 0.01), (1, 1.7, 0.03), (0, 1.1, 0.002)]
+# the yawed make_camera (ids as before the camera parameter) and every camera of tests/cameras.py, `far` included: both
+# sides are float32 with contraction off, so bit equality does not depend on the conditioning of view . p + t
+GEOMETRY_CASES = [(d, m, s, None) for d, m, s in GEOMETRY] + [(d, m, s, c) for c in cameras.NAMES for d, m, s in GEOMETRY]
+
+
+def _geometry_case(camera, margin, scale_px):
+    if camera is None:
+        cam = syn.make_camera(200, 120, fx=210.0, yaw_deg=7.0, translation=(0.1, -0.05, 0.3))
+        return cam, syn.make_scene(5000, cam, S=0, seed=11, margin=margin, zmin=0.15, zmax=30.0, scale_px=scale_px)
+    return cameras.scene(camera, 5000, 200, 120, fx=210.0, S=0, seed=11, margin=margin, zmin=0.15, zmax=30.0, scale_px=scale_px)
+
+
+@pytest.mark.parametrize("deg,margin,scale_px,camera", GEOMETRY_CASES,
+                         ids=[f"{d}-{m}-{s}" + (f"-{c}" if c else "") for d, m, s, c in GEOMETRY_CASES])
+def test_forward_geometry_bit_exact_and_backward_close(hm, deg, margin, scale_px, camera):
+    cam, sc = _geometry_case(camera, margin, scale_px)
+    sc.shs[::3, 0, :] -= 2.5  # some clamped colours
+    fw = oracle.forward(**oracle_kwargs(cam, sc, deg=deg))
+    P, M = sc.P, sc.shs.shape[1]
+    W, H = cam.image_width, cam.image_height
+    means, scales, rots, opac, shs = map(_f, (sc.means3D, sc.scales, sc.rotations, sc.opacities, sc.shs))
+    view, proj, campos = map(_f, (cam.viewmatrix, cam.projmatrix, cam.campos))
+    out = _hm_forward(hm, cam, sc, deg)
+    radii, m2d, depths, conic, cov3D, tiles, rgb, clamped, ext = (out[k] for k in ("radii", "m2d", "depths", "conic", "cov3D",
+                                                                                   "tiles", "rgb", "clamped", "ext"))
     vis = fw.radii > 0
     assert vis.sum() > 1000 and (~vis).sum() > 10
     assert (radii == fw.radii).all()
@@ -274,3 +301,31 @@ def test_tile_mask_row_form_never_drops_a_needed_tile_for_extreme_splats(hm):
         assert not (need & ~bits).any(), (i, m2[i], co[i], rects[i], hex(int(masks[i])))
         needed_total += int(need.sum())
     assert needed_total > n // 4  # the sweep does exercise tiles that are needed
+
+
+def test_general_constructor_reproduces_make_camera_and_no_output_reads_the_z_column(hm):
+    """synthetic.make_camera_general with a centred K, fx = fy and a yaw-only pose IS make_camera: viewmatrix and campos
+    bit for bit, the x, y and w columns of projmatrix within one float32 ulp (2 fx / W against znear / (tanfov znear)).  The z
+    column differs by design (the reference's K-projection has another z row and znear): the maths header must not read
+    it, so overwriting it with NaN changes no output of hm_forward."""
+    W, H, fx, yaw, t = 200, 120, 210.0, 7.0, (0.1, -0.05, 0.3)
+    old = syn.make_camera(W, H, fx=fx, yaw_deg=yaw, translation=t)
+    new = syn.make_camera_general(W, H, cameras.intrinsics(W, H, fx), cameras.rotation(yaw_deg=yaw), t)
+    bits = lambda a: a.contiguous().numpy().view(np.uint32)
+    assert np.array_equal(bits(new.viewmatrix), bits(old.viewmatrix))
+    assert np.array_equal(bits(new.campos), bits(old.campos))
+    assert new.tanfovx == old.tanfovx and new.tanfovy == old.tanfovy
+    a, b = new.projmatrix.reshape(-1).numpy(), old.projmatrix.reshape(-1).numpy()
+    xyw = [0, 1, 3, 4, 5, 7, 8, 9, 11, 12, 13, 15]
+    assert (np.abs(a[xyw] - b[xyw]) <= np.spacing(np.abs(b[xyw]))).all(), a[xyw] - b[xyw]
+    assert (a[[2, 6, 10, 14]] != b[[2, 6, 10, 14]]).any()
+    cam, sc = cameras.scene("general", 2000, W, H, fx=fx, S=0, seed=11, margin=1.6, zmin=0.15, zmax=30.0, scale_px=0.01)
+    want = _hm_forward(hm, cam, sc, 3)
+    assert (want["radii"] > 0).sum() > 500
+    poisoned = cam.projmatrix.clone().reshape(-1)
+    poisoned[[2, 6, 10, 14]] = float("nan")
+    cam_nan = syn.Camera(cam.image_height, cam.image_width, cam.tanfovx, cam.tanfovy, cam.viewmatrix,
+                         poisoned.reshape(4, 4), cam.campos)
+    got = _hm_forward(hm, cam_nan, sc, 3)
+    for k in want:
+        assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k

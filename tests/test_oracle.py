@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import cameras
 import torch_ref as tr
 from helpers import oracle_kwargs, small_case
 from oracle import oracle
@@ -26,13 +27,31 @@ CASES = {
 }
 
 
-@pytest.mark.parametrize("name", list(CASES))
-def test_oracle_matches_float64_autograd(name):
+# every case under small_case's yawed make_camera (ids as before the camera parameter) and under the general cameras of
+# tests/cameras.py.  `far` is not here: at t = (30, -4, 55) the float32 reference itself leaves these float64 gates (float32
+# cancellation in view . p + t); what holds there is stated bitwise in test_host_math.py and the -m gpu camera tests
+ORACLE_CAMERAS = [None, "pitch", "roll", "offcentre", "general", "zup", "skewed"]
+CAMERA_CASES = [(n, c) for c in ORACLE_CAMERAS for n in CASES]
+
+
+def _case(skw, opt, camera):
+    if camera is None:
+        cam, sc = small_case(**skw)
+        if "margin" in opt:
+            sc = syn.make_scene(skw["P"], cam, S=skw["S"], margin=opt["margin"], zmin=1.0, zmax=20.0,
+                                scale_px=skw.get("scale_px", 0.004))
+        return cam, sc
+    # small_case's image, focal length and scene parameters, the scene placed in the general camera's view
+    kw = dict(skw)
+    P = kw.pop("P")
+    return cameras.scene(camera, P, 48, 40, zmin=1.0, **{"zmax": 20.0, "scale_px": 0.004, **kw},
+                         **({"margin": opt["margin"]} if "margin" in opt else {}))
+
+
+@pytest.mark.parametrize("name,camera", CAMERA_CASES, ids=[n + (f"-{c}" if c else "") for n, c in CAMERA_CASES])
+def test_oracle_matches_float64_autograd(name, camera):
     skw, opt = CASES[name]
-    cam, sc = small_case(**skw)
-    if "margin" in opt:
-        sc = syn.make_scene(skw["P"], cam, S=skw["S"], margin=opt["margin"], zmin=1.0, zmax=20.0,
-                            scale_px=skw.get("scale_px", 0.004))
+    cam, sc = _case(skw, opt, camera)
     if opt.get("neg_dc"):
         sc.shs[:, 0, :] -= 1.2
     # boost opacity for the saturating case so that `done` triggers
