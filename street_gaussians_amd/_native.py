@@ -73,6 +73,7 @@ def _signatures():
         "sgr_scene_compose_backward": (i, [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
         "sgr_scene_compose_forward_ex": (i, [i, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
         "sgr_scene_compose_backward_ex": (i, [i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, ALLOC_FN, vp, vp]),
+        "sgr_scene_compose_backward_step": (i, [i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, d, d, f, ALLOC_FN, vp, vp]),
         "sgr_scene_densification_stats": (i, [i, vp, vp, vp, ALLOC_FN, vp, vp]),
         "sgr_ssim_workspace_floats": (sz, [i, i, i]),
         "sgr_ssim_forward": (i, [i, i, i, vp, vp, vp, vp, vp, vp, vp]),

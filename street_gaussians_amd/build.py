@@ -28,7 +28,7 @@ HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_math.h", "sgr_tile_walk.h
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h"),
            os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_object_alpha.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h"), os.path.join("..", "..", "include", "sgr_frame_loss.h"),
-           os.path.join("..", "..", "include", "sgr_sky_step.h")]
+           os.path.join("..", "..", "include", "sgr_sky_step.h"), os.path.join("..", "..", "include", "sgr_scene_step.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 ops into v_pk_* and pays for it with v_mov
 # shuffles; measured on MI355X it costs 6 % in the blend backward and 7 % in the per-Gaussian backward.
 # -mllvm -enable-post-misched=0: without the post-RA machine scheduler the blend kernels keep the order they were

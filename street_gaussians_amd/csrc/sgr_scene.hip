@@ -13,6 +13,8 @@
 //     Per frame (include/sgr_scene_frame.h): the camera pose correction of the static segments, whose gradient is the
 //     same 16-sum reduction over the background (thousands of chunks: two fixed-order levels instead of one wave), and
 //     zero spans for the gradient blocks of the models absent from the frame.
+// n12 the backward kernels in a second flavour (STEP = 1) whose sink is the optimiser (include/sgr_scene_step.h): where
+//     the plain flavour stores g into a gradient array, it applies adam1(p, g, m, v) to that element.
 // n2  densification statistics scattered back per model in one pass (street_gaussian_model.py:551-571).
 #include <cstring>
 #include <string>
@@ -20,6 +22,8 @@
 
 #include "../../include/sgr_scene.h"
 #include "../../include/sgr_scene_frame.h"
+#include "../../include/sgr_scene_step.h"
+#include "sgr_adam_math.h"
 #include "sgr_common.h"
 
 #define SGR_SC_THREADS 256
@@ -198,17 +202,63 @@ sgr_scene_sh_fwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __
     }
 }
 
+// ---- n12: the sink of a gradient value (include/sgr_scene_step.h) -------------------------------------------------
+// SGR_SINK(grad, param, group, e, g).  STEP = 0: g is stored at grad[e].  STEP = 1: element e of the group's block takes
+// one Adam step with g (adam1 keeps contraction off in its own body: a multiply that formed g stays a multiply and g
+// enters rounded to f32 as the plain flavour stores it).  The lane's last read of param[e] comes before the sink.
+struct SgrStepArgs {
+    const sgr_scene_step* steps;  // parallel to the segment table
+    AdamConsts k;
+    float eps;
+};
+// the group's record, read once per use site (uniform: scalar loads); nothing is read in the plain flavour
+template <int STEP>
+__device__ __forceinline__ sgr_scene_step_group sink_group(const sgr_scene_step_group* sp, int group) {
+    if constexpr (STEP) return sp[group];
+    else return sgr_scene_step_group{nullptr, nullptr, 0.f, 0.f};
+}
+// the record of the block that starts b elements into the group's
+template <int STEP>
+__device__ __forceinline__ sgr_scene_step_group sink_at(sgr_scene_step_group sg, size_t b) {
+    if constexpr (STEP) { sg.m += b; sg.v += b; }
+    return sg;
+}
+template <int STEP>
+__device__ __forceinline__ bool sink_wants(const float* grad, const sgr_scene_step_group& sg) {
+    return STEP ? sg.m != nullptr : grad != nullptr;
+}
+__device__ __forceinline__ void sink_step(const float* param, const sgr_scene_step_group& sg, const SgrStepArgs& a, size_t e,
+                                          float g) {
+    float* pp = const_cast<float*>(param) + e;
+    float p = *pp, m = sg.m[e], v = sg.v[e];
+    adam1(p, g, m, v, a.k, sg.step_size, sg.bc2_sqrt, a.eps);
+    *pp = p;
+    sg.m[e] = m;
+    sg.v[e] = v;
+}
+// one source text for the value in both flavours; the plain flavour's statement is the store it has always been
+#define SGR_SINK(grad, param, group, e, value)                        \
+    do {                                                              \
+        if constexpr (STEP) sink_step(param, group, sa, e, value);    \
+        else (grad)[e] = value;                                       \
+    } while (0)
+
 // ---- backward: small attributes + per-chunk pose partials ------------------------------------------------------
+template <int STEP>
 __global__ void __launch_bounds__(SGR_SC_THREADS)
 sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __restrict__ segs, int S,
                      const float* __restrict__ dmeans, const float* __restrict__ drot, const float* __restrict__ dscale,
                      const float* __restrict__ dopac, const float* __restrict__ dsem, float* __restrict__ partials,
-                     const float* __restrict__ corr, float* __restrict__ cpart) {
+                     const float* __restrict__ corr, float* __restrict__ cpart, const SgrStepArgs sa) {
     __shared__ float red[SGR_SC_THREADS / 64][SGR_SC_NPART];
     const SgrChunk c = chunks[blockIdx.x];
     const SgrSegDev& sd = segs[c.seg];
     const sgr_scene_segment& sg = sd.s;
     const sgr_scene_segment_grads& gr = sd.g;
+    const sgr_scene_step_group* sp = STEP ? sa.steps[c.seg].group : nullptr;
+    const sgr_scene_step_group kxyz = sink_group<STEP>(sp, SGR_STEP_XYZ), krot = sink_group<STEP>(sp, SGR_STEP_ROTATION),
+                               kscl = sink_group<STEP>(sp, SGR_STEP_SCALING), kopa = sink_group<STEP>(sp, SGR_STEP_OPACITY),
+                               ksem = sink_group<STEP>(sp, SGR_STEP_SEMANTIC);
     const bool live = (int)threadIdx.x < c.n;
     const size_t i = (size_t)c.start + (live ? threadIdx.x : 0), o = (size_t)c.out + (live ? threadIdx.x : 0);
     float part[SGR_SC_NPART];
@@ -274,30 +324,47 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
             part[12] = dqc.w; part[13] = dqc.x; part[14] = dqc.y; part[15] = dqc.z;
             dq = qmul(qconj(k.qc), dq);           // d(a b)/db . dO = a* dO
         }
-        if (gr.xyz) { gr.xyz[3 * i] = dx[0]; gr.xyz[3 * i + 1] = dx[1]; gr.xyz[3 * i + 2] = dx[2]; }
-        if (gr.rotation) {
+        if (sink_wants<STEP>(gr.xyz, kxyz)) {
+            SGR_SINK(gr.xyz, sg.xyz, kxyz, 3 * i, dx[0]);
+            SGR_SINK(gr.xyz, sg.xyz, kxyz, 3 * i + 1, dx[1]);
+            SGR_SINK(gr.xyz, sg.xyz, kxyz, 3 * i + 2, dx[2]);
+        }
+        if (sink_wants<STEP>(gr.rotation, krot)) {
             const Q4 d = qnormalize_bwd(ql0, n, dq, clamped);
-            *reinterpret_cast<float4*>(gr.rotation + 4 * i) = make_float4(d.w, d.x, d.y, d.z);
+            if constexpr (STEP) {  // the row as float4, like the plain store: p is the row read above
+                const sgr_scene_step_group& sgp = krot;
+                float4 p = qr, m = *reinterpret_cast<const float4*>(sgp.m + 4 * i), v = *reinterpret_cast<const float4*>(sgp.v + 4 * i);
+                adam1(p.x, d.w, m.x, v.x, sa.k, sgp.step_size, sgp.bc2_sqrt, sa.eps);
+                adam1(p.y, d.x, m.y, v.y, sa.k, sgp.step_size, sgp.bc2_sqrt, sa.eps);
+                adam1(p.z, d.y, m.z, v.z, sa.k, sgp.step_size, sgp.bc2_sqrt, sa.eps);
+                adam1(p.w, d.z, m.w, v.w, sa.k, sgp.step_size, sgp.bc2_sqrt, sa.eps);
+                *reinterpret_cast<float4*>(const_cast<float*>(sg.rotation) + 4 * i) = p;
+                *reinterpret_cast<float4*>(sgp.m + 4 * i) = m;
+                *reinterpret_cast<float4*>(sgp.v + 4 * i) = v;
+            } else {
+                *reinterpret_cast<float4*>(gr.rotation + 4 * i) = make_float4(d.w, d.x, d.y, d.z);
+            }
         }
-        if (gr.scaling) {
+        if (sink_wants<STEP>(gr.scaling, kscl)) {
 #pragma unroll
-            for (int k = 0; k < 3; k++) gr.scaling[3 * i + k] = (dscale ? dscale[3 * o + k] : 0.f) * expf(sg.scaling[3 * i + k]);
+            for (int k = 0; k < 3; k++)  // element k is read before it is written, and only by this lane
+                SGR_SINK(gr.scaling, sg.scaling, kscl, 3 * i + k, (dscale ? dscale[3 * o + k] : 0.f) * expf(sg.scaling[3 * i + k]));
         }
-        if (gr.opacity) {
+        if (sink_wants<STEP>(gr.opacity, kopa)) {
             const float sgm = sigmoidf_(sg.opacity[i]);
-            gr.opacity[i] = (dopac ? dopac[o] : 0.f) * sgm * (1.f - sgm);
+            SGR_SINK(gr.opacity, sg.opacity, kopa, i, (dopac ? dopac[o] : 0.f) * sgm * (1.f - sgm));
         }
-        if (gr.semantic && sg.semantic) {
+        if (sink_wants<STEP>(gr.semantic, ksem) && sg.semantic) {
             if (S <= 0 || !dsem) {
                 const int cols = sg.kind == SGR_SEG_ACTOR ? 1 : S;
-                for (int k = 0; k < cols; k++) gr.semantic[i * (size_t)cols + k] = 0.f;
+                for (int k = 0; k < cols; k++) SGR_SINK(gr.semantic, sg.semantic, ksem, i * (size_t)cols + k, 0.f);
             } else if (sg.kind == SGR_SEG_ACTOR) {
                 float d = (sg.class_label >= 0 && sg.class_label < S) ? dsem[o * (size_t)S + sg.class_label] : 0.f;
                 if (sg.sem_mode == SGR_SEM_PROBABILITIES) {
                     const float sgm = sigmoidf_(sg.semantic[i]);
                     d *= sgm * (1.f - sgm);
                 }
-                gr.semantic[i] = d;
+                SGR_SINK(gr.semantic, sg.semantic, ksem, i, d);
             } else if (sg.sem_mode == SGR_SEM_PROBABILITIES) {
                 const float* in = sg.semantic + i * (size_t)S;
                 const float* d = dsem + o * (size_t)S;
@@ -306,7 +373,8 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
                 float sum = 0.f, pd = 0.f;
                 for (int k = 0; k < S; k++) sum += expf(in[k] - m);
                 for (int k = 0; k < S; k++) pd += expf(in[k] - m) / sum * d[k];
-                for (int k = 0; k < S; k++) gr.semantic[i * (size_t)S + k] = expf(in[k] - m) / sum * (d[k] - pd);
+                for (int k = 0; k < S; k++)  // in[k] is read for the last time in the iteration that writes element k
+                    SGR_SINK(gr.semantic, sg.semantic, ksem, i * (size_t)S + k, expf(in[k] - m) / sum * (d[k] - pd));
             }  // static logits: copied by the SH kernel, one lane per float
         }
     }
@@ -458,34 +526,45 @@ sgr_scene_zero_kernel(const SgrZeroDev* __restrict__ spans, int n) {
 }
 
 // ---- backward: SH rows, one lane per float of each gradient array ----------------------------------------------
-template <int MC>
+// STEP = 1 steps the element in place of the store (SGR_SINK); the SH rows' gradients read no parameter.
+template <int MC, int STEP>
 __global__ void __launch_bounds__(SGR_SC_THREADS)
 sgr_scene_sh_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __restrict__ segs, int M_, int S,
-                        const float* __restrict__ dshs, const float* __restrict__ dsem) {
+                        const float* __restrict__ dshs, const float* __restrict__ dsem, const SgrStepArgs sa) {
     const SgrChunk c = chunks[blockIdx.x];
     const SgrSegDev& sd = segs[c.seg];
+    const sgr_scene_step_group* sp = STEP ? sa.steps[c.seg].group : nullptr;
     const int M = MC ? MC : M_;
     const int row = 3 * M, rest = 3 * (M - 1), C = sd.s.fourier_dim;
-    if (S > 0 && dsem && sd.g.semantic && sd.s.semantic && sd.s.kind == SGR_SEG_STATIC && sd.s.sem_mode == SGR_SEM_LOGITS) {
+    const sgr_scene_step_group ksem = sink_group<STEP>(sp, SGR_STEP_SEMANTIC), krest = sink_group<STEP>(sp, SGR_STEP_F_REST),
+                               kdc = sink_group<STEP>(sp, SGR_STEP_F_DC);
+    if (S > 0 && dsem && sink_wants<STEP>(sd.g.semantic, ksem) && sd.s.semantic && sd.s.kind == SGR_SEG_STATIC &&
+        sd.s.sem_mode == SGR_SEM_LOGITS) {
         const float* in = dsem + (size_t)c.out * S;
-        float* so = sd.g.semantic + (size_t)c.start * S;
-        for (int e = threadIdx.x; e < c.n * S; e += SGR_SC_THREADS) so[e] = in[e];
+        const size_t b = (size_t)c.start * S;  // the chunk's first element of the segment's block
+        float* so = STEP ? nullptr : sd.g.semantic + b;
+        const sgr_scene_step_group kb = sink_at<STEP>(ksem, b);
+        for (int e = threadIdx.x; e < c.n * S; e += SGR_SC_THREADS) SGR_SINK(so, sd.s.semantic + b, kb, e, in[e]);
     }
     const float* in = dshs + (size_t)c.out * row;
-    if (sd.g.features_rest) {
-        float* out = sd.g.features_rest + (size_t)c.start * rest;
+    if (sink_wants<STEP>(sd.g.features_rest, krest)) {
+        const size_t b = (size_t)c.start * rest;
+        float* out = STEP ? nullptr : sd.g.features_rest + b;
+        const sgr_scene_step_group kb = sink_at<STEP>(krest, b);
         for (int e = threadIdx.x; e < c.n * rest; e += SGR_SC_THREADS) {
             const int g = e / rest, j = e - g * rest;
-            out[e] = dshs ? in[g * row + 3 + j] : 0.f;
+            SGR_SINK(out, sd.s.features_rest + b, kb, e, dshs ? in[g * row + 3 + j] : 0.f);
         }
     }
-    if (sd.g.features_dc) {
-        float* out = sd.g.features_dc + (size_t)c.start * C * 3;
+    if (sink_wants<STEP>(sd.g.features_dc, kdc)) {
+        const size_t b = (size_t)c.start * C * 3;
+        float* out = STEP ? nullptr : sd.g.features_dc + b;
+        const sgr_scene_step_group kb = sink_at<STEP>(kdc, b);
         const bool four = sd.s.kind == SGR_SEG_ACTOR && sd.s.idft;
         for (int e = threadIdx.x; e < c.n * C * 3; e += SGR_SC_THREADS) {
             const int g = e / (C * 3), j = e - g * (C * 3), k = j / 3, ch = j - 3 * k;
             const float d = dshs ? in[g * row + ch] : 0.f;
-            out[e] = four ? d * sd.s.idft[k] : (k == 0 ? d : 0.f);
+            SGR_SINK(out, sd.s.features_dc + b, kb, e, four ? d * sd.s.idft[k] : (k == 0 ? d : 0.f));
         }
     }
 }
@@ -577,29 +656,33 @@ static int stage_get(size_t bytes, SgrPinnedStage** out) {
     return 0;
 }
 
-// uploads [segments | chunks | zero spans] (+ room for partials) into scratch; returns device pointers
+// uploads [segments | chunks | zero spans | step table] (+ room for partials) into scratch; returns device pointers
 template <typename SegDev>
 static int upload(const std::vector<SegDev>& sd, const std::vector<SgrChunk>& chunks, size_t extra_floats,
                   sgr_alloc_fn scratch, void* scratch_user, hipStream_t stream, SegDev** dsegs, SgrChunk** dchunks,
-                  float** dextra, const std::vector<SgrZeroDev>* spans = nullptr, SgrZeroDev** dspans = nullptr) {
+                  float** dextra, const std::vector<SgrZeroDev>* spans = nullptr, SgrZeroDev** dspans = nullptr,
+                  const sgr_scene_step* steps = nullptr, const sgr_scene_step** dsteps = nullptr) {
     const size_t b0 = sgr_align_up(sd.size() * sizeof(SegDev), 256), b1 = sgr_align_up(chunks.size() * sizeof(SgrChunk), 256);
     const size_t b2 = spans ? sgr_align_up(spans->size() * sizeof(SgrZeroDev), 256) : 0;
-    char* base = scratch(b0 + b1 + b2 + extra_floats * sizeof(float) + 512, scratch_user);
+    const size_t b3 = steps ? sgr_align_up(sd.size() * sizeof(sgr_scene_step), 256) : 0;  // parallel to the segments
+    char* base = scratch(b0 + b1 + b2 + b3 + extra_floats * sizeof(float) + 512, scratch_user);
     if (!base) return sgr_set_error(SGR_E_ALLOC, "scene scratch allocation failed");
     base = (char*)sgr_align_up((size_t)base, 256);
     SgrPinnedStage* st;
-    int rc = stage_get(b0 + b1 + b2, &st);
+    int rc = stage_get(b0 + b1 + b2 + b3, &st);
     if (rc) return rc;
     memcpy(st->p, sd.data(), sd.size() * sizeof(SegDev));
     memcpy(st->p + b0, chunks.data(), chunks.size() * sizeof(SgrChunk));
     if (spans) memcpy(st->p + b0 + b1, spans->data(), spans->size() * sizeof(SgrZeroDev));
-    SGR_HIP(hipMemcpyAsync(base, st->p, b0 + b1 + b2, hipMemcpyHostToDevice, stream));
+    if (steps) memcpy(st->p + b0 + b1 + b2, steps, sd.size() * sizeof(sgr_scene_step));
+    SGR_HIP(hipMemcpyAsync(base, st->p, b0 + b1 + b2 + b3, hipMemcpyHostToDevice, stream));
     SGR_HIP(hipEventRecord(st->ev, stream));
     st->pending = true;
     *dsegs = (SegDev*)base;
     *dchunks = (SgrChunk*)(base + b0);
     if (dspans) *dspans = (SgrZeroDev*)(base + b0 + b1);
-    if (dextra) *dextra = (float*)(base + b0 + b1 + b2);
+    if (dsteps) *dsteps = (const sgr_scene_step*)(base + b0 + b1 + b2);
+    if (dextra) *dextra = (float*)(base + b0 + b1 + b2 + b3);
     return 0;
 }
 
@@ -646,13 +729,39 @@ static int compose_forward(int K, const sgr_scene_segment* segs, int M, int S, f
     return 0;
 }
 
+// what sgr_scene_compose_backward_step refuses on top of the plain backward (include/sgr_scene_step.h)
+static int check_steps(int K, const sgr_scene_segment* segs, const sgr_scene_step* steps, const sgr_scene_segment_grads* grads,
+                       double beta1, double beta2) {
+    if (K > 0 && !steps) return sgr_set_error(SGR_E_INVALID, "steps is required");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return sgr_set_error(SGR_E_INVALID, "betas must lie in [0, 1)");
+    for (int k = 0; k < K; k++) {
+        if (grads) {
+            const sgr_scene_segment_grads& g = grads[k];
+            if (g.xyz || g.rotation || g.scaling || g.opacity || g.features_dc || g.features_rest || g.semantic)
+                return sgr_set_error(SGR_E_INVALID, "step sink: grads may carry only .pose (a group is stepped, not written)");
+        }
+        if (segs[k].count == 0) continue;
+        const sgr_scene_segment& s = segs[k];
+        const float* param[SGR_SCENE_STEP_GROUPS] = {s.xyz, s.features_dc, s.features_rest, s.opacity, s.scaling, s.rotation, s.semantic};
+        for (int g = 0; g < SGR_SCENE_STEP_GROUPS; g++) {
+            const sgr_scene_step_group& sg = steps[k].group[g];
+            if (sg.m && (!sg.v || !param[g]))
+                return sgr_set_error(SGR_E_INVALID, "step sink: a stepped group needs exp_avg_sq and its parameter pointer");
+        }
+    }
+    return 0;
+}
+
+// steps == NULL: the plain backward (gradients into `grads`); else the step sink, `grads` NULL or .pose only
 static int compose_backward(int K, const sgr_scene_segment* segs, const sgr_scene_segment_grads* grads, int M, int S,
                             const float* dL_dmeans3D, const float* dL_drotations, const float* dL_dscales,
                             const float* dL_dopacities, const float* dL_dshs, const float* dL_dsemantics,
-                            const sgr_scene_frame* frame, sgr_alloc_fn scratch, void* scratch_user, hipStream_t stream) {
+                            const sgr_scene_frame* frame, sgr_alloc_fn scratch, void* scratch_user, hipStream_t stream,
+                            const sgr_scene_step* steps = nullptr, double beta1 = 0.0, double beta2 = 0.0, float eps = 0.f) {
     int rc = check_segments(K, segs, M, S);
     if (rc) return rc;
-    if (!grads || !scratch) return sgr_set_error(SGR_E_INVALID, "grads and scratch are required");
+    if ((!grads && !steps) || !scratch) return sgr_set_error(SGR_E_INVALID, "grads and scratch are required");
+    if (steps && (rc = check_steps(K, segs, steps, grads, beta1, beta2))) return rc;
     std::vector<SgrZeroDev> spans;
     uint32_t zblocks = 0;
     if ((rc = zero_table(frame, spans, &zblocks))) return rc;
@@ -665,25 +774,34 @@ static int compose_backward(int K, const sgr_scene_segment* segs, const sgr_scen
     std::vector<SgrSegDev> sd(K);
     int nc = 0;  // corrected chunks
     for (int k = 0; k < K; k++) {
-        sd[k].s = segs[k]; sd[k].g = grads[k]; sd[k].first_chunk = first[k]; sd[k].nchunks = count[k]; sd[k].corr_first = -1;
+        sd[k].s = segs[k]; sd[k].g = grads ? grads[k] : sgr_scene_segment_grads{}; sd[k].first_chunk = first[k]; sd[k].nchunks = count[k]; sd[k].corr_first = -1;
         if (corr && segs[k].kind == SGR_SEG_STATIC) { sd[k].corr_first = nc; nc += count[k]; }
     }
     const int ng = (nc + SGR_SC_THREADS - 1) / SGR_SC_THREADS;  // groups of 256 corrected chunks
     const size_t np = chunks.size() * SGR_SC_NPART, ncp = corr_grad ? (size_t)nc * SGR_SC_NPART : 0;
     const size_t ngp = corr_grad ? (size_t)ng * SGR_SC_NPART : 0;
     SgrSegDev* dsegs; SgrChunk* dchunks; float* partials; SgrZeroDev* dspans;
-    if ((rc = upload(sd, chunks, np + ncp + ngp, scratch, scratch_user, stream, &dsegs, &dchunks, &partials, &spans, &dspans)))
+    SgrStepArgs sa{nullptr, AdamConsts{0.f, 0.f, 0.f}, eps};
+    if (steps) sa.k = adam_consts(beta1, beta2);
+    if ((rc = upload(sd, chunks, np + ncp + ngp, scratch, scratch_user, stream, &dsegs, &dchunks, &partials, &spans, &dspans,
+                     steps, &sa.steps)))
         return rc;
     float* cpart = corr_grad ? partials + np : nullptr;
     float* gpart = corr_grad ? partials + np + ncp : nullptr;
     if (zblocks) sgr_scene_zero_kernel<<<zblocks, SGR_SC_THREADS, 0, stream>>>(dspans, (int)spans.size());
     const unsigned nb = (unsigned)chunks.size();
-    if (nb) {
-        sgr_scene_bwd_kernel<<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, dL_dmeans3D, dL_drotations, dL_dscales,
-                                                                dL_dopacities, dL_dsemantics, partials, corr, cpart);
+    if (nb && !steps) {
+        sgr_scene_bwd_kernel<0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, dL_dmeans3D, dL_drotations, dL_dscales,
+                                                                   dL_dopacities, dL_dsemantics, partials, corr, cpart, sa);
         sgr_scene_pose_bwd_kernel<<<(unsigned)K, 64, 0, stream>>>(dsegs, partials);
-        if (M == 16) sgr_scene_sh_bwd_kernel<16><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics);
-        else sgr_scene_sh_bwd_kernel<0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics);
+        if (M == 16) sgr_scene_sh_bwd_kernel<16, 0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics, sa);
+        else sgr_scene_sh_bwd_kernel<0, 0><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics, sa);
+    } else if (nb) {  // the step sink: the same launches, the other flavour
+        sgr_scene_bwd_kernel<1><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, S, dL_dmeans3D, dL_drotations, dL_dscales,
+                                                                   dL_dopacities, dL_dsemantics, partials, corr, cpart, sa);
+        sgr_scene_pose_bwd_kernel<<<(unsigned)K, 64, 0, stream>>>(dsegs, partials);
+        if (M == 16) sgr_scene_sh_bwd_kernel<16, 1><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics, sa);
+        else sgr_scene_sh_bwd_kernel<0, 1><<<nb, SGR_SC_THREADS, 0, stream>>>(dchunks, dsegs, M, S, dL_dshs, dL_dsemantics, sa);
     }
     if (corr_grad) {
         if (ng) sgr_scene_corr_sum_kernel<<<(unsigned)ng, SGR_SC_THREADS, 0, stream>>>(cpart, nc, gpart);
@@ -723,6 +841,19 @@ int sgr_scene_compose_backward_ex(int K, const sgr_scene_segment* segs, const sg
                                   const sgr_scene_frame* frame, sgr_alloc_fn scratch, void* scratch_user, void* stream_) {
     return compose_backward(K, segs, grads, M, S, dL_dmeans3D, dL_drotations, dL_dscales, dL_dopacities, dL_dshs,
                             dL_dsemantics, frame, scratch, scratch_user, (hipStream_t)stream_);
+}
+
+int sgr_scene_compose_backward_step(int K, const sgr_scene_segment* segs, const sgr_scene_step* steps,
+                                    const sgr_scene_segment_grads* grads, int M, int S, const float* dL_dmeans3D,
+                                    const float* dL_drotations, const float* dL_dscales, const float* dL_dopacities,
+                                    const float* dL_dshs, const float* dL_dsemantics, const sgr_scene_frame* frame,
+                                    double beta1, double beta2, float eps, sgr_alloc_fn scratch, void* scratch_user,
+                                    void* stream_) {
+    if (K < 0 || (K > 0 && !steps)) return sgr_set_error(SGR_E_INVALID, "steps is required");
+    static const sgr_scene_step none{};  // K == 0: a frame without a segment still writes its zero spans
+    return compose_backward(K, segs, grads, M, S, dL_dmeans3D, dL_drotations, dL_dscales, dL_dopacities, dL_dshs,
+                            dL_dsemantics, frame, scratch, scratch_user, (hipStream_t)stream_, steps ? steps : &none, beta1,
+                            beta2, eps);
 }
 
 int sgr_scene_densification_stats(int K, const sgr_scene_stats_segment* segs, const float* dL_dmeans2D, const int* radii,

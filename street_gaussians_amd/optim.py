@@ -10,7 +10,9 @@ from a frame gets no gradient, and torch's Adam skips it (no moment decay, no mo
 ``SegmentedAdam`` keeps the learning rate and the step count per (segment, group) and updates every present block of
 every flat leaf in one HIP launch, with the arithmetic of torch's ``_multi_tensor_adam`` (op order in the header).
 Its state reads and writes as ``torch.optim.Adam.state_dict()`` per model, and as the ``(exp_avg, exp_avg_sq)`` pairs
-``densify.densify_and_prune(states=...)`` takes.  There is no CPU implementation: tensors must live on the GPU."""
+``densify.densify_and_prune(states=...)`` takes.  ``sink()`` plans a step that the backward of
+``FlatScene.compose(grad_sink=...)`` applies itself, without gradient tensors (include/sgr_scene_step.h).  There is no
+CPU implementation: tensors must live on the GPU."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -91,6 +93,42 @@ def chunk_table(layout, p: Dict[str, int], m: Dict[str, int], v: Dict[str, int])
     return tab
 
 
+def step_scalars(step: int, lr: float, betas: Tuple[float, float], bc_cache: dict) -> Tuple[float, float]:
+    """(step_size, bc2_sqrt) of one (segment, group) at step count ``step``, in double: ``-(lr / bc1)`` and
+    ``(1 - beta2 ** step) ** 0.5`` (include/sgr_optim.h).  The one definition ``plan_step`` and ``plan_sink`` share;
+    ``bc_cache`` keeps the bias corrections per step count.  The caller rounds to float32."""
+    bc = bc_cache.get(step)
+    if bc is None:
+        bc = bc_cache[step] = bias_corrections(step, *betas)
+    return -(lr / bc[0]), bc[1]
+
+
+def _segment_set(segments: Optional[Sequence[int]], nseg: int, who: str) -> List[int]:
+    if segments is None:
+        return list(range(nseg))
+    segs = sorted({int(s) for s in segments})
+    if segs and (segs[0] < 0 or segs[-1] >= nseg):
+        raise IndexError(f"{who}: segment index out of range [0, {nseg})")
+    return segs
+
+
+def plan_sink(layout, steps: List[Dict[str, int]], lrs: List[Dict[str, float]], segments: Optional[Sequence[int]],
+              groups: Sequence[str], betas: Tuple[float, float], bc_cache: Optional[dict] = None
+              ) -> Dict[Tuple[int, str], Tuple[np.float32, np.float32]]:
+    """{(segment, group): (step_size, bc2_sqrt)} as float32, the scalars ``plan_step(advance=True)`` would put into its
+    records for the same ``segments`` and groups: those of step count + 1.  Every (segment, group) of the set has an
+    entry, an empty block included (its count advances on commit as torch steps an empty parameter).  ``steps`` is only
+    read."""
+    bc_cache = {} if bc_cache is None else bc_cache
+    plan = {}
+    for s in _segment_set(segments, len(layout), "SegmentedAdam.sink"):
+        for g in GROUPS:
+            if g in groups:
+                ss, b2 = step_scalars(steps[s][g] + 1, lrs[s][g], betas, bc_cache)
+                plan[(s, g)] = (np.float32(ss), np.float32(b2))
+    return plan
+
+
 def plan_step(layout, steps: List[Dict[str, int]], lrs: List[Dict[str, float]], segments: Optional[Sequence[int]],
               grads: Dict[str, int], betas: Tuple[float, float], eps: float, span: int, advance: bool = True,
               bc_cache: Optional[dict] = None, max_records: Optional[int] = None) -> Tuple[np.ndarray, int]:
@@ -100,12 +138,7 @@ def plan_step(layout, steps: List[Dict[str, int]], lrs: List[Dict[str, float]], 
     only chunks with count > 0 get a record.  A step of more than ``max_records`` records (sgr_adam_max_records()) is
     refused with an SgrError before any step count advances."""
     nseg = len(layout)
-    if segments is None:
-        segs = range(nseg)
-    else:
-        segs = sorted({int(s) for s in segments})
-        if segs and (segs[0] < 0 or segs[-1] >= nseg):
-            raise IndexError(f"SegmentedAdam.step: segment index out of range [0, {nseg})")
+    segs = _segment_set(segments, nseg, "SegmentedAdam.step")
     if max_records is not None:
         n = sum(1 for s in segs for g in GROUPS if g in grads and layout[s][g][1])
         if n > max_records:
@@ -124,14 +157,10 @@ def plan_step(layout, steps: List[Dict[str, int]], lrs: List[Dict[str, float]], 
             off, cnt, _ = lay[g]
             if not cnt:
                 continue
-            bc = bc_cache.get(st[g])
-            if bc is None:
-                bc = bc_cache[st[g]] = bias_corrections(st[g], *betas)
             rec["g"][n] = grads[g] + 4 * off
             rec["chunk"][n] = s * len(GROUPS) + gi
             rec["span_start"][n] = span_start
-            rec["step_size"][n] = -(lr[g] / bc[0])
-            rec["bc2_sqrt"][n] = bc[1]
+            rec["step_size"][n], rec["bc2_sqrt"][n] = step_scalars(st[g], lr[g], betas, bc_cache)
             rec["eps"][n] = eps
             n += 1
             span_start += _spans(cnt, span)
@@ -197,6 +226,35 @@ def load_adam_state_dict(views, steps: Dict[str, int], lrs: Dict[str, float], sd
         steps[g] = step
 
 
+class AdamSink:
+    """One frame's Adam step, planned by ``SegmentedAdam.sink`` and applied by the backward of
+    ``FlatScene.compose(grad_sink=...)`` (include/sgr_scene_step.h).  ``segments``: the sorted persistent indices of the
+    frame; ``plan``: {(segment, group): (step_size, bc2_sqrt)} as float32, for step count + 1; ``eps``: float32.
+    ``consumed`` turns True when the backward has applied the plan (on ``stream``, the stream it ran on); the step
+    counts advance when ``SegmentedAdam.step`` commits it."""
+
+    def __init__(self, opt: "SegmentedAdam", segments: List[int], plan: dict):
+        self.opt = opt
+        self.segments = list(segments)
+        self.plan = plan
+        self.eps = np.float32(opt.eps)
+        self.consumed = False
+        self.stream = None
+
+    @property
+    def armed(self) -> bool:
+        return self.opt._sink is self
+
+    def discard(self) -> None:
+        """Drops an armed plan whose backward has not run: nothing was stepped, no count advances.  A consumed sink
+        cannot be discarded -- the parameters have moved -- and raises RuntimeError: commit it with ``step``."""
+        if self.consumed:
+            raise RuntimeError("AdamSink.discard: the backward has already applied this step; commit it with "
+                               "SegmentedAdam.step(segments)")
+        if self.armed:
+            self.opt._sink = None
+
+
 class SegmentedAdam:
     """One Adam per segment of ``flat`` (seven named groups each), stepped in one launch.
 
@@ -226,6 +284,7 @@ class SegmentedAdam:
         self.flat = flat
         self.exp_avg = {a: torch.zeros_like(t, memory_format=torch.contiguous_format) for a, t in flat.tensors.items()}
         self.exp_avg_sq = {a: torch.zeros_like(t, memory_format=torch.contiguous_format) for a, t in flat.tensors.items()}
+        self._sink = None
         self._relayout()
 
     # ---- checks ------------------------------------------------------------------------------------------------
@@ -268,6 +327,61 @@ class SegmentedAdam:
             self._chunks_key = key
         return self._chunks_dev
 
+    # ---- the step inside the compose backward ------------------------------------------------------------------------
+    def sink(self, segments: Optional[Sequence[int]] = None) -> AdamSink:
+        """Plans this frame's step for ``FlatScene.compose(..., grad_sink=)`` (host only, nothing is launched and no count
+        advances): per (segment, group) of ``segments`` (None = all) the scalars ``step`` would use now -- step count
+        + 1 and the CURRENT ``lrs``, so call it after the iteration's learning-rate update (the reference updates them
+        at the top of the iteration, train.py:67).  A group whose flat leaf has ``requires_grad == False`` is left out.
+
+        The contract of the armed sink:
+          * the backward of that ``compose`` applies the step: the seven flat leaves and the moments CHANGE during
+            ``loss.backward()``, and the leaves get no ``.grad``;
+          * ``compose`` must be the only autograd consumer of the seven leaves in that graph: a regulariser computed
+            directly on a leaf would read it in an undefined order relative to the step and lose its gradient;
+          * one backward per sink (a second one raises RuntimeError); ``step(segments)`` with the same segments then
+            commits it: it launches nothing and advances exactly the planned step counts;
+          * not for use with the ``multiview`` reducers, which need the gradients;
+          * moments, ``state_views``, ``model_state_dict`` and ``densify_scene(moments=...)`` work unchanged.
+
+        Raises RuntimeError while another sink is armed, and when the library's lazy forward is on (``sgr_set_lazy``): a
+        lazy frame that is found invalid one call late must be discarded, and a step already applied cannot be."""
+        if self._sink is not None:
+            raise RuntimeError("SegmentedAdam.sink: another sink is still armed (commit it with step(segments) or drop it "
+                               "with its discard())")
+        if int(_native.lib().sgr_set_lazy(-1)) == 1:
+            raise RuntimeError("SegmentedAdam.sink: the lazy forward is on (sgr_set_lazy): a lazy frame found invalid one "
+                               "call late must be discarded, and a step applied inside the backward cannot be")
+        groups = [g for g in GROUPS if self.flat.tensors[ATTR[g]].requires_grad]
+        segs = _segment_set(segments, len(self.layout), "SegmentedAdam.sink")
+        plan = plan_sink(self.layout, self.steps, self.lrs, segs, groups, self.betas, bc_cache=self._bc)
+        self._sink = AdamSink(self, segs, plan)
+        return self._sink
+
+    def _refuse_armed(self, who: str) -> None:
+        if self._sink is not None:
+            raise RuntimeError(f"SegmentedAdam.{who}: a sink is armed (commit it with step(segments) or drop it with its "
+                               "discard())")
+
+    def _commit_sink(self, segments) -> bool:
+        """True when an armed, consumed sink was committed (the step has been applied by the backward already)."""
+        sink = self._sink
+        if sink is None:
+            return False
+        if not sink.consumed:  # no output had an upstream gradient: the backward never ran, nothing was stepped
+            self._sink = None
+            return False
+        if _segment_set(segments, len(self.layout), "SegmentedAdam.step") != sink.segments:
+            raise ValueError(f"SegmentedAdam.step: segments {segments} do not match the consumed sink's {sink.segments}")
+        stray = [ATTR[g] for g in GROUPS if self.flat.tensors[ATTR[g]].grad is not None]
+        if stray:
+            raise ValueError(f"SegmentedAdam.step: the sink has stepped this frame, but {stray} carry a .grad: a mixed "
+                             "step (another autograd consumer of the leaves?); nothing changes")
+        for s, g in sink.plan:
+            self.steps[s][g] += 1
+        self._sink = None
+        return True
+
     # ---- the step ------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, segments: Optional[Sequence[int]] = None) -> None:
@@ -276,7 +390,14 @@ class SegmentedAdam:
         every segment; a skipped (segment, group) keeps its bytes and its step count.  Set the leaves' ``.grad`` to
         None afterwards, as the reference's ``zero_grad(set_to_none=True)`` does.  One step takes at most
         sgr_adam_max_records() (4096) non-empty (segment, group) blocks, 585 models with all seven: more is refused with
-        an SgrError before anything changes, and the caller steps the segments in several calls."""
+        an SgrError before anything changes, and the caller steps the segments in several calls.
+
+        After a backward into this optimiser's ``sink()``, the step has been applied already: this call launches
+        nothing, checks that ``segments`` is the sink's set and that no leaf carries a ``.grad`` (ValueError, nothing
+        changes), advances the planned step counts and disarms.  An armed sink whose backward never ran is dropped
+        and the call behaves as without one."""
+        if self._commit_sink(segments):
+            return
         grads = {}
         for g in GROUPS:
             leaf = self.flat.tensors[ATTR[g]]
@@ -320,6 +441,7 @@ class SegmentedAdam:
     def load_model_state_dict(self, seg: int, sd: dict) -> None:
         """Restores segment ``seg`` from a ``torch.optim.Adam.state_dict()`` over the reference's seven groups: learning
         rates, step counts and moments (a group without state gets step 0 and zero moments)."""
+        self._refuse_armed("load_model_state_dict")
         load_adam_state_dict(self.state_views(seg), self.steps[seg], self.lrs[seg], sd, self.betas, self.eps)
 
     def rebuild(self, new_flat, states: Sequence[Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]]) -> None:
@@ -327,6 +449,7 @@ class SegmentedAdam:
         results of ``densify_and_prune``).  ``states[i]`` is segment i's new ``{group: (exp_avg, exp_avg_sq)}`` (the
         ``new_states`` of its densify call), or None to keep its current moments (its counts must be unchanged).
         Learning rates and step counts carry over per segment, as cat_optimizer / prune_optimizer keep them."""
+        self._refuse_armed("rebuild")
         if len(new_flat.meta) != len(self.layout):
             raise ValueError(f"rebuild: {len(self.layout)} segments before, {len(new_flat.meta)} after")
         if len(states) != len(self.layout):
@@ -354,6 +477,7 @@ class SegmentedAdam:
         """Adopts ``densify.densify_scene``'s results without a copy: ``new_moments`` = ``(exp_avg, exp_avg_sq)``, dicts
         keyed by flat attribute and shaped like ``new_flat``'s leaves, become this optimiser's moments.  Learning rates and
         step counts carry over per segment, as ``rebuild`` keeps them."""
+        self._refuse_armed("rebuild_flat")
         if len(new_flat.meta) != len(self.layout):
             raise ValueError(f"rebuild_flat: {len(self.layout)} segments before, {len(new_flat.meta)} after")
         self._check_flat(new_flat)

@@ -72,6 +72,14 @@ def _correction(t):
     return _f32c(t.reshape(7), "correction")
 
 
+class _CStepGroup(C.Structure):
+    _fields_ = [("m", C.c_void_p), ("v", C.c_void_p), ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
+
+
+class _CStep(C.Structure):  # sgr_scene_step: the seven groups in optim.GROUPS order
+    _fields_ = [("group", _CStepGroup * 7)]
+
+
 class _CStatSeg(C.Structure):
     _fields_ = [("count", C.c_int32), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p),
                 ("max_radii2D", C.c_void_p)]
@@ -311,7 +319,7 @@ class FlatScene:
 
     def compose(self, max_sh_coeffs: int, num_classes: int, flip_masks: Optional[Sequence] = None,
                 poses: Optional[torch.Tensor] = None, idfts: Optional[Sequence] = None,
-                segments: Optional[Sequence[int]] = None, correction: Optional[torch.Tensor] = None):
+                segments: Optional[Sequence[int]] = None, correction: Optional[torch.Tensor] = None, grad_sink=None):
         """Same result as ``scene.compose(segments, M, S)``; gradients arrive in the 7 flat leaves and in the poses.
 
         ``segments``: the indices (into the persistent models) this frame renders, in rasterization order, each at most
@@ -327,7 +335,17 @@ class FlatScene:
         [fourier_dim] per rendered segment (None for the background): it depends on the frame's timestamp
         (gaussian_model_actor.py:71-80); default: the rows the segments carried at construction.  ``flip_masks`` = one
         bool [n] mask per rendered segment or None (training-time symmetry flips, :270-283).  ``correction``: the [7]
-        camera pose correction of the image, applied to the background (see ``scene.compose``)."""
+        camera pose correction of the image, applied to the background (see ``scene.compose``).
+
+        ``grad_sink``: the ``sink()`` of a ``SegmentedAdam`` over this very FlatScene, planned for the same set of
+        ``segments`` (else ValueError).  The forward is unchanged; the backward applies the Adam step to every element
+        it would have written a gradient for (include/sgr_scene_step.h) instead of returning gradients for the seven
+        flat leaves, so the PARAMETERS CHANGE DURING ``loss.backward()`` and the leaves get no ``.grad``; the ``poses``
+        and ``correction`` gradients are returned as without a sink, bit for bit.  ``compose`` must then be the only
+        autograd consumer of the seven leaves in the graph (a regulariser computed directly on a leaf would read it in
+        an undefined order relative to the step, and lose its gradient), one backward per sink (a second backward, or
+        a second ``compose`` given the same sink, raises RuntimeError in backward), and not with the ``multiview``
+        reducers, which need the gradients.  ``SegmentedAdam.step(segments)`` afterwards commits the step counts."""
         K = len(self.meta)
         if segments is None:
             seg = list(range(K))
@@ -363,8 +381,14 @@ class FlatScene:
         ids = None
         if idfts is not None:
             ids = [None if t is None else torch.as_tensor(t, dtype=torch.float32, device=self.xyz.device).contiguous() for t in idfts]
+        if grad_sink is not None:
+            if getattr(grad_sink, "opt", None) is None or grad_sink.opt.flat is not self:
+                raise ValueError("FlatScene.compose: grad_sink must be the sink() of a SegmentedAdam over this FlatScene")
+            if sorted(seg) != list(grad_sink.segments):
+                raise ValueError(f"FlatScene.compose: the frame renders the models {sorted(seg)}, the sink was planned "
+                                 f"for {list(grad_sink.segments)}")
         args = [self.tensors[k] for k in _FLAT] + [P, correction]
-        return _ComposeFlat.apply(self, (fm, ids, seg, rows), int(max_sh_coeffs), int(num_classes), *args)
+        return _ComposeFlat.apply(self, (fm, ids, seg, rows), int(max_sh_coeffs), int(num_classes), grad_sink, *args)
 
 
 def _blocks(fs: FlatScene, rest_w: int):
@@ -455,9 +479,38 @@ def _pack_flat(fs: FlatScene, tensors, frame, grads=None):
     return arr, garr, keep
 
 
+# flat attribute (the order of _FLAT) -> its group's place in optim.GROUPS / sgr_scene_step.group
+_STEP_GROUP = {"xyz": (0, "xyz"), "features_dc": (1, "f_dc"), "features_rest": (2, "f_rest"), "opacity": (3, "opacity"),
+               "scaling": (4, "scaling"), "rotation": (5, "rotation"), "semantic": (6, "semantic")}
+
+
+def _pack_steps(fs: FlatScene, tensors, frame, sink):
+    """sgr_scene_step array parallel to ``_pack_flat``'s segments: the moments' blocks of the sink's optimiser and the
+    plan's scalars; a group outside the plan, or with an empty block, keeps m == NULL (neither stepped nor written)."""
+    _, _, seg, _ = frame
+    opt = sink.opt
+    arr = (_CStep * len(seg))()
+    rest_w = tensors[5].shape[1] if tensors[5] is not None and tensors[5].dim() == 2 else 0
+    blocks = _blocks(fs, rest_w)
+    for j, i in enumerate(seg):
+        for k, t in zip(_FLAT, tensors):
+            gi, gname = _STEP_GROUP[k]
+            sc = sink.plan.get((i, gname))
+            off, cnt = blocks[i][k]
+            if sc is None or not cnt:
+                continue
+            m, v = opt.exp_avg[k], opt.exp_avg_sq[k]
+            if t.data_ptr() != fs.tensors[k].data_ptr() or m.shape != t.shape or v.shape != t.shape:
+                raise RuntimeError(f"compose(grad_sink=): flat.{k} or its moments changed between compose and backward")
+            g = arr[j].group[gi]
+            g.m, g.v = m.data_ptr() + 4 * off, v.data_ptr() + 4 * off
+            g.step_size, g.bc2_sqrt = float(sc[0]), float(sc[1])
+    return arr
+
+
 class _ComposeFlat(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fs, frame, M, S, *tensors):
+    def forward(ctx, fs, frame, M, S, sink, *tensors):
         dev = tensors[0].device
         *tensors, correction = tensors
         for t in tensors:
@@ -478,6 +531,7 @@ class _ComposeFlat(torch.autograd.Function):
         ctx.present = [t is not None for t in tensors]
         ctx.keep = keep
         ctx.corr = (correction, corr)
+        ctx.sink = sink
         return tuple(outs)
 
     @staticmethod
@@ -486,7 +540,13 @@ class _ComposeFlat(torch.autograd.Function):
         tensors = [next(saved) if p else None for p in ctx.present]
         fs, M, S = ctx.fs, ctx.M, ctx.S
         dev = tensors[0].device
-        need = ctx.needs_input_grad[4:]
+        need = ctx.needs_input_grad[5:]
+        sink = ctx.sink
+        if sink is not None:
+            if sink.consumed or not sink.armed:
+                raise RuntimeError("compose(grad_sink=): this sink has already been consumed by a backward (one backward "
+                                   "per sink)" if sink.consumed else "compose(grad_sink=): the sink is no longer armed")
+            need = [False] * 7 + list(need[7:])  # the seven Gaussian leaves are stepped, not given gradients
         grads = [torch.empty_like(t) if (t is not None and need[i]) else None for i, t in enumerate(tensors)]
         arr, garr, keep = _pack_flat(fs, tensors, ctx.frame, grads)
         spans = _zero_spans(fs, ctx.frame, grads)
@@ -496,12 +556,19 @@ class _ComposeFlat(torch.autograd.Function):
         dz = lambda t: None if t is None else _f32c(t, "grad")
         ins = [dz(d_means), dz(d_rot), dz(d_scale), dz(d_opac), dz(d_shs), dz(d_sem) if S else None]
         grow = Grow(dev)
-        call("sgr_scene_compose_backward_ex", dev, len(arr), arr, garr, M, S,
-             *[t if t is not None and t.numel() else None for t in ins], cframe, grow.cb, None)
+        ins = [t if t is not None and t.numel() else None for t in ins]
+        if sink is None:
+            call("sgr_scene_compose_backward_ex", dev, len(arr), arr, garr, M, S, *ins, cframe, grow.cb, None)
+        else:
+            steps = _pack_steps(fs, tensors, ctx.frame, sink)
+            beta1, beta2 = sink.opt.betas
+            call("sgr_scene_compose_backward_step", dev, len(arr), arr, steps, garr, M, S, *ins, cframe, beta1, beta2,
+                 float(sink.eps), grow.cb, None)
+            sink.consumed, sink.stream = True, torch.cuda.current_stream(dev)
         del keep
         if dcorr is not None:
             dcorr = dcorr.view(correction.shape).to(correction.dtype)
-        return (None, None, None, None) + tuple(grads) + (dcorr,)
+        return (None, None, None, None, None) + tuple(grads) + (dcorr,)
 
 
 def densification_stats(models: Sequence[dict], dL_dmeans2D: torch.Tensor, radii: torch.Tensor) -> None:
