@@ -23,7 +23,7 @@ SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_
 # `python tools/build_variant.py <name> -DSGR_WITH_VARIANTS=1` builds a library that contains them (sgr_has_variants() = 1),
 # and the tests of those paths run only against such a build.
 VARIANT_SOURCES = [os.path.join("variants", "sgr_blend_bwd_sw.hip")]
-HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_math.h", "sgr_tile_walk.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", os.path.join("..", "..", "include", "sgr.h"),
+HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_math.h", "sgr_launch.h", "sgr_tile_walk.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", os.path.join("..", "..", "include", "sgr.h"),
            os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h"),
@@ -45,6 +45,9 @@ PER_FILE_FLAGS = {"sgr_scan_sort.hip": ["-mllvm", "-amdgpu-sched-strategy=max-il
                   "sgr_actor_pose.hip": ["-ffp-contract=off"]}
 # sources that #include another source (a second instantiation under other names / other FP settings)
 INCLUDES = {"sgr_gauss_bwd_strict.hip": ["sgr_gauss_bwd.hip"]}
+# -z defs: a launcher that is called (declared in csrc/sgr_launch.h) but defined with another signature, or not at all, is an
+# undefined symbol, and an undefined symbol fails the link instead of the first call
+LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs"]
 
 
 def flags_for(src: str) -> list:
@@ -101,7 +104,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     with open(stamp, "w") as f:
         f.write(want)
     if force or any(c for _, c in results) or not os.path.exists(LIB):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+        cmd = [hipcc] + LINK_FLAGS + ["-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stderr}")

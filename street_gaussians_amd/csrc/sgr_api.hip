@@ -15,70 +15,7 @@
 #include "../../include/sgr.h"
 #include "../../include/sgr_layers.h"
 #include "../../include/sgr_object_alpha.h"
-#include "sgr_math.h"
-
-// launchers implemented in the kernel translation units
-void sgr_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s);
-void sgr_launch_preprocess(int P, int D, int M, const float* means3D, const float* scales, const float* rotations,
-                           const float* opacities, const float* shs, const float* cov3D_precomp,
-                           const float* colors_precomp, const SgrCam* cam, const SgrGeomView& gv, int* radii,
-                           int prefiltered, bool stage_sh, int tight, bool want_jac, hipStream_t s);
-void sgr_launch_filter(int P, const float* means3D, const float* scales, const float* rotations,
-                       const float* cov3D_precomp, const SgrCamArgs& ca, const SgrGeomView& gv, int* radii,
-                       float* means2D, int prefiltered, hipStream_t s);
-void sgr_launch_duplicate(int P, const SgrGeomView& gv, const uint32_t* order, const uint32_t* bsum, const uint32_t* sub, void* keys,
-                          int key16, uint32_t* vals, int gx, uint32_t cap, int marks, hipStream_t s);
-void sgr_launch_tile_ranges(int L, const void* keys, int key16, uint2* ranges, uint8_t* touched, uint32_t T, hipStream_t s);
-void sgr_launch_tile_order(const uint2* ranges, int T, int force, hipStream_t s);
-void sgr_launch_compose_keys(int L, const void* tile_keys, int key16, const uint32_t* point_list, const float4* rec, uint64_t* out,
-                             hipStream_t s);
-void sgr_launch_blend_fwd(bool cull, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                          int S, const float4* rec, const float* semantics, const float* bg, float* out_color,
-                          float* out_depth, float* out_alpha, float* out_semantic, uint32_t* n_contrib, uint8_t* hit4,
-                          uint32_t* hlist, uint32_t* n_contrib_k, hipStream_t s);
-void sgr_launch_blend_layers(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                             const float4* rec, int split, int P, const float* bg, int clamp, float* const color[2],
-                             float* const alpha[2], hipStream_t s);
-void sgr_launch_layers_fill(int W, int H, const float* bg, int clamp, float* const color[2], float* const alpha[2], hipStream_t s);
-void sgr_launch_object_alpha_fwd(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                                 const float4* rec, int split, float* out_alpha, uint32_t* out_last, hipStream_t s);
-void sgr_launch_object_alpha_bwd(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                                 const float4* rec, const uint32_t* u0, const uint64_t* tmask, int split, const float* layer_alpha,
-                                 const uint32_t* layer_last, const float* dL_dlayer_alpha, float* partials, int row_stride,
-                                 uint8_t* touched, uint32_t row_limit, hipStream_t s);
-int sgr_partial_row_stride(int S);
-void sgr_launch_blend_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W,
-                          int H, int S, const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* semantics, const float* alphas,
-                          const uint32_t* n_contrib, const uint8_t* hit4, const float* dL_dpix, const float* dL_ddepth,
-                          const float* dL_dalpha, const float* dL_dsem, float* partials, uint8_t* touched, uint32_t row_limit,
-                          const uint32_t* hlist, const uint32_t* n_contrib_k, const uint32_t* hl_flag, hipStream_t s);
-int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const int* radii, const float* shs,
-                          const float* scales, const float* rotations, const float* cov3D_precomp, const SgrCam* cam,
-                          const SgrGeomView& gv, const float* partials, int row_stride, const uint8_t* touched,
-                          float4* cd, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                          float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dsemantic,
-                          const SgrStatSink& sink, int quad, int exact, int W, int H, hipEvent_t after_rows, int rs_wave,
-                          uint32_t row_limit, float* masked_color_out, int skip_sh, int skip_cov, hipStream_t s);
-void sgr_launch_blend_bwd_sw(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                             const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* alphas,
-                             const uint32_t* n_contrib, const uint8_t* hit4, const float* dL_dpix, const float* dL_ddepth,
-                             const float* dL_dalpha, float* partials, int row_stride, uint8_t* touched, hipStream_t s);
-// the same compiled with FP contraction off (sgr_gauss_bwd_strict.hip): parity mode
-int sgr_launch_gauss_bwd_strict(int P, int D, int M, int S, const float* means3D, const int* radii, const float* shs,
-                                 const float* scales, const float* rotations, const float* cov3D_precomp, const SgrCam* cam,
-                                 const SgrGeomView& gv, const float* partials, int row_stride, const uint8_t* touched,
-                                 float4* cd, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                                 float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dsemantic,
-                                 const SgrStatSink& sink, int quad, int exact, int W, int H, hipEvent_t after_rows, int rs_wave,
-                                 uint32_t row_limit, float* masked_color_out, int skip_sh, int skip_cov, hipStream_t s);
-void sgr_launch_masked_color_grad(int P, const uint32_t* clamped, const float* dL_dcolor, float* out, hipStream_t s);
-void sgr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, size_t means_stride,
-                                   const float* campos, size_t campos_stride, const float* drgb, size_t drgb_stride,
-                                   float* dL_dsh, hipStream_t s);
-void sgr_launch_wave_sum_test(const float* in, float* out_dpp, float* out_shfl, int nwaves, hipStream_t s);
-void sgr_launch_lds_atomic_order_test(const uint32_t* pattern, uint32_t* out, int trials, hipStream_t s);
-int sgr_knn_impl(int P, const float* points, float* meanDists, sgr_alloc_fn scratch, void* scratch_user, hipStream_t s,
-                 std::string& err);
+#include "sgr_launch.h"  // every launcher of the kernel translation units
 
 static thread_local std::string g_err;
 
@@ -267,19 +204,26 @@ static bool lazy_on() {
     }
     return v != 0;
 }
-struct LazyPending {
-    bool pending = false;       // a lazy forward's read-back has not been looked at yet
-    uint32_t cap = 0;           // the capacity that forward ran with
-    uint32_t* host_vals = nullptr;
+// What a host thread's forwards remember from one call to the next.
+struct ThreadState {
+    // The front end of the forward runs once -- or twice, the second time with a depth sort on all 32 key bits, when the
+    // preprocess reports a view depth beyond what the 27-bit keys order (>= 13 107: never seen in a street scene); the thread
+    // then keeps the wide sort for its next 64 forwards before it tries the narrow one again, so a scene that really has
+    // such depths pays the repeat on one frame in 64.
+    int wide_left = 0;
+    size_t r_hint = 0;  // instance-list size to expect: high-water mark of its forwards' R + head-room; 0: the next one blocks
+    int epoch = 0;      // the g_lazy_epoch this thread has seen
+    bool pending = false;  // its last lazy forward's read-back has not been looked at yet
+    uint32_t cap = 0;      // the capacity it ran with
+    uint32_t* host_vals = nullptr;  // (where its read-back lands, and the event that says so)
     hipEvent_t landed = nullptr;
-    bool wide = false;          // it sorted the depths on all 32 bits
+    bool wide = false;     // it sorted the depths on all 32 bits
+    // 0 = fine, else a bit set: 1 R > capacity, 2 prefilter violation, 4 far depth with the narrow depth sort
+    int lazy_flags() const {
+        return (host_vals[4] > cap ? 1 : 0) | ((host_vals[0] & 1u) ? 2 : 0) | (((host_vals[2] & 1u) && !wide) ? 4 : 0);
+    }
 };
-static thread_local LazyPending t_lazy;
-// 0 = fine, else a bit set: 1 R > capacity, 2 prefilter violation, 4 far depth with the narrow depth sort
-static int lazy_flags(const LazyPending& lp) {
-    const uint32_t* hv = lp.host_vals;
-    return (hv[4] > lp.cap ? 1 : 0) | ((hv[0] & 1u) ? 2 : 0) | (((hv[2] & 1u) && !lp.wide) ? 4 : 0);
-}
+static thread_local ThreadState t_state;
 
 // ---- the switches as one call sees them --------------------------------------------------------------------------------
 // Decoded from ONE load of the mask (and the lazy mode) at the entry of sgr_forward, sgr_backward_ex and sgr_export_internal
@@ -355,6 +299,70 @@ static uint32_t binning_ladder(size_t r) {
     return (uint32_t)std::min<size_t>((r + step - 1) / step * step, 0x7fffffffu);
 }
 
+// ---- what a frame is: the tile grid of its image and the views of the three buffers a forward fills --------------------------
+struct TileGrid {
+    int W, H, gx, gy;  // image size, tiles per axis
+    size_t N, T;       // pixels, tiles
+    // beyond what the packed tile rects hold: every entry point that takes an image size refuses it
+    bool too_large() const { return gx > SGR_MAX_GRID_DIM || gy > SGR_MAX_GRID_DIM; }
+};
+static TileGrid tile_grid(int W, int H) {
+    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
+    return {W, H, gx, gy, (size_t)W * H, (size_t)gx * gy};
+}
+
+// The forward builds it once it knows R; the backward, the object-alpha head and the exports build the same value from the buffers
+// the caller hands back -- which is why they must run under the forward's TILE_SORT / KEY32 switch (include/sgr.h).
+struct Frame {
+    TileGrid g;
+    SgrGeomView gv;
+    SgrImgView iv;
+    SgrBinView bv;         // filled only when R > 0 (the forward: always -- it has a buffer for R = 0 too)
+    const int* radii;      // the caller's, or the forward's own (rasterizer_impl.cu:232-235)
+    int key16;             // the tile keys are 16-bit (Switches::key16)
+    int pair;              // which of the two ping-pong pairs holds the sorted tile keys: one flip per 8-bit pass
+    const void* keys;      // the sorted tile keys, bv.keys[pair]
+    const uint32_t* list;  // the final instance list, bv.vals[pair] -- the per-tile sort form (TILE_SORT) writes it to the other one
+    // frame_order: the tiles as the forward's blend walked them -- what every consumer but the scalar-walk variant asks for
+    SgrTileLists tiles(bool frame_order) const { return {g.gx, frame_order ? -g.gy : g.gy, g.W, g.H, iv.ranges, list, gv.rec}; }
+};
+static Frame make_frame(int P, int R, int W, int H, char* geom, char* binning, char* image, const int* radii, const Switches& sw,
+                        bool carve_empty_list = false) {
+    Frame f = {};
+    f.g = tile_grid(W, H);
+    f.gv = sgr_geom_carve(geom, (size_t)P);
+    f.iv = sgr_img_carve(image, f.g.N, f.g.T);
+    f.radii = radii ? radii : f.gv.internal_radii;
+    f.key16 = sw.key16(f.g.T);
+    if (R > 0 || carve_empty_list) {
+        f.bv = sgr_bin_carve(binning, (size_t)R);
+        // (the tile sort only; depth order comes from the emission order.  R = 0: no sort ran)
+        f.pair = R > 0 ? (sgr_sort_pass_count((int)getHigherMsb((uint32_t)f.g.T)) & 1) : 0;  // rasterizer_impl.cu:303
+        f.keys = f.bv.keys[f.pair];
+        f.list = f.bv.vals[f.pair ^ (sw.tile_sort ? 1 : 0)];
+    }
+    return f;
+}
+
+// The backward's scratch: [P float4: conic + depth terms between the two per-Gaussian stages][`rows` partial rows of `stride`
+// floats][`extra_bytes`: whatever else the caller carves behind them].  false: the allocation failed.
+struct BwdScratch { float4* cd; float* partials; char* extra; };
+static bool bwd_scratch(sgr_alloc_fn scratch, void* user, int P, size_t rows, int stride, size_t extra_bytes, BwdScratch& out) {
+    const size_t cd_bytes = sgr_align_up((size_t)P * sizeof(float4), 256);
+    const size_t row_bytes = sgr_align_up(rows * stride * sizeof(float), 256);
+    char* base = scratch(cd_bytes + row_bytes + extra_bytes, user);
+    out = {reinterpret_cast<float4*>(base), reinterpret_cast<float*>(base + cd_bytes), base + cd_bytes + row_bytes};
+    return base != nullptr;
+}
+// One byte per (tile, instance) row: "written by this backward".  It lives in the binning buffer and arrives zeroed by the
+// forward's tile-ranges launch; the rows the composite's backward writes are a function of the forward's hit record alone, so
+// repeated backwards over one forward re-mark the same bytes.  A backward that marks any OTHER set clears them before its
+// walk and after its per-Gaussian stage: whichever backward comes next finds them as the forward left them.
+static int clear_touched(const Frame& f, int R, bool odd_set, hipStream_t stream) {
+    uint8_t* const touched = f.bv.touched;
+    if (R > 0 && odd_set) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
+    return 0;
+}
 // The camera arrives as three device arrays; a small kernel packs it (plus the host-side scalars) into a
 // device-resident SgrCam so no device->host copy is needed.  The same launch clears what the forward needs cleared before
 // its first real kernel -- the 16 header words (flags, num_rendered), the T tile ranges (rasterizer_impl.cu:313) and the
@@ -392,15 +400,22 @@ static_assert(sizeof(SgrCam) <= 48 * 4, "SgrCam must fit the geometry header");
 static_assert(SGR_STAT_SEG_MAX == SGR_MAX_STAT_SEGMENTS, "sgr_common.h and include/sgr.h disagree");
 
 static void pack_camera(const SgrGeomView& gv, const float* view, const float* proj, const float* campos,
-                        float tan_fovx, float tan_fovy, int W, int H, float scale_modifier, uint2* ranges, int T,
-                        const Switches& sw, bool jac, hipStream_t s) {
+                        float tan_fovx, float tan_fovy, int W, int H, float scale_modifier, uint2* ranges,
+                        const TileGrid& g, const Switches& sw, bool jac, hipStream_t s) {
     const float focal_y = H / (2.0f * tan_fovy);  // rasterizer_impl.cu:225-226
     const float focal_x = W / (2.0f * tan_fovx);
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const int nb = std::max(1, std::min(64, (T + 255) / 256));
+    const int T = (int)g.T, nb = std::max(1, std::min(64, (T + 255) / 256));
     sgr_pack_camera_kernel<<<nb, 256, 0, s>>>(cam_slot(gv), view, proj, campos, tan_fovx, tan_fovy, focal_x, focal_y, W, H,
-                                             gx, gy, scale_modifier, gv.header, ranges, T,
+                                             g.gx, g.gy, scale_modifier, gv.header, ranges, T,
                                              (uint32_t)sw.rect_mode | (sw.hit_list ? 0x100u : 0u) | (jac ? 0x200u : 0u));
+}
+
+// The per-Gaussian stage of a backward: parity mode takes the instantiation with FP contraction off (sgr_gauss_bwd_strict.hip).
+static int gauss_bwd(const Switches& sw, SgrGaussBwdArgs& a, const Frame& f, hipStream_t stream) {
+    a.cam = cam_slot(f.gv);
+    a.gv = f.gv; a.radii = f.radii; a.W = f.g.W; a.H = f.g.H;
+    a.exact = sw.exact ? 1 : 0; a.rs_wave = sw.rs_wave ? 1 : 0;
+    return (sw.exact ? sgr_launch_gauss_bwd_strict : sgr_launch_gauss_bwd)(a, stream);
 }
 
 // One 256-byte device block per DEVICE for the whole process (allocated on first use, kept): the flag word of
@@ -431,8 +446,8 @@ size_t sgr_binning_bytes(int R) {
     return sgr_required([&](char* b, char** e) { sgr_bin_carve(b, (size_t)R, e); });
 }
 size_t sgr_image_bytes(int width, int height) {
-    const size_t T = (size_t)((width + SGR_BLOCK_X - 1) / SGR_BLOCK_X) * ((height + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y);
-    return sgr_required([&](char* b, char** e) { sgr_img_carve(b, (size_t)width * height, T, e); });
+    const TileGrid g = tile_grid(width, height);
+    return sgr_required([&](char* b, char** e) { sgr_img_carve(b, g.N, g.T, e); });
 }
 int sgr_partial_row_floats(int S) { return sgr_partial_row_stride(S); }
 size_t sgr_geometry_jac_offset(int P) {
@@ -440,8 +455,25 @@ size_t sgr_geometry_jac_offset(int P) {
     return (size_t)((char*)sgr_geom_carve(base, (size_t)P).jac - base);
 }
 
+// K5 first: num_rendered (header[4], summed by the preprocess kernel), the prefilter flag (header[0]) and "a depth beyond the
+// 27-bit sort keys" (header[2]) go to pinned host memory in ONE 24-byte copy.  The blocking forward only waits for THAT copy
+// (an event), after the depth sort and the scan have been queued behind it: while it wakes up, allocates the binning buffer
+// and queues the dozen short binning kernels, the GPU is busy with the ~0.15 ms of sort + scan instead of idling (rocprofv3
+// kernel trace: ~0.2 ms of gaps per forward with the wait placed after the scan, as rasterizer_impl.cu:281 has it).
+// watched: the words are armed with a value the device never writes, so that the host can see them arrive
+// (wait_for_readback), and the landing is marked by an event -- not for a lazy forward inside a stream capture.
+static int queue_readback(int slot, const SgrGeomView& gv, bool watched, hipStream_t stream, uint32_t*& host_vals, hipEvent_t& landed) {
+    host_vals = pinned_pair(slot);
+    landed = readback_event(slot);
+    if (!host_vals || !landed) return fail(SGR_E_HIP, "pinned readback slot / event creation failed");
+    if (watched) host_vals[0] = host_vals[2] = host_vals[4] = host_vals[5] = SGR_READBACK_PENDING;
+    SGR_HIP(hipMemcpyAsync(host_vals, gv.header, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (watched) SGR_HIP(hipEventRecord(landed, stream));
+    return 0;
+}
+
 // The forward, and -- `layers` given -- the layer kernel behind it (include/sgr_layers.h; its arguments are checked by
-// sgr_forward_layers before this runs).  sgr_forward is this with layers == nullptr.
+// sgr_forward_layers before this runs).  The three C entry points are this with layers and / or extras == nullptr.
 static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
                         sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
                         int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -449,7 +481,7 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
                         const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                         const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                         float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_,
-                        const sgr_layer_images* layers, const sgr_forward_extras* fx = nullptr) {
+                        const sgr_layer_images* layers, const sgr_forward_extras* fx) {
     hipStream_t stream = (hipStream_t)stream_;
     const Switches sw = resolve_switches();
     // the call's own request, resolved with the switches: the preprocess stores the colour Jacobian for the backward
@@ -457,12 +489,11 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
     const bool want_jac = fx && fx->color_jacobian && shs != nullptr && colors_precomp == nullptr;
     const int W = width, H = height;
     if (P < 0 || W <= 0 || H <= 0) return fail(SGR_E_INVALID, "P, width and height must be positive");
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    if (gx > SGR_MAX_GRID_DIM || gy > SGR_MAX_GRID_DIM)
-        return fail(SGR_E_INVALID, "image larger than 16368 px per side is not supported");
+    const TileGrid g = tile_grid(W, H);
+    if (g.too_large()) return fail(SGR_E_INVALID, "image larger than 16368 px per side is not supported");
     if (S < 0 || S > SGR_SEM_MAX) return fail(SGR_E_INVALID, "semantic channels must be in [0, 32]");
     if (D < 0 || D > 3) return fail(SGR_E_INVALID, "SH degree must be in [0, 3]");
-    const size_t N = (size_t)W * H, T = (size_t)gx * gy;
+    const size_t N = g.N, T = g.T;
 
     if (P == 0) {  // rasterize_points.cu:86: nothing runs, outputs stay at their zero fill
         SGR_HIP(hipMemsetAsync(out_color, 0, 3 * N * sizeof(float), stream));
@@ -489,20 +520,16 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
     const SgrGeomView gv = sgr_geom_carve(gbase, (size_t)P);
     char* ibase = image_buffer(sgr_image_bytes(W, H), image_user);
     if (!ibase) return fail(SGR_E_ALLOC, "image buffer allocation failed");
-    const SgrImgView iv = sgr_img_carve(ibase, N, T);
+    uint2* const ranges = sgr_img_carve(ibase, N, T).ranges;
     int* radii_ptr = radii ? radii : gv.internal_radii;  // rasterizer_impl.cu:232-235
 
-    // The front end (camera pack, preprocess, depth sort, scan) runs once -- or twice, the second time with a depth sort on
-    // all 32 key bits, when the preprocess reports a view depth beyond what the 27-bit keys order (>= 13 107: never seen in a
-    // street scene; the host thread then keeps the wide sort for its next 64 forwards before it tries the narrow one again,
-    // so a scene that really has such depths pays the repeat on one frame in 64).
-    static thread_local int wide_left = 0;
-    bool wide_depth = wide_left > 0;
-    if (wide_depth) wide_left--;
+    ThreadState& ts = t_state;  // (the front end below runs once -- or twice, the second time with the wide depth sort)
+    bool wide_depth = ts.wide_left > 0;
+    if (wide_depth) ts.wide_left--;
     uint32_t* host_vals = nullptr;
+    hipEvent_t landed = nullptr;  // (the read-back: queue_readback)
     const uint32_t* order = nullptr;
     char* bbase = nullptr;
-    static thread_local size_t r_hint = 0;
 
     // ---- lazy mode (sgr_set_lazy): what the previous lazy forward of this thread left to check
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
@@ -510,32 +537,29 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
     const bool capturing = cap_status != hipStreamCaptureStatusNone;
     // (also inside a stream capture: the pending copy and its event were queued BEFORE the capture began, waiting for them
     // on the host is legal, and the frame they belong to must not lose its check)
-    if (t_lazy.pending) {
-        t_lazy.pending = false;
-        SGR_HIP(wait_for_readback(t_lazy.host_vals, t_lazy.landed));  // queued a whole step ago: landed long since
-        const int fl = lazy_flags(t_lazy);
-        if (t_lazy.host_vals[2] & 1u) wide_left = 64;
+    if (ts.pending) {
+        ts.pending = false;
+        SGR_HIP(wait_for_readback(ts.host_vals, ts.landed));  // queued a whole step ago: landed long since
+        const int fl = ts.lazy_flags();
+        if (ts.host_vals[2] & 1u) ts.wide_left = 64;
         if (fl) {
-            r_hint = 0;  // the next forward of this thread is a blocking one: it re-seeds the capacity
+            ts.r_hint = 0;  // the next forward of this thread is a blocking one: it re-seeds the capacity
             return fail(SGR_E_LAZY, std::string("the PREVIOUS lazy forward of this thread was invalid (") +
                         ((fl & 1) ? "more tile instances than the list capacity; " : "") +
                         ((fl & 2) ? "a Gaussian failed the frustum test although prefiltered is set; " : "") +
                         ((fl & 4) ? "a view depth beyond the 27-bit depth keys; " : "") + "its outputs must be discarded)");
         }
         // high-water mark with a slow decay, as in the blocking path (lazy: 1/16 of head-room -- the sort runs over it)
-        const size_t Rp = t_lazy.host_vals[4];
-        r_hint = std::max(Rp + Rp / 16 + 1024, r_hint - r_hint / 64);
+        const size_t Rp = ts.host_vals[4];
+        ts.r_hint = std::max(Rp + Rp / 16 + 1024, ts.r_hint - ts.r_hint / 64);
     }
-    {   // a change of the mode forgets the thread's capacity: its next forward blocks and seeds it from THAT frame (a
-        // high-water mark left by much larger frames would make the lazy sort run over mostly padding)
-        static thread_local int t_epoch = 0;
-        const int e = g_lazy_epoch.load(std::memory_order_relaxed);
-        if (t_epoch != e) {
-            t_epoch = e;
-            r_hint = 0;
-        }
+    // a change of the mode forgets the thread's capacity: its next forward blocks and seeds it from THAT frame (a
+    // high-water mark left by much larger frames would make the lazy sort run over mostly padding)
+    if (const int e = g_lazy_epoch.load(std::memory_order_relaxed); ts.epoch != e) {
+        ts.epoch = e;
+        ts.r_hint = 0;
     }
-    const bool lazy = sw.lazy_mode && r_hint > 0;
+    const bool lazy = sw.lazy_mode && ts.r_hint > 0;
     // what the list is made of, in index order: {count, rect} records of 8 bytes, or (marked-list mode) 16-byte records whose
     // first half is the reference's count + rect and whose second half is the live part
     const int aux16 = sw.rect_mode == 3 ? 1 : 0;
@@ -545,7 +569,7 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
     // queues its own way -- the depth sort + scan.
     const auto preprocess = [&]() -> int {
         prof_begin(0, stream);
-        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, iv.ranges, (int)T, sw, want_jac, stream);
+        pack_camera(gv, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, W, H, scale_modifier, ranges, g, sw, want_jac, stream);
         SGR_STAGE("pack_camera");
         sgr_launch_preprocess(P, D, M, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp,
                               cam_slot(gv), gv, radii_ptr, prefiltered, sw.pre_stage(P), sw.rect_mode, want_jac, stream);
@@ -583,42 +607,25 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
     uint32_t cap = 0;  // lazy: slots of the instance list
     if (lazy) {
         if (const int rc = preprocess()) return rc;
-        host_vals = pinned_pair(1);
-        hipEvent_t landed = readback_event(1);
-        if (!host_vals || !landed) return fail(SGR_E_HIP, "pinned readback slot / event creation failed");
-        if (!capturing) host_vals[0] = host_vals[2] = host_vals[4] = host_vals[5] = SGR_READBACK_PENDING;
-        SGR_HIP(hipMemcpyAsync(host_vals, gv.header, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        if (!capturing) SGR_HIP(hipEventRecord(landed, stream));
+        if (const int rc = queue_readback(1, gv, !capturing, stream, host_vals, landed)) return rc;
         // from here on a copy is in flight: the late check is owed whatever happens to the rest of this call (an error
         // return below must not leave a copy nobody waits for -- the next forward would take its late arrival for its own)
-        t_lazy.pending = !capturing;
-        t_lazy.host_vals = host_vals;
-        t_lazy.landed = landed;
-        t_lazy.wide = wide_depth;
-        t_lazy.cap = 0x7fffffffu;  // (set below; until then "no overflow")
+        ts.pending = !capturing;
+        ts.host_vals = host_vals;
+        ts.landed = landed;
+        ts.wide = wide_depth;
+        ts.cap = 0x7fffffffu;  // (set below; until then "no overflow")
         if (const int rc = depth_sort_scan()) return rc;
-        cap = binning_ladder(r_hint);  // (consecutive calls ask for the same block size)
+        cap = binning_ladder(ts.r_hint);  // (consecutive calls ask for the same block size)
         bbase = binning_buffer(sgr_binning_bytes((int)cap), binning_user);
         if (!bbase) return fail(SGR_E_ALLOC, "binning buffer allocation failed");
         R = (int)cap;  // what the caller hands to sgr_backward: it sizes the same carving there
-        t_lazy.cap = cap;
+        ts.cap = cap;
     } else {
         size_t have_bytes = 0;
         for (int attempt = 0; attempt < 2; attempt++) {
             if (const int rc = preprocess()) return rc;
-            // K5 first: num_rendered (header[4], summed by the preprocess kernel) and the prefilter flag (header[0]) go to
-            // pinned host memory in ONE 24-byte copy.  The host only waits for THAT copy (an event), after the depth sort and
-            // the scan have been queued behind it: while it wakes up, allocates the binning buffer and queues the dozen short
-            // binning kernels, the GPU is busy with the ~0.15 ms of sort + scan instead of idling (rocprofv3 kernel trace:
-            // ~0.2 ms of gaps per forward with the wait placed after the scan, as rasterizer_impl.cu:281 has it).
-            host_vals = pinned_pair();
-            hipEvent_t landed = readback_event();
-            if (!host_vals || !landed) return fail(SGR_E_HIP, "pinned readback slot / event creation failed");
-            // the words carry a value the device never writes, so that the host can see them arrive (wait_for_readback);
-            // header[2] = "a depth beyond the 27-bit sort keys" rides along
-            host_vals[0] = host_vals[2] = host_vals[4] = host_vals[5] = SGR_READBACK_PENDING;
-            SGR_HIP(hipMemcpyAsync(host_vals, gv.header, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            SGR_HIP(hipEventRecord(landed, stream));
+            if (const int rc = queue_readback(0, gv, true, stream, host_vals, landed)) return rc;
             // an error return between here and the wait must not leave this copy in flight: the next forward of this thread
             // would take its late arrival for its own read-back
             struct ReadbackDrain {
@@ -634,8 +641,8 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
             // partly unused.
             have_bytes = 0;
             bbase = nullptr;
-            if (r_hint > 0) {
-                have_bytes = sgr_binning_bytes((int)binning_ladder(r_hint));
+            if (ts.r_hint > 0) {
+                have_bytes = sgr_binning_bytes((int)binning_ladder(ts.r_hint));
                 bbase = binning_buffer(have_bytes, binning_user);
                 if (!bbase) return fail(SGR_E_ALLOC, "binning buffer allocation failed");
             }
@@ -644,7 +651,7 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
 
             if (!(host_vals[2] & 1u) || wide_depth || sw.tile_sort) break;  // (the per-tile sort reads the far-depth flag on the device)
             wide_depth = true;
-            wide_left = 64;
+            ts.wide_left = 64;
         }
         if (host_vals[0] & 1u)
             return fail(SGR_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
@@ -658,62 +665,63 @@ static int forward_impl(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_a
             if (!bbase) return fail(SGR_E_ALLOC, "binning buffer allocation failed");
         }
         // high-water mark with a slow decay: the views of one scene differ, and a miss only costs the late allocation
-        r_hint = std::max((size_t)R + (size_t)R / 4 + 1024, r_hint - r_hint / 16);
+        ts.r_hint = std::max((size_t)R + (size_t)R / 4 + 1024, ts.r_hint - ts.r_hint / 16);
     }
-    const SgrBinView bv = sgr_bin_carve(bbase, (size_t)R);
-
-    int cur = 0;
+    const Frame f = make_frame(P, R, W, H, gbase, bbase, ibase, radii, sw, true);
+    const SgrBinView& bv = f.bv;
     // (also with R == 0: the kernel finishes the index-order scan, SgrGeomView::u0, which the exports read)
     prof_begin(2, stream);
     SgrGeomView gv_dup = gv;
     if (sw.tile_sort) gv_dup.aux_sorted = const_cast<uint2*>(aux_emit);  // index-order emission: "depth order" is the identity
-    const int key16 = sw.key16(T);
-    sgr_launch_duplicate(P, gv_dup, order, gv.scan_tmp, gv.sub_sums, bv.keys[0], key16, bv.vals[0], gx, cap, aux16, stream);
+    sgr_launch_duplicate(P, gv_dup, order, gv.scan_tmp, gv.sub_sums, bv.keys[0], f.key16, bv.vals[0], g.gx, cap, aux16, stream);
     SGR_STAGE("duplicate");
     prof_end(stream);
     if (R > 0) {
         prof_begin(3, stream);
         const int bit = (int)getHigherMsb((uint32_t)T);  // rasterizer_impl.cu:303
         // (lazy: over all `cap` slots; the padding's keys are all ones in every sorted bit and stay behind the instances)
-        if (key16) {
+        // (the result lands in pair f.pair: sgr_sort_pass_count, which is all the consumers of the buffers have to go by)
+        if (f.key16) {
             uint16_t* const k16[2] = {reinterpret_cast<uint16_t*>(bv.keys[0]), reinterpret_cast<uint16_t*>(bv.keys[1])};
-            cur = sgr_launch_sort_pairs16(k16, bv.vals, (uint32_t)R, bit, bv.hist, bv.scan_tmp, stream);
+            sgr_launch_sort_pairs16(k16, bv.vals, (uint32_t)R, bit, bv.hist, bv.scan_tmp, stream);
         } else {
-            cur = sgr_launch_sort_pairs32(bv.keys, bv.vals, (uint32_t)R, bit, bv.hist, bv.scan_tmp, stream);
+            sgr_launch_sort_pairs32(bv.keys, bv.vals, (uint32_t)R, bit, bv.hist, bv.scan_tmp, stream);
         }
         SGR_STAGE("sort");
         prof_end(stream);
         prof_begin(4, stream);
-        sgr_launch_tile_ranges(R, bv.keys[cur], key16, iv.ranges, bv.touched, lazy ? (uint32_t)T : 0xffffffffu, stream);
+        sgr_launch_tile_ranges(R, f.keys, f.key16, f.iv.ranges, bv.touched, lazy ? (uint32_t)T : 0xffffffffu, stream);
         SGR_STAGE("tile_ranges");
         if (sw.tile_sort) {
             // every tile's list (ascending id so far) into (depth, id) order: a stable radix sort on the depth keys in LDS
-            sgr_launch_tile_sort((int)T, iv.ranges, bv.vals[cur], bv.vals[cur ^ 1], gv.dkeys[0], gv.header, bv.keys[cur ^ 1], bv.tkeys, stream);
+            sgr_launch_tile_sort((int)T, f.iv.ranges, bv.vals[f.pair], bv.vals[f.pair ^ 1], gv.dkeys[0], gv.header, bv.keys[f.pair ^ 1], bv.tkeys, stream);
             SGR_STAGE("tile_sort");
         }
         prof_end(stream);
     }
-    const int lcur = sw.tile_sort ? (cur ^ 1) : cur;  // which vals[] holds the final list (list_index())
+    const SgrTileLists tl = f.tiles(sw.lpt);  // (without the tile-order launch: the supertile order, no look at the flag word)
     prof_begin(5, stream);
     if (sw.lpt) {
-        sgr_launch_tile_order(iv.ranges, (int)T, sw.lpt_force ? 1 : 0, stream);
+        sgr_launch_tile_order(f.iv.ranges, (int)T, sw.lpt_force ? 1 : 0, stream);
         SGR_STAGE("tile_order");
     }
-    sgr_launch_blend_fwd(sw.cull, sw.exact, gx, sw.lpt ? -gy : gy, iv.ranges, bv.vals[lcur], W, H, S, gv.rec, semantics,
-                         background, out_color, out_depth, out_alpha, out_semantic, iv.n_contrib, bv.hit4,
-                         sw.hit_list ? bv.hlist : nullptr, iv.n_contrib_k, stream);
+    sgr_launch_blend_fwd(sw.cull, sw.exact, tl, S, semantics, background, out_color, out_depth, out_alpha, out_semantic,
+                         f.iv.n_contrib, bv.hit4, sw.hit_list ? bv.hlist : nullptr, f.iv.n_contrib_k, stream);
     SGR_STAGE("blend_fwd");
     prof_end(stream);
     if (layers) {
         // one more walk of the same ranges, the same final list and the same records, in the same tile order: the images of
         // Gaussians [0, split) and [split, P) alone (sgr_blend_layers.hip).  It writes none of the composite's buffers.
-        sgr_launch_blend_layers(sw.exact, gx, sw.lpt ? -gy : gy, iv.ranges, bv.vals[lcur], W, H, gv.rec, layers->split, P,
-                                layers->background, layers->clamp, layers->color, layers->alpha, stream);
+        sgr_launch_blend_layers(sw.exact, tl, layers->split, P, layers->background, layers->clamp, layers->color, layers->alpha, stream);
         SGR_STAGE("blend_layers");
     }
     return R;
 }
 
+#define SGR_FORWARD_ARGS /* what the three entry points share, as their parameters name it */                                \
+    geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S, background, width, height, \
+        means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,        \
+        projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, out_semantic, radii, debug, stream_
 int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
                 sgr_alloc_fn image_buffer, void* image_user, int P, int D, int M, int S, const float* background,
                 int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -721,10 +729,7 @@ int sgr_forward(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn 
                 const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                 const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                 float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_) {
-    return forward_impl(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S,
-                        background, width, height, means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier,
-                        rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                        out_depth, out_alpha, out_semantic, radii, debug, stream_, nullptr);
+    return sgr_forward_ex(SGR_FORWARD_ARGS, nullptr);
 }
 
 int sgr_forward_ex(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
@@ -735,10 +740,7 @@ int sgr_forward_ex(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_
                    const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                    float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug, void* stream_,
                    const sgr_forward_extras* extras) {
-    return forward_impl(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S,
-                        background, width, height, means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier,
-                        rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                        out_depth, out_alpha, out_semantic, radii, debug, stream_, nullptr, extras);
+    return forward_impl(SGR_FORWARD_ARGS, nullptr, extras);
 }
 
 int sgr_forward_layers(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_fn binning_buffer, void* binning_user,
@@ -757,21 +759,9 @@ int sgr_forward_layers(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_al
             if (!layers->alpha[l]) return fail(SGR_E_INVALID, "layers: alpha[" + std::to_string(l) + "] is NULL");
         }
     }
-    return forward_impl(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M, S,
-                        background, width, height, means3D, shs, colors_precomp, semantics, opacities, scales, scale_modifier,
-                        rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                        out_depth, out_alpha, out_semantic, radii, debug, stream_, layers);
+    return forward_impl(SGR_FORWARD_ARGS, layers, nullptr);
 }
-
-// which of the two ping-pong pairs holds the sorted tile keys: one flip per 8-bit pass
-static int sorted_index(int width, int height) {
-    const int gx = (width + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (height + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const int end_bit = (int)getHigherMsb((uint32_t)(gx * gy));  // the tile sort only; depth order comes from the emission order
-    return sgr_sort_pass_count(end_bit) & 1;
-}
-// ... and which vals[] holds the final instance list: the per-tile sort form (TILE_SORT) writes it to the other one.
-// (A forward and the backward / exports over its buffers must run under the same switch, include/sgr.h.)
-static int list_index(int width, int height, const Switches& sw) { return sorted_index(width, height) ^ (sw.tile_sort ? 1 : 0); }
+#undef SGR_FORWARD_ARGS
 
 int sgr_backward(int P, int D, int M, int R, int S, const float* background, int width, int height,
                  const float* means3D, const float* shs, const float* colors_precomp, const float* semantics,
@@ -801,7 +791,8 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
                     const sgr_backward_extras* extras) {
     hipStream_t stream = (hipStream_t)stream_;
     const Switches sw = resolve_switches();
-    SgrStatSink sink;
+    SgrGaussBwdArgs ga;  // the per-Gaussian stage; filled by name as the checks below go
+    SgrStatSink& sink = ga.sink;
     if (extras && (extras->xyz_gradient_accum || extras->denom || extras->max_radii2D)) {
         if (!extras->xyz_gradient_accum || !extras->denom || !extras->max_radii2D)
             return fail(SGR_E_INVALID, "the statistics sink needs xyz_gradient_accum, denom and max_radii2D together");
@@ -854,11 +845,7 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
     if (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || (!dL_dcov3D && !skip_cov) || !dL_dscale || !dL_drot)
         return fail(SGR_E_INVALID, "all gradient outputs except dL_dsh / dL_dsemantic are required");
     if (shs && !dL_dsh && !skip_sh) return fail(SGR_E_INVALID, "shs given but dL_dsh is NULL");
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const size_t N = (size_t)W * H, T = (size_t)gx * gy;
-    const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
-    const SgrImgView iv = sgr_img_carve(image_buffer, N, T);
-    const int* radii_ptr = radii ? radii : gv.internal_radii;
+    const Frame f = make_frame(P, R, W, H, geom_buffer, binning_buffer, image_buffer, radii, sw);
     const int stride = sgr_partial_row_stride(S);
     // Which blend backward runs.  Default: the LDS-staged kernel (sgr_blend_bwd.hip).  USE_SW (SGR_SW=1) selects the
     // scalar walk (sgr_blend_bwd_sw.hip; S = 0 with the hit record, cull, DPP reduction and deterministic combine on): it
@@ -866,57 +853,48 @@ int sgr_backward_ex(int P, int D, int M, int R, int S, const float* background, 
     // measured 11 % slower per step: both kernels sit at the VALU issue bound of the same per-visit
     // arithmetic, and the per-quadrant rows cost the row sum more than the barriers cost the LDS kernel.
     const bool quad = sw.quad && S == 0 && R > 0;
-    // scratch = [P float4: conic + depth terms between the two per-Gaussian stages][R (or 4 R) partial rows]
-    const size_t cd_bytes = sgr_align_up((size_t)P * sizeof(float4), 256);
-    const size_t bytes = sgr_align_up((size_t)R * (quad ? 4u : 1u) * stride * sizeof(float), 256);
-    char* sbase = scratch(cd_bytes + bytes, scratch_user);
-    if (!sbase) return fail(SGR_E_ALLOC, "backward scratch allocation failed");
-    float4* cd = reinterpret_cast<float4*>(sbase);
-    float* partials = reinterpret_cast<float*>(sbase + cd_bytes);
-    // One byte per (tile, instance) row: "written by this backward".  It lives in the binning buffer and arrives zeroed
-    // by the forward's tile-ranges launch; the rows a backward writes are a function of the forward's hit record alone,
-    // so repeated backwards over one forward re-mark the same bytes.  The A/B switches that change the visited set
-    // (no cull / no hit record) clear it explicitly, before and after.
-    // (the scalar walk leaves quadrant MASKS in these bytes and the LDS kernel ones: a scalar-walk backward clears them
-    // before and after itself, so that the two kernels can follow each other over one forward)
+    BwdScratch sc;  // R (or 4 R) partial rows
+    if (!bwd_scratch(scratch, scratch_user, P, (size_t)R * (quad ? 4u : 1u), stride, 0, sc))
+        return fail(SGR_E_ALLOC, "backward scratch allocation failed");
+    // clear_touched: the A/B switches that change the visited set (no cull / no hit record), and the scalar walk -- it leaves
+    // quadrant MASKS in these bytes and the LDS kernel ones, so that the two kernels can follow each other over one forward
     const bool odd_set = !sw.cull || !sw.use_hits || quad;
-    uint8_t* touched = nullptr;
     if (R > 0) {
-        const SgrBinView bv = sgr_bin_carve(binning_buffer, (size_t)R);
-        touched = bv.touched;
-        const int cur = list_index(W, H, sw);
         prof_begin(6, stream);
-        if (odd_set) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
+        if (const int rc = clear_touched(f, R, odd_set, stream)) return rc;
         prof_end(stream);
         prof_begin(7, stream);
+        SgrBlendBwdArgs ba;
+        ba.cull = sw.cull; ba.dpp = sw.dpp; ba.det = sw.det; ba.v2 = sw.v2; ba.exact = sw.exact;
+        ba.S = S; ba.bg = background; ba.u0 = f.gv.u0; ba.tmask = f.gv.tmask; ba.semantics = semantics; ba.alphas = alphas;
+        ba.n_contrib = f.iv.n_contrib;
         // the forward's record of which (quadrant, instance) pairs blended at all; NO_HITS: the kernel redoes the
         // geometric cull instead (A/B and tests: the two walks must give bit-identical gradients)
-        const uint8_t* hits = sw.use_hits ? bv.hit4 : nullptr;
+        ba.hit4 = sw.use_hits ? f.bv.hit4 : nullptr;
+        ba.dL_dpix = dL_dpix; ba.dL_ddepth = dL_dpix_depth; ba.dL_dalpha = dL_dalphas; ba.dL_dsem = dL_dpix_semantic;
+        ba.partials = sc.partials; ba.touched = f.bv.touched; ba.row_limit = (uint32_t)R;
+        ba.hlist = sw.hlist_walk ? f.bv.hlist : nullptr; ba.n_contrib_k = f.iv.n_contrib_k; ba.hl_flag = f.gv.header + 7;
 #if SGR_WITH_VARIANTS
-        if (quad)
-            sgr_launch_blend_bwd_sw(sw.exact, gx, gy, iv.ranges, bv.vals[cur], W, H, background, gv.rec, gv.u0, gv.tmask, alphas,
-                                    iv.n_contrib, bv.hit4, dL_dpix, dL_dpix_depth, dL_dalphas, partials, stride, touched, stream);
+        if (quad) sgr_launch_blend_bwd_sw(f.tiles(false), ba, stride, stream);
         else
 #endif
-            // (-gy: the tiles in the frame's order, the flag word behind the ranges -- the order the forward's blend walked)
-            sgr_launch_blend_bwd(sw.cull, sw.dpp, sw.det, sw.v2, sw.exact, gx, -gy, iv.ranges, bv.vals[cur], W, H, S, background, gv.rec, gv.u0, gv.tmask, semantics,
-                                 alphas, iv.n_contrib, hits, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_semantic, partials,
-                                 touched, (uint32_t)R, sw.hlist_walk ? bv.hlist : nullptr, iv.n_contrib_k,
-                                 gv.header + 7, stream);
+            sgr_launch_blend_bwd(f.tiles(true), ba, stream);
         SGR_STAGE("blend_bwd");
         prof_end(stream);
     }
     prof_begin(8, stream);
-    const int ev_failed = (sw.exact ? sgr_launch_gauss_bwd_strict : sgr_launch_gauss_bwd)(
-        P, D, M, S, means3D, radii_ptr, shs, scales, rotations, cov3D_precomp, cam_slot(gv), gv, partials, stride, touched, cd,
-        dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dsemantic, sink, quad ? 1 : 0,
-        sw.exact ? 1 : 0, W, H, extras ? (hipEvent_t)extras->color_ready_event : nullptr, sw.rs_wave ? 1 : 0,
-        (uint32_t)R, extras ? extras->masked_color_out : nullptr, skip_sh, skip_cov, stream);
+    ga.P = P; ga.D = D; ga.M = M; ga.S = S;
+    ga.means3D = means3D; ga.shs = shs; ga.scales = scales; ga.rotations = rotations; ga.cov3D_precomp = cov3D_precomp;
+    ga.partials = sc.partials; ga.row_stride = stride; ga.touched = f.bv.touched; ga.cd = sc.cd;
+    ga.dL_dmean2D = dL_dmean2D; ga.dL_dopacity = dL_dopacity; ga.dL_dcolor = dL_dcolor; ga.dL_dmean3D = dL_dmean3D;
+    ga.dL_dcov3D = dL_dcov3D; ga.dL_dsh = dL_dsh; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot; ga.dL_dsemantic = dL_dsemantic;
+    ga.quad = quad ? 1 : 0; ga.row_limit = (uint32_t)R; ga.skip_sh = skip_sh; ga.skip_cov = skip_cov;
+    if (extras) { ga.after_rows = (hipEvent_t)extras->color_ready_event; ga.masked_color_out = extras->masked_color_out; }
+    const int ev_failed = gauss_bwd(sw, ga, f, stream);
     SGR_STAGE("gauss_bwd");
     prof_end(stream);
     if (ev_failed) return fail(SGR_E_HIP, "hipEventRecord(color_ready_event) failed: is it a valid event of this device?");
-    if (touched && odd_set) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
-    return 0;
+    return clear_touched(f, R, odd_set, stream);
 }
 
 // ---- the object-alpha head (include/sgr_object_alpha.h, sgr_object_alpha.hip) -------------------------------------------
@@ -925,8 +903,7 @@ static int layer_alpha_check(int P, int R, int width, int height, int split, con
                              const void* image) {
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(SGR_E_INVALID, "layer alpha: P, R must not be negative, width and height positive");
     if (split < 0 || split > P) return fail(SGR_E_INVALID, "layer alpha: split must lie in [0, P]");
-    const int gx = (width + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (height + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    if (gx > SGR_MAX_GRID_DIM || gy > SGR_MAX_GRID_DIM) return fail(SGR_E_INVALID, "layer alpha: image larger than 16368 px per side is not supported");
+    if (tile_grid(width, height).too_large()) return fail(SGR_E_INVALID, "layer alpha: image larger than 16368 px per side is not supported");
     if (P > 0 && (!geom || !image || (R > 0 && !binning)))
         return fail(SGR_E_INVALID, "layer alpha: the buffers produced by sgr_forward are required");
     return 0;
@@ -940,20 +917,15 @@ int sgr_layer_alpha_forward(int P, int R, int width, int height, int split, cons
     if (const int rc = layer_alpha_check(P, R, width, height, split, geom_buffer, binning_buffer, image_buffer)) return rc;
     if (!out_alpha || !out_last) return fail(SGR_E_INVALID, "layer alpha: out_alpha and out_last are required");
     const Switches sw = resolve_switches();
-    const int W = width, H = height;
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const size_t N = (size_t)W * H, T = (size_t)gx * gy;
+    const size_t N = tile_grid(width, height).N;
     if (P == 0 || split == P || R == 0) {  // an empty layer (or an empty frame): zeros without a walk
         SGR_HIP(hipMemsetAsync(out_alpha, 0, N * sizeof(float), stream));
         SGR_HIP(hipMemsetAsync(out_last, 0, N * sizeof(uint32_t), stream));
         return 0;
     }
-    const SgrGeomView gv = sgr_geom_carve(const_cast<char*>(geom_buffer), (size_t)P);
-    const SgrImgView iv = sgr_img_carve(const_cast<char*>(image_buffer), N, T);
-    const SgrBinView bv = sgr_bin_carve(const_cast<char*>(binning_buffer), (size_t)R);
-    // (-gy: the tiles in the frame's order, the flag word behind the ranges -- as the backwards walk them)
-    sgr_launch_object_alpha_fwd(sw.exact, gx, -gy, iv.ranges, bv.vals[list_index(W, H, sw)], W, H, gv.rec, split, out_alpha,
-                                out_last, stream);
+    const Frame f = make_frame(P, R, width, height, const_cast<char*>(geom_buffer), const_cast<char*>(binning_buffer),
+                               const_cast<char*>(image_buffer), nullptr, sw);
+    sgr_launch_object_alpha_fwd(sw.exact, f.tiles(true), split, out_alpha, out_last, stream);
     SGR_STAGE("object_alpha_fwd");
     return 0;
 }
@@ -976,48 +948,32 @@ int sgr_layer_alpha_backward(int P, int R, int width, int height, int split, con
         return fail(SGR_E_INVALID, "layer alpha: dL_dmean3D, dL_dopacity, dL_dscale and dL_drot are required");
     if (!scratch) return fail(SGR_E_INVALID, "layer alpha: the scratch callback is required");
     const Switches sw = resolve_switches();
-    const int W = width, H = height;
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const size_t N = (size_t)W * H, T = (size_t)gx * gy;
-    const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
-    const SgrImgView iv = sgr_img_carve(image_buffer, N, T);
-    const int* radii_ptr = radii ? radii : gv.internal_radii;
+    const Frame f = make_frame(P, R, width, height, geom_buffer, binning_buffer, image_buffer, radii, sw);
     const int stride = sgr_partial_row_stride(0);
-    // scratch = [P float4: conic + depth terms between the two per-Gaussian stages][R partial rows][the two outputs of the
-    // row sum this head has no receiver for: dL/dmean2D and dL/dcolour, 3 P floats each]
-    const size_t cd_bytes = sgr_align_up((size_t)P * sizeof(float4), 256);
-    const size_t row_bytes = sgr_align_up((size_t)R * stride * sizeof(float), 256);
+    // behind the R partial rows: the row sum's two outputs this head has no receiver for, dL/dmean2D and dL/dcolour, 3 P floats each
     const size_t p3_bytes = sgr_align_up((size_t)P * 3 * sizeof(float), 256);
-    char* sbase = scratch(cd_bytes + row_bytes + 2 * p3_bytes, scratch_user);
-    if (!sbase) return fail(SGR_E_ALLOC, "layer alpha: backward scratch allocation failed");
-    float4* cd = reinterpret_cast<float4*>(sbase);
-    float* partials = reinterpret_cast<float*>(sbase + cd_bytes);
-    float* dL_dmean2D = reinterpret_cast<float*>(sbase + cd_bytes + row_bytes);
-    float* dL_dcolor = reinterpret_cast<float*>(sbase + cd_bytes + row_bytes + p3_bytes);
+    BwdScratch sc;
+    if (!bwd_scratch(scratch, scratch_user, P, (size_t)R, stride, 2 * p3_bytes, sc))
+        return fail(SGR_E_ALLOC, "layer alpha: backward scratch allocation failed");
     // The rows this walk writes are not the set the composite's backward marks (behind an opaque wall it writes rows the
-    // composite never does; in front of one, fewer): the bytes are cleared before and after, like sgr_backward_ex does for
-    // its own odd sets, so that either backward finds them as the forward left them.
-    uint8_t* touched = nullptr;
-    if (R > 0) {
-        const SgrBinView bv = sgr_bin_carve(binning_buffer, (size_t)R);
-        touched = bv.touched;
-        SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
-        if (split < P) {
-            sgr_launch_object_alpha_bwd(sw.exact, gx, -gy, iv.ranges, bv.vals[list_index(W, H, sw)], W, H, gv.rec, gv.u0, gv.tmask,
-                                        split, layer_alpha, layer_last, dL_dlayer_alpha, partials, stride, touched, (uint32_t)R,
-                                        stream);
-            SGR_STAGE("object_alpha_bwd");
-        }
+    // composite never does; in front of one, fewer): an odd set, cleared before and after.
+    if (const int rc = clear_touched(f, R, true, stream)) return rc;
+    if (R > 0 && split < P) {
+        sgr_launch_object_alpha_bwd(sw.exact, f.tiles(true), f.gv.u0, f.gv.tmask, split, layer_alpha, layer_last, dL_dlayer_alpha,
+                                    sc.partials, stride, f.bv.touched, (uint32_t)R, stream);
+        SGR_STAGE("object_alpha_bwd");
     }
     // S = 0, no SH (neither a read of the rows nor of the stored colour Jacobian, no dL/dSH), an empty statistics sink, no
     // colour event, no masked colour output
-    (sw.exact ? sgr_launch_gauss_bwd_strict : sgr_launch_gauss_bwd)(
-        P, 0, 0, 0, means3D, radii_ptr, nullptr, scales, rotations, cov3D_precomp, cam_slot(gv), gv, partials, stride, touched, cd,
-        dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, nullptr, dL_dscale, dL_drot, nullptr, SgrStatSink(), 0,
-        sw.exact ? 1 : 0, W, H, nullptr, sw.rs_wave ? 1 : 0, (uint32_t)R, nullptr, 1, dL_dcov3D ? 0 : 1, stream);
+    SgrGaussBwdArgs ga;
+    ga.P = P; ga.means3D = means3D; ga.scales = scales; ga.rotations = rotations; ga.cov3D_precomp = cov3D_precomp;
+    ga.partials = sc.partials; ga.row_stride = stride; ga.touched = f.bv.touched; ga.cd = sc.cd;
+    ga.dL_dmean2D = reinterpret_cast<float*>(sc.extra); ga.dL_dcolor = reinterpret_cast<float*>(sc.extra + p3_bytes);
+    ga.dL_dopacity = dL_dopacity; ga.dL_dmean3D = dL_dmean3D; ga.dL_dcov3D = dL_dcov3D; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot;
+    ga.row_limit = (uint32_t)R; ga.skip_sh = 1; ga.skip_cov = dL_dcov3D ? 0 : 1;
+    gauss_bwd(sw, ga, f, stream);
     SGR_STAGE("object_alpha gauss_bwd");
-    if (touched) SGR_HIP(hipMemsetAsync(touched, 0, (size_t)R, stream));
-    return 0;
+    return clear_touched(f, R, true, stream);
 }
 
 // ---- view-sharded training: factored exchange of the SH gradient (sgr_multiview.hip) ----
@@ -1068,10 +1024,11 @@ int sgr_set_lazy(int on) {
 }
 
 int sgr_lazy_status(int* num_rendered, int* capacity, int* flags) {
-    if (!t_lazy.host_vals || t_lazy.cap == 0) return fail(SGR_E_INVALID, "no lazy forward has run on this thread");
-    if (num_rendered) *num_rendered = (int)t_lazy.host_vals[4];
-    if (capacity) *capacity = (int)t_lazy.cap;
-    if (flags) *flags = lazy_flags(t_lazy);
+    const ThreadState& ts = t_state;
+    if (!ts.host_vals || ts.cap == 0) return fail(SGR_E_INVALID, "no lazy forward has run on this thread");
+    if (num_rendered) *num_rendered = (int)ts.host_vals[4];
+    if (capacity) *capacity = (int)ts.cap;
+    if (flags) *flags = ts.lazy_flags();
     return 0;
 }
 
@@ -1161,8 +1118,8 @@ int sgr_visible_filter(int P, int width, int height, const float* means3D, const
     hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0) return 0;
     const int W = width, H = height;
-    const int gx = (W + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (H + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    if (gx > SGR_MAX_GRID_DIM || gy > SGR_MAX_GRID_DIM) return fail(SGR_E_INVALID, "image too large");
+    const TileGrid g = tile_grid(W, H);
+    if (g.too_large()) return fail(SGR_E_INVALID, "image too large");
     if (!means3D || !viewmatrix || !projmatrix || !radii || !means2D)
         return fail(SGR_E_INVALID, "means3D, viewmatrix, projmatrix, radii and means2D are required");
     if (((scales == nullptr) || (rotations == nullptr)) == (cov3D_precomp == nullptr))
@@ -1171,7 +1128,7 @@ int sgr_visible_filter(int P, int width, int height, const float* means3D, const
     ca.view = viewmatrix; ca.proj = projmatrix;
     ca.tan_fovx = tan_fovx; ca.tan_fovy = tan_fovy;
     ca.focal_y = H / (2.0f * tan_fovy); ca.focal_x = W / (2.0f * tan_fovx);
-    ca.W = W; ca.H = H; ca.gx = gx; ca.gy = gy; ca.scale_modifier = scale_modifier;
+    ca.W = W; ca.H = H; ca.gx = g.gx; ca.gy = g.gy; ca.scale_modifier = scale_modifier;
     SgrGeomView gv;
     memset(&gv, 0, sizeof(gv));
     uint32_t* flag = nullptr;
@@ -1245,11 +1202,12 @@ int sgr_export_internal(int which, int P, int R, int width, int height, char* ge
     hipStream_t stream = (hipStream_t)stream_;
     const Switches sw = resolve_switches();
     const int debug = 1;
-    const int gx = (width + SGR_BLOCK_X - 1) / SGR_BLOCK_X, gy = (height + SGR_BLOCK_Y - 1) / SGR_BLOCK_Y;
-    const size_t N = (size_t)width * height, T = (size_t)gx * gy;
+    // (pointer arithmetic only: a branch below looks at a view only where its buffer was asked for and is there)
+    const Frame f = make_frame(std::max(P, 0), R, width, height, geom_buffer, binning_buffer, image_buffer, nullptr, sw);
+    const SgrGeomView& gv = f.gv;
+    const size_t N = f.g.N, T = f.g.T;
     if (which <= 7 || which == 14 || which == 16 || which == 17 || which == 18) {
         if (P <= 0) return 0;
-        const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
         if (which == 17) { SGR_HIP(hipMemcpyAsync(dst, gv.header + 5, 4, hipMemcpyDeviceToDevice, stream)); return 0; }
         if (which == 3) return fail(SGR_E_INVALID, "cov3D is not materialised (the backward recomputes it): sgr_export_cov3d");
         if (which == 7) {
@@ -1269,25 +1227,21 @@ int sgr_export_internal(int which, int P, int R, int width, int height, char* ge
     }
     if (which == 8 || which == 9 || which == 15 || which == 19) {
         if (R <= 0) return 0;
-        const SgrBinView bv = sgr_bin_carve(binning_buffer, (size_t)R);
-        if (which == 19) { SGR_HIP(hipMemcpyAsync(dst, bv.hlist, (size_t)R * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
-        if (which == 15) { SGR_HIP(hipMemcpyAsync(dst, bv.hit4, (size_t)R, hipMemcpyDeviceToDevice, stream)); return 0; }
-        const int cur = sorted_index(width, height), lcur = list_index(width, height, sw);
+        if (which == 19) { SGR_HIP(hipMemcpyAsync(dst, f.bv.hlist, (size_t)R * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
+        if (which == 15) { SGR_HIP(hipMemcpyAsync(dst, f.bv.hit4, (size_t)R, hipMemcpyDeviceToDevice, stream)); return 0; }
         if (which == 8) {
-            SGR_HIP(hipMemcpyAsync(dst, bv.vals[lcur], (size_t)R * 4, hipMemcpyDeviceToDevice, stream));
+            SGR_HIP(hipMemcpyAsync(dst, f.list, (size_t)R * 4, hipMemcpyDeviceToDevice, stream));
             sgr_strip_dead_kernel<<<(R + 255) / 256, 256, 0, stream>>>((uint32_t*)dst, R);  // marked-list mode: bit 31 = cannot blend
             SGR_STAGE("export point_list");
         } else {
-            const SgrGeomView gv = sgr_geom_carve(geom_buffer, (size_t)P);
-            sgr_launch_compose_keys(R, bv.keys[cur], sw.key16(T), bv.vals[lcur], gv.rec, (uint64_t*)dst, stream);
+            sgr_launch_compose_keys(R, f.keys, f.key16, f.list, gv.rec, (uint64_t*)dst, stream);
             SGR_STAGE("export keys");
         }
         return 0;
     }
-    const SgrImgView iv = sgr_img_carve(image_buffer, N, T);
-    if (which == 12) { SGR_HIP(hipMemcpyAsync(dst, iv.ranges, T * 8, hipMemcpyDeviceToDevice, stream)); return 0; }
-    if (which == 13) { SGR_HIP(hipMemcpyAsync(dst, iv.n_contrib, N * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
-    if (which == 20) { SGR_HIP(hipMemcpyAsync(dst, iv.n_contrib_k, N * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
+    if (which == 12) { SGR_HIP(hipMemcpyAsync(dst, f.iv.ranges, T * 8, hipMemcpyDeviceToDevice, stream)); return 0; }
+    if (which == 13) { SGR_HIP(hipMemcpyAsync(dst, f.iv.n_contrib, N * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
+    if (which == 20) { SGR_HIP(hipMemcpyAsync(dst, f.iv.n_contrib_k, N * 4, hipMemcpyDeviceToDevice, stream)); return 0; }
     return fail(SGR_E_INVALID, "unknown internal array");
 }
 
@@ -1317,6 +1271,14 @@ int sgr_export_cov3d(int P, const float* scales, float scale_modifier, const flo
 
 // ------------------------------------------------------------------------------------------------
 // primitive self-tests
+// one-sweep form: a look-back that gave up leaves its mark in the control block
+static int sort_gave_up(uint32_t n, const uint32_t* hist, hipStream_t stream) {
+    uint32_t e = 0;
+    if (!sgr_sort_get_one_sweep() || !n) return 0;
+    SGR_HIP(hipMemcpyAsync(&e, hist + SGR_SORT_MAX_PASS * 256 + SGR_SORT_MAX_PASS, 4, hipMemcpyDeviceToHost, stream));
+    SGR_HIP(hipStreamSynchronize(stream));
+    return e ? sgr_set_error(SGR_E_HIP, "radix sort: look-back gave up") : 0;
+}
 int sgr_test_scan(const uint32_t* in, uint32_t* out, size_t n, int inclusive, uint32_t* tmp, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int debug = 1;
@@ -1332,12 +1294,7 @@ int sgr_test_sort(uint64_t* keys0, uint64_t* keys1, uint32_t* vals0, uint32_t* v
     uint32_t* vals[2] = {vals0, vals1};
     const int cur = sgr_launch_sort_pairs(keys, vals, n, end_bit, hist, scan_tmp, stream);
     SGR_STAGE("sort");
-    if (sgr_sort_get_one_sweep() && n) {  // one-sweep form: a look-back that gave up leaves its mark in the control block
-        uint32_t e = 0;
-        SGR_HIP(hipMemcpyAsync(&e, hist + SGR_SORT_MAX_PASS * 256 + SGR_SORT_MAX_PASS, 4, hipMemcpyDeviceToHost, stream));
-        SGR_HIP(hipStreamSynchronize(stream));
-        if (e) return sgr_set_error(SGR_E_HIP, "radix sort: look-back gave up");
-    }
+    if (const int rc = sort_gave_up(n, hist, stream)) return rc;
     return cur;
 }
 int sgr_test_sort32(uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, uint32_t* vals1, uint32_t n, int end_bit,
@@ -1349,12 +1306,7 @@ int sgr_test_sort32(uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, uint32_t*
     uint32_t* vals[2] = {vals0, vals1};
     const int cur = sgr_launch_sort_pairs32(keys, vals, n, end_bit, hist, scan_tmp, stream, false, nullptr, nullptr, max_bits);
     SGR_STAGE("sort32");
-    if (sgr_sort_get_one_sweep() && n) {  // one-sweep form: a look-back that gave up leaves its mark in the control block
-        uint32_t e = 0;
-        SGR_HIP(hipMemcpyAsync(&e, hist + SGR_SORT_MAX_PASS * 256 + SGR_SORT_MAX_PASS, 4, hipMemcpyDeviceToHost, stream));
-        SGR_HIP(hipStreamSynchronize(stream));
-        if (e) return sgr_set_error(SGR_E_HIP, "radix sort: look-back gave up");
-    }
+    if (const int rc = sort_gave_up(n, hist, stream)) return rc;
     return cur;
 }
 size_t sgr_test_sort_hist_words(uint32_t n) { return sgr_sort_hist_words(n ? n : 1); }

@@ -16,6 +16,7 @@
 // Row layout (stride = the instantiation's 12 + SMAX floats rounded up to float4s, 16-B aligned): [0..2] dL/dmean2D (x, y, |x|+|y|),
 // [3..5] dL/dconic (x, y, w), [6] dL/dopacity, [7..9] dL/drgb, [10] dL/ddepth, [11..11+S) dL/dsemantic.
 #include "sgr_tile_walk.h"
+#include "sgr_launch.h"
 #include "sgr_reduce.h"
 
 #include <type_traits>
@@ -1043,54 +1044,33 @@ sgr_blend_bwd_kernel_v2(SGR_BWD_ARGS) {
 #endif  // SGR_WITH_VARIANTS
 
 template <int SMAX>
-static void launch_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, unsigned tiles, hipStream_t s, const uint2* ranges, const uint32_t* point_list,
-                       int W, int H, int S, int gx, int gy, const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* semantics,
-                       const float* alphas,
-                       const uint32_t* n_contrib, const uint8_t* hit4, const float* dL_dpix, const float* dL_ddepth,
-                       const float* dL_dalpha, const float* dL_dsem, float* partials, int row_stride, uint8_t* touched, uint32_t row_limit,
-                       const uint32_t* hlist, const uint32_t* n_contrib_k, const uint32_t* hl_flag) {
+static void launch_bwd(const SgrTileLists& tl, const SgrBlendBwdArgs& a, int row_stride, unsigned tiles, hipStream_t s) {
     constexpr bool kDet = true;  // every instantiation has the two-row deterministic combine (see SgrBwdBatch)
-    if (exact) {
-        sgr_blend_bwd_kernel_exact<SMAX><<<tiles, SGR_TILE_THREADS, 0, s>>>(
-            ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, n_contrib, hit4, dL_dpix, dL_ddepth, dL_dalpha,
-            dL_dsem, partials, row_stride, touched, row_limit, hlist, n_contrib_k, hl_flag);
-        return;
-    }
+    bool cull = a.cull, dpp = a.dpp, det = a.det;
+// the kernels' parameters, all instantiations alike
+#define SGR_BWD_LAUNCH(...)                                                                                                 \
+    __VA_ARGS__<<<tiles, SGR_TILE_THREADS, 0, s>>>(tl.ranges, tl.point_list, tl.W, tl.H, a.S, tl.gx, tl.gy, a.bg, tl.rec, a.u0, a.tmask,    \
+                                              a.semantics, a.alphas, a.n_contrib, a.hit4, a.dL_dpix, a.dL_ddepth, a.dL_dalpha,      \
+                                              a.dL_dsem, a.partials, row_stride, a.touched, a.row_limit, a.hlist, a.n_contrib_k,  \
+                                              a.hl_flag)
+    if (a.exact) return (void)SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_exact<SMAX>);
 #if SGR_WITH_VARIANTS
     if constexpr (SMAX == 0) {
-        if (v2 && dpp) {  // transposed accumulation (S = 0)
-#define SGR_V2(C, D) sgr_blend_bwd_kernel_v2<C, D><<<tiles, SGR_TILE_THREADS, 0, s>>>(                                    \
-            ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, n_contrib, hit4, dL_dpix, dL_ddepth,         \
-            dL_dalpha, dL_dsem, partials, row_stride, touched, row_limit, hlist, n_contrib_k, hl_flag)
-            if (cull) { if (det) SGR_V2(true, true); else SGR_V2(true, false); }
-            else { if (det) SGR_V2(false, true); else SGR_V2(false, false); }
-#undef SGR_V2
+        if (a.v2 && dpp) {  // transposed accumulation (S = 0)
+            if (cull) { if (det) SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_v2<true, true>); else SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_v2<true, false>); }
+            else { if (det) SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_v2<false, true>); else SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_v2<false, false>); }
             return;
         }
     }
-#else
-    (void)v2;
 #endif
     if (SMAX > 4) { cull = true; dpp = true; }  // the A/B switches (tests) exist for the small instantiations only
-#define SGR_GO(C, D)                                                                                                 \
-    do {                                                                                                             \
-        if constexpr (SMAX == 0) {                                                                                   \
-            if (det)                                                                                                 \
-                sgr_blend_bwd_kernel_s0<C, D, true><<<tiles, SGR_TILE_THREADS, 0, s>>>(                               \
-                    ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, n_contrib, hit4, dL_dpix, dL_ddepth,    \
-                    dL_dalpha, dL_dsem, partials, row_stride, touched, row_limit, hlist, n_contrib_k, hl_flag);                                               \
-            else                                                                                                     \
-                sgr_blend_bwd_kernel_s0<C, D, false><<<tiles, SGR_TILE_THREADS, 0, s>>>(                              \
-                    ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, n_contrib, hit4, dL_dpix, dL_ddepth,    \
-                    dL_dalpha, dL_dsem, partials, row_stride, touched, row_limit, hlist, n_contrib_k, hl_flag);                                               \
-        } else if (kDet && det)                                                                                      \
-            sgr_blend_bwd_kernel<SMAX, C, D, kDet><<<tiles, SGR_TILE_THREADS, 0, s>>>(                                \
-                ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, n_contrib, hit4, dL_dpix, dL_ddepth,        \
-                dL_dalpha, dL_dsem, partials, row_stride, touched, row_limit, hlist, n_contrib_k, hl_flag);                                                   \
-        else                                                                                                         \
-            sgr_blend_bwd_kernel<SMAX, C, D, false><<<tiles, SGR_TILE_THREADS, 0, s>>>(                               \
-                ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas, n_contrib, hit4, dL_dpix, dL_ddepth,        \
-                dL_dalpha, dL_dsem, partials, row_stride, touched, row_limit, hlist, n_contrib_k, hl_flag);                                                   \
+#define SGR_GO(C, D)                                                                            \
+    do {                                                                                        \
+        if constexpr (SMAX == 0) {                                                              \
+            if (det) SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_s0<C, D, true>);                     \
+            else SGR_BWD_LAUNCH(sgr_blend_bwd_kernel_s0<C, D, false>);                        \
+        } else if (kDet && det) SGR_BWD_LAUNCH(sgr_blend_bwd_kernel<SMAX, C, D, kDet>);       \
+        else SGR_BWD_LAUNCH(sgr_blend_bwd_kernel<SMAX, C, D, false>);                         \
     } while (0)
     if (cull && dpp) SGR_GO(true, true);
     else if constexpr (SMAX <= 4) {
@@ -1099,6 +1079,7 @@ static void launch_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, unsig
         else SGR_GO(false, false);
     }
 #undef SGR_GO
+#undef SGR_BWD_LAUNCH
 }
 
 // floats per partial row for S semantic channels: the kernel's SMAX bucket writes ceil((11+SMAX)/4) float4
@@ -1106,16 +1087,9 @@ static void launch_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, unsig
 // them to 64 bytes cost 25 % more row traffic in this kernel's stores and in the per-Gaussian row sum's loads)
 int sgr_partial_row_stride(int S) { return (SGR_ROW_BASE + sgr_smax(S) + 3) / 4 * 4; }
 
-void sgr_launch_blend_bwd(bool cull, bool dpp, bool det, bool v2, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W,
-                          int H, int S, const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* semantics, const float* alphas, const uint32_t* n_contrib,
-                          const uint8_t* hit4, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
-                          const float* dL_dsem, float* partials, uint8_t* touched, uint32_t row_limit, const uint32_t* hlist,
-                          const uint32_t* n_contrib_k, const uint32_t* hl_flag, hipStream_t s) {
-    if (gx <= 0 || gy == 0) return;
-    const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
-    const int stride = sgr_partial_row_stride(S);
-    sgr_with_smax(S, [&](auto N) {
-        launch_bwd<N>(cull, dpp, det, v2, exact, tiles, s, ranges, point_list, W, H, S, gx, gy, bg, rec, u0, tmask, semantics, alphas,
-                      n_contrib, hit4, dL_dpix, dL_ddepth, dL_dalpha, dL_dsem, partials, stride, touched, row_limit, hlist, n_contrib_k, hl_flag);
-    });
+void sgr_launch_blend_bwd(const SgrTileLists& tl, const SgrBlendBwdArgs& a, hipStream_t s) {
+    const unsigned tiles = tl.blocks();
+    if (!tiles) return;
+    const int stride = sgr_partial_row_stride(a.S);
+    sgr_with_smax(a.S, [&](auto N) { launch_bwd<N>(tl, a, stride, tiles, s); });
 }

@@ -7,6 +7,7 @@
 // forward.cu:442-444).  Results are identical to walking the full list: a culled instance can only
 // fail the alpha test for every pixel of the quadrant.
 #include "sgr_tile_walk.h"
+#include "sgr_launch.h"
 
 #ifndef SGR_FWD_SEL
 #define SGR_FWD_SEL 1  // selects of the blend step on an SGPR-pair lane mask (0: plain ?: -- the compiler's v_cndmask on VCC)
@@ -241,29 +242,19 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
     }
 }
 
-template <int SMAX>
-static void launch_fwd(bool cull, bool exact, unsigned tiles, hipStream_t s, const uint2* ranges, const uint32_t* point_list, int W,
-                       int H, int S, int gx, int gy, const float4* rec, const float* semantics, const float* bg, float* out_color, float* out_depth, float* out_alpha,
-                       float* out_semantic, uint32_t* n_contrib, uint8_t* hit4, uint32_t* hlist, uint32_t* n_contrib_k) {
-#define SGR_FWD_GO(C, E)                                                                                              \
-    sgr_blend_fwd_kernel<SMAX, C, E><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, S, gx, gy, rec, semantics, \
-                                                                        bg, out_color, out_depth, out_alpha, out_semantic,   \
-                                                                        n_contrib, hit4, hlist, n_contrib_k)
-    if (exact) SGR_FWD_GO(true, true);  // parity mode: with the cull (it is invisible in the results)
-    else if (cull) SGR_FWD_GO(true, false);
-    else SGR_FWD_GO(false, false);
-#undef SGR_FWD_GO
-}
-
-// S must be <= SGR_SEM_MAX (checked by the caller).
-void sgr_launch_blend_fwd(bool cull, bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                          int S, const float4* rec, const float* semantics,
-                          const float* bg, float* out_color, float* out_depth, float* out_alpha, float* out_semantic,
-                          uint32_t* n_contrib, uint8_t* hit4, uint32_t* hlist, uint32_t* n_contrib_k, hipStream_t s) {
-    if (gx <= 0 || gy == 0) return;
-    const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
+void sgr_launch_blend_fwd(bool cull, bool exact, const SgrTileLists& tl, int S, const float* semantics, const float* bg,
+                          float* out_color, float* out_depth, float* out_alpha, float* out_semantic, uint32_t* n_contrib,
+                          uint8_t* hit4, uint32_t* hlist, uint32_t* n_contrib_k, hipStream_t s) {
+    const unsigned tiles = tl.blocks();
+    if (!tiles) return;
     sgr_with_smax(S, [&](auto N) {
-        launch_fwd<N>(cull, exact, tiles, s, ranges, point_list, W, H, S, gx, gy, rec, semantics, bg, out_color, out_depth, out_alpha,
-                      out_semantic, n_contrib, hit4, hlist, n_contrib_k);
+#define SGR_FWD_GO(C, E)                                                                                                    \
+    sgr_blend_fwd_kernel<N, C, E><<<tiles, SGR_TILE_THREADS, 0, s>>>(tl.ranges, tl.point_list, tl.W, tl.H, S, tl.gx, tl.gy, tl.rec,   \
+                                                                     semantics, bg, out_color, out_depth, out_alpha, out_semantic, \
+                                                                     n_contrib, hit4, hlist, n_contrib_k)
+        if (exact) SGR_FWD_GO(true, true);  // parity mode: with the cull (it is invisible in the results)
+        else if (cull) SGR_FWD_GO(true, false);
+        else SGR_FWD_GO(false, false);
+#undef SGR_FWD_GO
     });
 }

@@ -20,6 +20,7 @@
 // staged any more either: its entries are treated like dead ones (no record fetch), which is what keeps the walk behind an
 // opaque background wall cheap while the object layer is still looking for its splats.
 #include "sgr_tile_walk.h"
+#include "sgr_launch.h"
 
 __device__ __forceinline__ float sgr_layer_out(float v, int clamp) {  // NaN stays NaN, as torch.clamp
     return clamp ? (v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v)) : v;
@@ -145,17 +146,13 @@ __global__ void __launch_bounds__(256) sgr_layers_fill_kernel(size_t N, const fl
     alpha1[i] = 0.0f;
 }
 
-void sgr_launch_blend_layers(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                             const float4* rec, int split, int P, const float* bg, int clamp, float* const color[2],
-                             float* const alpha[2], hipStream_t s) {
-    if (gx <= 0 || gy == 0) return;
-    const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
-    if (exact)
-        sgr_blend_layers_kernel<true><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, (uint32_t)P, bg,
-                                                                           clamp, color[0], alpha[0], color[1], alpha[1]);
-    else
-        sgr_blend_layers_kernel<false><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, (uint32_t)P, bg,
-                                                                            clamp, color[0], alpha[0], color[1], alpha[1]);
+void sgr_launch_blend_layers(bool exact, const SgrTileLists& tl, int split, int P, const float* bg, int clamp,
+                             float* const color[2], float* const alpha[2], hipStream_t s) {
+    const unsigned tiles = tl.blocks();
+    if (tiles) sgr_with_flag(exact, [&](auto E) {
+        sgr_blend_layers_kernel<E><<<tiles, SGR_TILE_THREADS, 0, s>>>(tl.ranges, tl.point_list, tl.W, tl.H, tl.gx, tl.gy, tl.rec, (uint32_t)split,
+                                                                    (uint32_t)P, bg, clamp, color[0], alpha[0], color[1], alpha[1]);
+    });
 }
 
 void sgr_launch_layers_fill(int W, int H, const float* bg, int clamp, float* const color[2], float* const alpha[2], hipStream_t s) {

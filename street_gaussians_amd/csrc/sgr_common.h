@@ -170,15 +170,11 @@ static inline SgrGeomView sgr_geom_carve(char* base, size_t P, char** end = null
     return v;
 }
 
-static inline size_t sgr_sort_blocks(size_t R) { return (R + SGR_SORT_ITEMS - 1) / SGR_SORT_ITEMS; }
-
 static inline SgrBinView sgr_bin_carve(char* base, size_t R, char** end = nullptr) {
     SgrBinView v;
     char* p = base;
     size_t Rn = R ? R : 1;
-    size_t nb = sgr_sort_blocks(Rn);
     size_t nh = sgr_sort_hist_words(Rn);
-    (void)nb;
     sgr_carve(p, v.header, 64);
     sgr_carve(p, v.keys[0], Rn);
     sgr_carve(p, v.keys[1], Rn);

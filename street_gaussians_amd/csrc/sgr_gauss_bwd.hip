@@ -8,6 +8,7 @@
 // so the caller allocates the gradient tensors uninitialised instead of the reference's eleven
 // torch::zeros (rasterize_points.cu:166-176).
 #include "sgr_math.h"
+#include "sgr_launch.h"
 
 #include <cstdlib>
 
@@ -672,17 +673,11 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
     *reinterpret_cast<float4*>(dL_drot + 4 * (size_t)idx) = make_float4(drot[0], drot[1], drot[2], drot[3]);
 }
 
-// returns non-zero when `after_rows` could not be recorded (everything is launched regardless)
-int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const int* radii, const float* shs,
-                          const float* scales, const float* rotations, const float* cov3D_precomp, const SgrCam* cam,
-                          const SgrGeomView& gv, const float* partials, int row_stride, const uint8_t* touched,
-                          float4* cd, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                          float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dsemantic,
-                          const SgrStatSink& sink, int quad, int exact, int W, int H, hipEvent_t after_rows, int rs_wave,
-                          uint32_t row_limit, float* masked_color_out, int skip_sh, int skip_cov, hipStream_t s) {
+int sgr_launch_gauss_bwd(const SgrGaussBwdArgs& a, hipStream_t s) {
+    const int P = a.P, S = a.S;
     if (P <= 0) return 0;
-    const float lsc = exact ? 1.0f : SGR_LOG2E;
-    const float kx = (0.5f * (float)W) / lsc, ky = (0.5f * (float)H) / lsc;
+    const float lsc = a.exact ? 1.0f : SGR_LOG2E;
+    const float kx = (0.5f * (float)a.W) / lsc, ky = (0.5f * (float)a.H) / lsc;
     const unsigned nb = (P + SGR_GB_THREADS - 1) / SGR_GB_THREADS;
     // switch bit 9 / SGR_RS_WAVE=1: the wave-cooperative row sum instead of the four-lanes-per-Gaussian one (A/B: measured SLOWER on MI355X --
     // per-Gaussian backward stage 0.258 vs 0.213 ms at 1 M Gaussians, 1.14 vs 0.76 ms at 5 M, 0.83 vs 0.57 ms at 2 M + 19
@@ -690,33 +685,31 @@ int sgr_launch_gauss_bwd(int P, int D, int M, int S, const float* means3D, const
     // (both A/B forms exist only in a -DSGR_WITH_VARIANTS=1 build: tools/build_variant.py)
 #if SGR_WITH_VARIANTS
     const unsigned nb4 = (unsigned)(((size_t)P * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
-    const bool quads = !rs_wave;  // (sgr_test_switches bit 9)
     const unsigned nbw = (unsigned)((P + 64 * SGR_RSW_WAVES - 1) / (64 * SGR_RSW_WAVES));
-    if (quad) {  // the scalar-walk blend backward's rows (S = 0 only)
-        sgr_row_sum_kernel<0, true><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
-                                                                  dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink, kx, ky, exact, 0xffffffffu, masked_color_out);
-    } else if (!quads) {
+    if (a.quad) {  // the scalar-walk blend backward's rows (S = 0 only)
+        sgr_row_sum_kernel<0, true><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, a.radii, a.gv, a.partials, a.row_stride, a.touched, a.dL_dmean2D,
+                                                                  a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink, kx, ky, a.exact,
+                                                                  0xffffffffu, a.masked_color_out);
+    } else if (a.rs_wave) {  // (sgr_test_switches bit 9)
         sgr_with_smax(S, [&](auto N) {
-            sgr_row_sum_wave_kernel<N><<<nbw, 64 * SGR_RSW_WAVES, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
-                                                                         dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink);
+            sgr_row_sum_wave_kernel<N><<<nbw, 64 * SGR_RSW_WAVES, 0, s>>>(P, S, a.radii, a.gv, a.partials, a.row_stride, a.touched, a.dL_dmean2D,
+                                                                         a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink);
         });
     } else
-#else
-    (void)quad; (void)rs_wave;
 #endif
     sgr_with_smax(S, [&](auto N) {
         constexpr int G = sgr_rs_pair<decltype(N)::value, false>;  // Gaussians per quad of this instantiation
         const unsigned nb4 = (unsigned)((((size_t)P + G - 1) / G * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
-        sgr_row_sum_kernel<N, false><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, radii, gv, partials, row_stride, touched, dL_dmean2D,
-                                                                   dL_dopacity, dL_dcolor, dL_dsemantic, cd, sink, kx, ky, exact,
-                                                                   row_limit, masked_color_out);
+        sgr_row_sum_kernel<N, false><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, a.radii, a.gv, a.partials, a.row_stride, a.touched, a.dL_dmean2D,
+                                                                   a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink, kx, ky, a.exact,
+                                                                   a.row_limit, a.masked_color_out);
     });
     // dL/dmean2D, dL/dopacity, dL/dcolour are final from here on.  A failed record must not pass silently: the reducer's side
-    // stream would wait on a stale record and read the colour gradient unsynchronised -- the error is picked up by the
-    // failure is returned to sgr_backward_ex, which reports SGR_E_HIP
-    const bool ev_failed = after_rows && hipEventRecord(after_rows, s) != hipSuccess;
-    sgr_gauss_bwd_kernel<<<nb, SGR_GB_THREADS, 0, s>>>(P, D, M, means3D, radii, shs, scales, rotations, cov3D_precomp, cam,
-                                                       gv, cd, dL_dmean2D, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                                       dL_dscale, dL_drot, skip_sh, skip_cov);
+    // stream would wait on a stale record and read the colour gradient unsynchronised -- the failure is returned to
+    // sgr_backward_ex, which reports SGR_E_HIP
+    const bool ev_failed = a.after_rows && hipEventRecord(a.after_rows, s) != hipSuccess;
+    sgr_gauss_bwd_kernel<<<nb, SGR_GB_THREADS, 0, s>>>(P, a.D, a.M, a.means3D, a.radii, a.shs, a.scales, a.rotations, a.cov3D_precomp,
+                                                       a.cam, a.gv, a.cd, a.dL_dmean2D, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D,
+                                                       a.dL_dsh, a.dL_dscale, a.dL_drot, a.skip_sh, a.skip_cov);
     return ev_failed ? 1 : 0;
 }

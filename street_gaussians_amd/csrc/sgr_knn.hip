@@ -15,6 +15,7 @@
 
 #include "../../include/sgr.h"
 #include "sgr_common.h"
+#include "sgr_launch.h"
 #include <float.h>
 
 #define SGR_KNN_BOX 1024  // simple_knn.cu:12

@@ -8,6 +8,7 @@
 // dRGB_v per Gaussian and rebuild  sum_v Y(dir_v) (x) dRGB_v  locally, in view order (deterministic, identical on
 // every rank): 12 B per Gaussian and view on the wire instead of a 192 B all-reduce.
 #include "sgr_math.h"
+#include "sgr_launch.h"
 
 #define SGR_MV_THREADS 256
 

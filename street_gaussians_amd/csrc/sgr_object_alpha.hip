@@ -22,6 +22,7 @@
 // (one writer per element); after the round one thread per slot adds the rows of the quadrants that visited it, in
 // quadrant order, turns the moments into gradients exactly as the shipped flush does and writes the row once.
 #include "sgr_tile_walk.h"
+#include "sgr_launch.h"
 #include "sgr_reduce.h"
 
 #define SGR_OA_BATCH 128  // list positions per round of the backward (20 KB of LDS: occupancy is set by registers)
@@ -243,27 +244,19 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
     }
 }
 
-void sgr_launch_object_alpha_fwd(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                                 const float4* rec, int split, float* out_alpha, uint32_t* out_last, hipStream_t s) {
-    if (gx <= 0 || gy == 0) return;
-    const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);  // supertile-ordered grid incl. padding blocks
-    if (exact)
-        sgr_object_alpha_fwd_kernel<true><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, out_alpha, out_last);
-    else
-        sgr_object_alpha_fwd_kernel<false><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, (uint32_t)split, out_alpha, out_last);
+void sgr_launch_object_alpha_fwd(bool exact, const SgrTileLists& tl, int split, float* out_alpha, uint32_t* out_last, hipStream_t s) {
+    const unsigned tiles = tl.blocks();
+    if (tiles) sgr_with_flag(exact, [&](auto E) {
+        sgr_object_alpha_fwd_kernel<E><<<tiles, SGR_TILE_THREADS, 0, s>>>(tl.ranges, tl.point_list, tl.W, tl.H, tl.gx, tl.gy, tl.rec, (uint32_t)split, out_alpha, out_last);
+    });
 }
 
-// row_stride: sgr_partial_row_stride(0) = 12 floats (three float4 stores per row)
-void sgr_launch_object_alpha_bwd(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                                 const float4* rec, const uint32_t* u0, const uint64_t* tmask, int split, const float* layer_alpha,
-                                 const uint32_t* layer_last, const float* dL_dlayer_alpha, float* partials, int row_stride,
-                                 uint8_t* touched, uint32_t row_limit, hipStream_t s) {
-    if (gx <= 0 || gy == 0) return;
-    const unsigned tiles = sgr_xcd_grid_blocks(gx, gy < 0 ? -gy : gy);
-    if (exact)
-        sgr_object_alpha_bwd_kernel<true><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, u0, tmask, (uint32_t)split,
-                                                                           layer_alpha, layer_last, dL_dlayer_alpha, partials, row_stride, touched, row_limit);
-    else
-        sgr_object_alpha_bwd_kernel<false><<<tiles, SGR_TILE_THREADS, 0, s>>>(ranges, point_list, W, H, gx, gy, rec, u0, tmask, (uint32_t)split,
-                                                                            layer_alpha, layer_last, dL_dlayer_alpha, partials, row_stride, touched, row_limit);
+void sgr_launch_object_alpha_bwd(bool exact, const SgrTileLists& tl, const uint32_t* u0, const uint64_t* tmask, int split,
+                                 const float* layer_alpha, const uint32_t* layer_last, const float* dL_dlayer_alpha,
+                                 float* partials, int row_stride, uint8_t* touched, uint32_t row_limit, hipStream_t s) {
+    const unsigned tiles = tl.blocks();
+    if (tiles) sgr_with_flag(exact, [&](auto E) {
+        sgr_object_alpha_bwd_kernel<E><<<tiles, SGR_TILE_THREADS, 0, s>>>(tl.ranges, tl.point_list, tl.W, tl.H, tl.gx, tl.gy, tl.rec, u0, tmask, (uint32_t)split,
+                                                                        layer_alpha, layer_last, dL_dlayer_alpha, partials, row_stride, touched, row_limit);
+    });
 }

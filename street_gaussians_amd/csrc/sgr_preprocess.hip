@@ -6,6 +6,7 @@
 // outputs are packed into three float4 records per Gaussian so that the tile kernels gather each
 // instance with three 16-byte loads.
 #include "sgr_math.h"
+#include "sgr_launch.h"
 
 #include <cstdlib>
 

@@ -25,6 +25,7 @@
 //   up to 4096 / 8192 entries     8 / 16 waves per tile, three barriers per pass;
 //   beyond                        the same passes over a ping-pong in HBM (the tile's own slices of the binning buffer).
 #include "sgr_common.h"
+#include "sgr_launch.h"
 
 #define SGR_TS_BITS 9
 #define SGR_TS_NB (1 << SGR_TS_BITS)

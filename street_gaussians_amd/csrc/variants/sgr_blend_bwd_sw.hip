@@ -20,6 +20,7 @@
 // Bit-reproducible like the LDS kernel: every float sum has a fixed order (lanes of a wave by the reduction tree, rows of
 // a Gaussian by (tile, quadrant) in the row sum).
 #include "../sgr_math.h"
+#include "../sgr_launch.h"
 #include "../sgr_reduce.h"
 
 typedef int sgr_i16 __attribute__((ext_vector_type(16)));
@@ -368,18 +369,13 @@ sgr_blend_bwd_sw_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
 // rows per instance / flag semantics of this kernel: four rows (one per quadrant) of `sgr_partial_row_stride(0)` floats,
 // holding the raw moments in natural order [S gx, S gy, S abs, S gxx, S gxy, S gyy, S Gd, r, g, b, depth, -];
 // touched[u] = mask of the quadrant rows that were written (sgr_row_sum_kernel<0, true> consumes both)
-void sgr_launch_blend_bwd_sw(bool exact, int gx, int gy, const uint2* ranges, const uint32_t* point_list, int W, int H,
-                             const float* bg, const float4* rec, const uint32_t* u0, const uint64_t* tmask, const float* alphas,
-                             const uint32_t* n_contrib, const uint8_t* hit4, const float* dL_dpix, const float* dL_ddepth,
-                             const float* dL_dalpha, float* partials, int row_stride, uint8_t* touched, hipStream_t s) {
-    if (gx <= 0 || gy <= 0) return;
-    const unsigned waves = 4u * sgr_xcd_grid_blocks(gx, gy);
-    if (exact)
-        sgr_blend_bwd_sw_kernel<true><<<waves, 64, 0, s>>>(ranges, point_list, W, H, gx, gy, bg, rec, u0, tmask, alphas, n_contrib, hit4,
-                                                          dL_dpix, dL_ddepth, dL_dalpha, partials, row_stride,
-                                                          reinterpret_cast<uint32_t*>(touched));
-    else
-        sgr_blend_bwd_sw_kernel<false><<<waves, 64, 0, s>>>(ranges, point_list, W, H, gx, gy, bg, rec, u0, tmask, alphas, n_contrib, hit4,
-                                                           dL_dpix, dL_ddepth, dL_dalpha, partials, row_stride,
-                                                           reinterpret_cast<uint32_t*>(touched));
+// (the supertile order only: tl.gy > 0)
+void sgr_launch_blend_bwd_sw(const SgrTileLists& tl, const SgrBlendBwdArgs& a, int row_stride, hipStream_t s) {
+    if (tl.gx <= 0 || tl.gy <= 0) return;
+    const unsigned waves = 4u * tl.blocks();
+    sgr_with_flag(a.exact, [&](auto E) {
+        sgr_blend_bwd_sw_kernel<E><<<waves, 64, 0, s>>>(tl.ranges, tl.point_list, tl.W, tl.H, tl.gx, tl.gy, a.bg, tl.rec, a.u0, a.tmask, a.alphas,
+                                                       a.n_contrib, a.hit4, a.dL_dpix, a.dL_ddepth, a.dL_dalpha, a.partials, row_stride,
+                                                       reinterpret_cast<uint32_t*>(a.touched));
+    });
 }

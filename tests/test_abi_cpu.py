@@ -134,6 +134,27 @@ def test_host_only_entry_points_answer_without_a_gpu(lib):
     assert lib.sgr_set_lazy(-1) == prev
 
 
+def test_cross_file_launchers_are_declared_in_one_header_only():
+    """Every launcher one kernel source defines and another calls is declared in csrc/sgr_launch.h, which the defining
+    file includes too: no .hip file carries a prototype (a declaration ending in `;`) of its own that could go stale.  The
+    header is a build dependency (build.HEADERS: objects rebuild, source_sha16 sees it) and declares them."""
+    from street_gaussians_amd import build
+    proto = re.compile(r"^[A-Za-z_][\w \t\*&:<>]*?\b(sgr_launch_\w+|sgr_knn_impl|sgr_partial_row_stride)\s*\([^;{}]*\)\s*;", re.M)
+    stale = {}
+    for path in sorted(glob.glob(os.path.join(build.CSRC, "**", "*.hip"), recursive=True)):
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(path).read(), flags=re.S)
+        names = [m.group(1) for m in proto.finditer(text)]  # (at column 0: a call is indented, a definition ends in `{`)
+        if names:
+            stale[os.path.relpath(path, build.CSRC)] = names
+    assert not stale, stale
+    assert "sgr_launch.h" in build.HEADERS
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(build.CSRC, "sgr_launch.h")).read(), flags=re.S)
+    declared = {m.group(1) for m in proto.finditer(header)}
+    assert {"sgr_launch_preprocess", "sgr_launch_blend_fwd", "sgr_launch_blend_bwd", "sgr_launch_blend_bwd_sw",
+            "sgr_knn_impl", "sgr_partial_row_stride"} <= declared, sorted(declared)
+    assert re.search(r"\bsgr_launch_gauss_bwd\s*,\s*sgr_launch_gauss_bwd_strict\s*;", header)  # one declaration, both names
+
+
 SW_ENUM = re.compile(r"^\s*SGR_SW_(\w+)\s*=\s*1\s*<<\s*(\d+)\s*,?", re.M)
 VARIANT_BITS = (1 << 4) | (1 << 5) | (1 << 8) | (1 << 9)  # USE_V2, USE_ONESWEEP, USE_SW, USE_RS_WAVE
 

@@ -45,5 +45,5 @@ if any(f.replace(" ", "") == "-DSGR_WITH_VARIANTS=1" for f in flags):  # the rej
 with ThreadPoolExecutor(max_workers=8) as ex:
     objs = list(ex.map(one, sources))
 lib = os.path.join(out_dir, f"libsgr_hip_{name}.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
+subprocess.check_call(["/opt/rocm/bin/hipcc"] + b.LINK_FLAGS + ["-o", lib] + objs)
 print(lib)
