@@ -165,6 +165,58 @@ __device__ __forceinline__ int sgr_popc64(uint64_t m) {
     return r;
 }
 
+// the first nb bits of a lane or slot mask
+__device__ __forceinline__ uint64_t sgr_first_bits(const uint64_t m, const int nb) {
+    return nb >= 64 ? m : (nb <= 0 ? 0ull : (m & ((1ull << nb) - 1ull)));
+}
+
+// VROWS: a visit with at least one hitting pixel takes the wave's next row (`rown`, wave-uniform) and sets its bit in `vis`
+template <bool VROWS>
+__device__ __forceinline__ int sgr_claim_visit_row(int& rown, uint64_t& vis, const int j) {
+    const int rowi = rown;
+    if constexpr (VROWS) {
+        rown++;
+        vis = sgr_bitset1(vis, j & 63);
+    }
+    return rowi;
+}
+
+// VROWS, plan rows: from the survivor masks of all four quadrants (wave-uniform: scalar registers) how many slots of this
+// round are walked -- the return value: all of them unless the masks hold more visits than the CAP rows, then (rare) the
+// largest multiple of 32 slots whose visits fit -- and the first row of every quadrant.
+template <int BATCH, int CAP>
+__device__ __forceinline__ int sgr_bwd_plan_rows(const uint64_t (&sBits)[4][4], int (&vfirst)[4]) {
+    constexpr int NCH = BATCH / 64;
+    int lim = BATCH;
+    uint64_t raw[4][NCH];
+    int total = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            raw[q][c] = sgr_uniform_u64(sBits[q][c]);
+            total += sgr_popc64(raw[q][c]);
+        }
+    if (total > CAP) {
+        for (lim = BATCH - 32; lim > 32; lim -= 32) {
+            int t = 0;
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int c = 0; c < NCH; c++) t += sgr_popc64(sgr_first_bits(raw[q][c], lim - 64 * c));
+            if (t <= CAP) break;
+        }
+    }
+    int first = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        vfirst[q] = first;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) first += sgr_popc64(sgr_first_bits(raw[q][c], lim - 64 * c));
+    }
+    return lim;
+}
+
 template <int SMAX, bool CULL, bool DPP, bool DET, int BATCH, bool EXACT = false>
 __device__ __forceinline__ void
 sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H, int S,
@@ -257,8 +309,8 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     // d(pixel)/d(ndc) (backward.cu:501-502) with the 1/log2(e) of the pre-scaled conic folded in
     // EXACT (parity mode): the conic is staged with exact power-of-two scalings only (scale constant 1 instead of log2 e),
     // G comes from the reference's own power expression + the accurate expf, T is recovered by a true division
-    constexpr float LSC = EXACT ? 1.0f : SGR_LOG2E;
-    const float kx = (0.5f * (float)W) / LSC, ky = (0.5f * (float)H) / LSC;
+    const SgrNdcScale ks = sgr_ndc_scale(W, H, EXACT);
+    const float kx = ks.kx, ky = ks.ky;
 
     // colour / depth recurrences as register pairs {C0, C1} and {C2, D}: the four channels follow the same recurrence,
     // and the float4 {r, g, b, depth} read from LDS is already laid out that way, so they run on v_pk_mul / v_pk_fma
@@ -278,7 +330,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     // instead of after it).
     float Arec = 0.f, u_last = 0.f;
 
-    // highest list position any pixel of the tile blended
+    // highest list position any pixel of the tile blended (own code: inlined from a shared function every prologue reschedules)
     int mx = lastc;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
@@ -298,6 +350,8 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     // The staging of a round is a dependent pair of gathers (list entry -> record).  The first half is taken out of the
     // round: the entry (and its hit byte) of round n + 1 is loaded while round n walks -- 2 VGPRs held across the walk --
     // so that a round opens with the record gather itself (SGR_BWD_PREFETCH, A/B in DESIGN.md section 10).
+    // (Three copies of the fetch on purpose: as one lambda or function the S = 0 kernels spill a scalar pair through v_writelane.
+    // The round's stages -- stage, plan rows, walk, flush -- are comments, not lambdas: those cost the unrolled chunk loop.)
 #ifndef SGR_BWD_PREFETCH
 #define SGR_BWD_PREFETCH 1
 #endif
@@ -315,7 +369,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
         }
     }
     for (int hi = maxc - 1; hi >= 0;) {
-        // slot t of this batch holds list position hi - t (descending: back to front)
+        // STAGE: slot t of this batch holds list position hi - t (descending: back to front)
         sgr_lds_barrier();  // previous batch fully consumed (rows written) before LDS is overwritten
         const bool stager = tid < BATCH;  // whole waves: the batch is a multiple of 64
         const int pos = stager ? hi - tid : -1;
@@ -341,11 +395,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
             const float4 d4 = r[3];
             sB[tid] = sgr_stage_conic_mode<EXACT>(b);
             sC[tid] = r[2];
-            const uint32_t dy_ = __float_as_uint(d4.y);
-            // first row of the Gaussian (compact array, L2-resident) + rank of this tile among the tiles it is emitted for:
-            // rides in the spare word of the slot's position record (written and read back by this thread only)
-            const uint32_t urow = sgr_row_of(dy_, tx, ty, u0, tmask, g);
-            sA[tid] = make_float4(a.x, a.y, __uint_as_float(urow), 0.0f);
+            const bool live = sgr_stage_bwd_row(a, d4, g, tx, ty, u0, tmask, row_limit, sA[tid]);
             if (SMAX > 0) {
 #pragma unroll
                 for (int ch = 0; ch < SMAX; ch++) sSem[tid * SMAX + ch] = ch < S ? semantics[(size_t)g * S + ch] : 0.0f;
@@ -353,10 +403,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
             // which quadrants to walk: the forward's record of the quadrants it blended this instance into (exactly the
             // visits that can contribute; nothing to compute), else the geometric cull the forward uses
             mask4 = CULL ? (hit4 != nullptr ? h_raw : sgr_quadrant_mask(a, b, tx0, ty0)) : 0xFu;
-            // lazy forward (sgr_set_lazy) whose frame had more instances than the list capacity: the rows are numbered over ALL
-            // instances (index-order scan), the row array holds `row_limit` of them -- rows past it are not visited (the frame
-            // is reported invalid one call later; nothing may be written outside the buffers meanwhile)
-            if (urow >= row_limit) mask4 = 0;
+            if (!live) mask4 = 0;
         }
         if (SGR_BWD_PREFETCH) {  // next round's list entries: in flight under this round's walk
             const int posn = stager ? (hi - BATCH) - tid : -1;
@@ -369,81 +416,114 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
         if (stager) sgr_store_cull_ballots(mask4, lane, wave, sBits);
         sgr_lds_barrier();
 
-        // VROWS: the survivor masks of all four quadrants (wave-uniform: scalar registers), how many slots of this round are
-        // walked (`lim`: all of them unless the masks hold more visits than there are rows) and the first row of every quadrant
-        int lim = BATCH;
-        uint64_t vm[4][NCH];
-        int vfirst[4] = {0, 0, 0, 0};
-        if constexpr (VROWS) {
-            auto below = [](const uint64_t m, const int nb) { return nb >= 64 ? m : (nb <= 0 ? 0ull : (m & ((1ull << nb) - 1ull))); };
-            uint64_t raw[4][NCH];
-            int total = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-#pragma unroll
-                for (int c = 0; c < NCH; c++) {
-                    raw[q][c] = sgr_uniform_u64(sBits[q][c]);
-                    total += sgr_popc64(raw[q][c]);
-                }
-            if (total > CAP) {  // rare: shrink the round to the largest multiple of 32 slots whose visits fit the rows
-                for (lim = BATCH - 32; lim > 32; lim -= 32) {
-                    int t = 0;
-#pragma unroll
-                    for (int q = 0; q < 4; q++)
-#pragma unroll
-                        for (int c = 0; c < NCH; c++) t += sgr_popc64(below(raw[q][c], lim - 64 * c));
-                    if (t <= CAP) break;
-                }
-            }
-            int first = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                vfirst[q] = first;
-#pragma unroll
-                for (int c = 0; c < NCH; c++) {
-                    vm[q][c] = below(raw[q][c], lim - 64 * c);
-                    first += sgr_popc64(vm[q][c]);
-                }
-            }
-        }
+        // PLAN ROWS
+        int lim = BATCH, vfirst[4] = {0, 0, 0, 0};
+        if constexpr (VROWS) lim = sgr_bwd_plan_rows<BATCH, CAP>(sBits, vfirst);
         int rown = 0;  // VROWS: the row of this wave's next visit
-        constexpr int kq = SPK;                              // sparse visits: the threshold ...
-        const int stage_off = (CAP + wave_s * SPK) * ACCW;   // ... and this wave's stage (floats from sAcc; wave-uniform)
+        const int stage_off = (CAP + wave_s * SPK) * ACCW;  // sparse visits: this wave's stage (floats from sAcc; wave-uniform)
         if constexpr (VROWS) {
 #pragma unroll
             for (int q = 0; q < 4; q++) rown = (wave_s == q) ? vfirst[q] : rown;
         }
-        (void)kq; (void)stage_off;
 
+        // DENSE visit: the folded reduction of v[0..10] and the channel products wm * dL/dsemantic into the row at dst, 16 values
+        // at a time (one result register, one ds_add_f32 each): the same instructions as one pass over all NVAL values, but the
+        // products are formed chunk by chunk, so a wide instantiation keeps 16 + 8 instead of NVAL + NVAL/2 registers live
+        auto dense_fold = [&](const float (&v)[NVAL], const float wm, float* dst) __attribute__((always_inline)) {
+            auto fold_chunk = [&](auto C0, auto CN) __attribute__((always_inline)) {
+                constexpr int c0 = decltype(C0)::value, cn = decltype(CN)::value;
+                float vv[cn], g[1];
+#pragma unroll
+                for (int k = 0; k < cn; k++) {
+                    const int idx = c0 + k;
+                    vv[k] = idx < SGR_ROW_BASE ? v[idx < NVAL ? idx : 0]
+                                               : (idx - SGR_ROW_BASE < SMAX ? wm * dLdS[(idx - SGR_ROW_BASE) % NS] : 0.0f);
+                }
+                sgr_wave_reduce_fold<cn>(vv, g);
+                if (fold_leader && fold_t0 < cn / 4) {
+                    if constexpr (VROWS) dst[c0] = g[0];  // the visit's own row: one writer
+                    else atomicAdd(&dst[c0], g[0]);
+                }
+            };
+            fold_chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, (NVAL < 16 ? NVAL : 16)>{});
+            if constexpr (NVAL > 16)
+                fold_chunk(std::integral_constant<int, 16>{}, std::integral_constant<int, (NVAL - 16 < 16 ? NVAL - 16 : 16)>{});
+            if constexpr (NVAL > 32)
+                fold_chunk(std::integral_constant<int, 32>{}, std::integral_constant<int, (NVAL - 32 < 16 ? NVAL - 32 : 16)>{});
+            static_assert(NVAL <= 48, "add a fold chunk");
+        };
+        // SPARSE visit (see SGR_SPARSE_K): kc <= SPK lanes (hm) hit.  They file their twelve values in the wave's stage, the
+        // lanes that own a row position add the entries in rank order and store the sum into the visit's own row `rowi`.
+        auto sparse_sum = [&](const uint64_t hm, const int kc, const bool hit, const float (&v)[NVAL], const int rowi) __attribute__((always_inline)) {
+            if (hit) {  // entry = rank among the hit lanes; an entry is laid out like a row (float4 t = values 4t, 4t+2, 4t+1, 4t+3)
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+                // 32-bit stores written as ds_write_b32 (the optimiser merges plain stores into ds_write_b128, which
+                // wants its four values in consecutive registers: the copies that takes landed in the dense path too)
+                const uint32_t ea = sgr_lds_addr(sAcc + stage_off) + rank * 48u;
+#define SGR_STAGE_ST(OFF, VAL) asm volatile("ds_write_b32 %0, %1 offset:" #OFF : : "v"(ea), "v"(VAL) : "memory")
+                SGR_STAGE_ST(0, v[0]); SGR_STAGE_ST(4, v[2]); SGR_STAGE_ST(8, v[1]); SGR_STAGE_ST(12, v[3]);
+                SGR_STAGE_ST(16, v[4]); SGR_STAGE_ST(20, v[6]); SGR_STAGE_ST(24, v[5]); SGR_STAGE_ST(28, v[7]);
+                SGR_STAGE_ST(32, v[8]); SGR_STAGE_ST(36, v[10]); SGR_STAGE_ST(40, v[9]); SGR_STAGE_ST(44, v[11]);
+#undef SGR_STAGE_ST
+            }
+            __builtin_amdgcn_wave_barrier();  // same wave, program order: the LDS serves the reads below after the writes above
+            if (fold_leader && fold_t0 < NVAL / 4) {
+                const float* src = sAcc + (acc_fold_off + stage_off);
+                // kc is wave-uniform: one case, all its loads in flight at once, adds in rank order
+                auto sum_first = [&](auto KC) __attribute__((always_inline)) {
+                    constexpr int kk = decltype(KC)::value, k0 = kk < 8 ? kk : 8;
+                    float a[k0];  // (at most eight loads in flight: the kernel lives on 64 registers)
+#pragma unroll
+                    for (int e = 0; e < k0; e++) a[e] = src[e * 12];
+                    float t = a[0];
+#pragma unroll
+                    for (int e = 1; e < k0; e++) t += a[e];
+                    if constexpr (kk > 8) {
+                        float b[kk - 8];
+#pragma unroll
+                        for (int e = 8; e < kk; e++) b[e - 8] = src[e * 12];
+#pragma unroll
+                        for (int e = 8; e < kk; e++) t += b[e - 8];
+                    }
+                    return t;
+                };
+                float t = 0.0f;
+                switch (kc) {
+#define SGR_SPARSE_CASE(N) case N: if constexpr (N <= SPK) t = sum_first(std::integral_constant<int, (N <= SPK ? N : 1)>{}); break
+                    SGR_SPARSE_CASE(1); SGR_SPARSE_CASE(2); SGR_SPARSE_CASE(3); SGR_SPARSE_CASE(4);
+                    SGR_SPARSE_CASE(5); SGR_SPARSE_CASE(6); SGR_SPARSE_CASE(7); SGR_SPARSE_CASE(8);
+                    SGR_SPARSE_CASE(9); SGR_SPARSE_CASE(10); SGR_SPARSE_CASE(11); SGR_SPARSE_CASE(12);
+                    SGR_SPARSE_CASE(13); SGR_SPARSE_CASE(14); SGR_SPARSE_CASE(15); SGR_SPARSE_CASE(16);
+#undef SGR_SPARSE_CASE
+                    default: break;
+                }
+                sAcc[acc_fold_off + rowi * ACCW] = t;  // the visit's own row: one writer
+                // keeps the optimiser from merging this store with the dense path's: the merged tail made the
+                // twelve values live across this block (and the loads above serialise for want of registers)
+                asm volatile("; sparse visit done" ::: "memory");
+            }
+        };
         uint64_t vis = 0;  // VROWS: the slots of the current chunk this wave gave a row (scalar)
-        // VROWS: a visit with at least one hitting pixel takes the wave's next row (`rown`, wave-uniform) and sets its bit in `vis`
+        // One VISIT: sgr_bwd_hit + sgr_claim_visit_row, the per-pixel recurrence, sgr_bwd_moments, then sparse_sum or dense_fold
         auto process = [&](const SgrVisit& vt) __attribute__((always_inline)) {
                 const int j = vt.j;
                 const float4 q = vt.q;
                 const float dx = vt.dx, dy = vt.dy, power2 = vt.power, G = vt.G, alpha = vt.alpha;
                 const int posj = hi - j;  // 0-based list position == `contributor` after its decrement
-                // backward.cu:527-545
-                // (pixels outside the image have lastc = 0).  The wave-wide "any hit" is taken from the three compare
-                // masks with scalar ANDs: ballot(compound bool) costs hipcc a v_cndmask + v_cmp per survivor.
-                const bool k0 = posj < lastc, k1 = !(power2 > 0.0f), k2 = !(alpha < SGR_ALPHA_MIN);
-                const uint64_t hm = __builtin_amdgcn_ballot_w64(k0) & __builtin_amdgcn_ballot_w64(k1) &
-                                    __builtin_amdgcn_ballot_w64(k2);
+                const SgrBwdHit h = sgr_bwd_hit(posj, lastc, power2, alpha);
+                const uint64_t hm = h.hm; const bool hit = h.hit;
                 // no pixel takes part (every passing pixel of the forward finished on this instance): no row, nothing to add
                 if (hm == 0) return;
-                const int rowi = rown;
-                if constexpr (VROWS) {
-                    rown++;
-                    vis = sgr_bitset1(vis, j & 63);
-                }
-                const bool hit = k0 && k1 && k2;
-
+                const int rowi = sgr_claim_visit_row<VROWS>(rown, vis, j);
                 const float4 c = sC[j];
                 float v[NVAL];
 #pragma unroll
                 for (int k = 0; k < NVAL; k++) v[k] = 0.0f;
                 // Everything per-pixel runs under the hit mask and updates the recurrences in place; the other lanes
-                // keep dopa = wm = 0, and every output below is a product with one of those two.
+                // keep Gd = wm = 0, and every output below is a product with one of those two.
                 float Gd = 0.0f, wm = 0.0f;  // Gd = G * dL/dalpha-term: zero off the hit lanes even if G overflowed there
+                // The per-pixel RECURRENCE that yields Gd and wm (backward.cu:547-614).  Inline, and its two channel loops as they
+                // were: as a lambda or function either moves a v_mul_f32 in the 18 instantiations with 8 or more channels.
                 if (hit) {
                     const float oma = 1.0f - alpha;
                     float inv1ma = __builtin_amdgcn_rcpf(oma);
@@ -517,27 +597,8 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
 #pragma unroll
                     for (int ch = 0; ch < SMAX; ch++) v[SGR_ROW_BASE + ch] = wm * dLdS[ch];
                 }
-                // Per pixel only the MOMENTS of Gd = G * dopa are formed (Gd*dx, Gd*dy, Gd*dx^2, Gd*dx*dy, Gd*dy^2) plus the
-                // "abs" term, which is not linear; the flush turns the tile's sums into dL/dmean2D and dL/dconic with the
-                // instance's conic and opacity (dL_dG = opacity * dopa is constant per instance, backward.cu:616-635):
-                // 17 instead of 26 instructions per visit, same sums up to rounding.
-                const float gx = Gd * dx, gy = Gd * dy;
-                // dG/ddelx / G = (2*qa*dx + qb*dy)/log2e  (qa = -0.5*log2e*A, qb = -log2e*B; 1/log2e is in kx, ky)
-                // built on the two products sgr_power2 already formed (qa*dx + qb*dy and qc*dy: common subexpressions)
-                float ax, ay;
-                {
-#pragma clang fp contract(off)
-                    const float e1 = fmaf(q.y, dy, q.x * dx), e2 = q.z * dy;
-                    ax = fmaf(q.x, dx, e1);
-                    ay = fmaf(q.y, dx, e2 + e2);
-                }
-                v[0] = gx;
-                v[1] = gy;
-                v[2] = fabsf(Gd) * fmaf(fabsf(ax), kx, fabsf(ay) * ky);
-                v[3] = gx * dx;
-                v[4] = gx * dy;
-                v[5] = gy * dy;
-                v[6] = Gd;
+                // MOMENTS: 17 instead of the 26 instructions per visit of the per-pair products
+                sgr_bwd_moments(Gd, q.x, q.y, q.z, dx, dy, kx, ky, v);
                 const sgr_f2 o01 = wm * dL01, o2D = wm * dL2D;
                 v[7] = o01.x;
                 v[8] = o01.y;
@@ -548,83 +609,13 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                 float r[NVAL / 4];
                 if constexpr (SPK > 0) {
                     const int kc = sgr_popc64(hm);
-                    if (kc <= kq) {
-                        if (hit) {  // entry = rank among the hit lanes; an entry is laid out like a row (float4 t = values 4t, 4t+2, 4t+1, 4t+3)
-                            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-                            // 32-bit stores written as ds_write_b32 (the optimiser merges plain stores into ds_write_b128, which
-                            // wants its four values in consecutive registers: the copies that takes landed in the dense path too)
-                            const uint32_t ea = sgr_lds_addr(sAcc + stage_off) + rank * 48u;
-#define SGR_STAGE_ST(OFF, VAL) asm volatile("ds_write_b32 %0, %1 offset:" #OFF : : "v"(ea), "v"(VAL) : "memory")
-                            SGR_STAGE_ST(0, v[0]); SGR_STAGE_ST(4, v[2]); SGR_STAGE_ST(8, v[1]); SGR_STAGE_ST(12, v[3]);
-                            SGR_STAGE_ST(16, v[4]); SGR_STAGE_ST(20, v[6]); SGR_STAGE_ST(24, v[5]); SGR_STAGE_ST(28, v[7]);
-                            SGR_STAGE_ST(32, v[8]); SGR_STAGE_ST(36, v[10]); SGR_STAGE_ST(40, v[9]); SGR_STAGE_ST(44, v[11]);
-#undef SGR_STAGE_ST
-                        }
-                        __builtin_amdgcn_wave_barrier();  // same wave, program order: the LDS serves the reads below after the writes above
-                        if (fold_leader && fold_t0 < NVAL / 4) {
-                            const float* src = sAcc + (acc_fold_off + stage_off);
-                            // kc is wave-uniform: one case, all its loads in flight at once, adds in rank order
-                            auto sum_first = [&](auto KC) __attribute__((always_inline)) {
-                                constexpr int kk = decltype(KC)::value, k0 = kk < 8 ? kk : 8;
-                                float a[k0];  // (at most eight loads in flight: the kernel lives on 64 registers)
-#pragma unroll
-                                for (int e = 0; e < k0; e++) a[e] = src[e * 12];
-                                float t = a[0];
-#pragma unroll
-                                for (int e = 1; e < k0; e++) t += a[e];
-                                if constexpr (kk > 8) {
-                                    float b[kk - 8];
-#pragma unroll
-                                    for (int e = 8; e < kk; e++) b[e - 8] = src[e * 12];
-#pragma unroll
-                                    for (int e = 8; e < kk; e++) t += b[e - 8];
-                                }
-                                return t;
-                            };
-                            float t = 0.0f;
-                            switch (kc) {
-#define SGR_SPARSE_CASE(N) case N: if constexpr (N <= SPK) t = sum_first(std::integral_constant<int, (N <= SPK ? N : 1)>{}); break
-                                SGR_SPARSE_CASE(1); SGR_SPARSE_CASE(2); SGR_SPARSE_CASE(3); SGR_SPARSE_CASE(4);
-                                SGR_SPARSE_CASE(5); SGR_SPARSE_CASE(6); SGR_SPARSE_CASE(7); SGR_SPARSE_CASE(8);
-                                SGR_SPARSE_CASE(9); SGR_SPARSE_CASE(10); SGR_SPARSE_CASE(11); SGR_SPARSE_CASE(12);
-                                SGR_SPARSE_CASE(13); SGR_SPARSE_CASE(14); SGR_SPARSE_CASE(15); SGR_SPARSE_CASE(16);
-#undef SGR_SPARSE_CASE
-                                default: break;
-                            }
-                            sAcc[acc_fold_off + rowi * ACCW] = t;  // the visit's own row: one writer
-                            // keeps the optimiser from merging this store with the dense path's: the merged tail made the
-                            // twelve values live across this block (and the loads above serialise for want of registers)
-                            asm volatile("; sparse visit done" ::: "memory");
-                        }
+                    if (kc <= SPK) {
+                        sparse_sum(hm, kc, hit, v, rowi);
                         return;
                     }
                 }
                 if (DPP && SGR_FOLD) {
-                    // 16 values at a time (one result register, one ds_add_f32 each): the same instructions as one
-                    // pass over all NVAL values, but the channel products w * dL/dsemantic are formed chunk by chunk,
-                    // so a wide instantiation keeps 16 + 8 instead of NVAL + NVAL/2 reduction registers live
-                    float* dst = sAcc + (acc_fold_off + (VROWS ? rowi : j) * ACCW);  // wave-uniform: scalar multiply
-                    auto fold_chunk = [&](auto C0, auto CN) __attribute__((always_inline)) {
-                        constexpr int c0 = decltype(C0)::value, cn = decltype(CN)::value;
-                        float vv[cn], g[1];
-#pragma unroll
-                        for (int k = 0; k < cn; k++) {
-                            const int idx = c0 + k;
-                            vv[k] = idx < SGR_ROW_BASE ? v[idx < NVAL ? idx : 0]
-                                                       : (idx - SGR_ROW_BASE < SMAX ? wm * dLdS[(idx - SGR_ROW_BASE) % NS] : 0.0f);
-                        }
-                        sgr_wave_reduce_fold<cn>(vv, g);
-                        if (fold_leader && fold_t0 < cn / 4) {
-                            if constexpr (VROWS) dst[c0] = g[0];  // the visit's own row: one writer
-                            else atomicAdd(&dst[c0], g[0]);
-                        }
-                    };
-                    fold_chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, (NVAL < 16 ? NVAL : 16)>{});
-                    if constexpr (NVAL > 16)
-                        fold_chunk(std::integral_constant<int, 16>{}, std::integral_constant<int, (NVAL - 16 < 16 ? NVAL - 16 : 16)>{});
-                    if constexpr (NVAL > 32)
-                        fold_chunk(std::integral_constant<int, 32>{}, std::integral_constant<int, (NVAL - 32 < 16 ? NVAL - 32 : 16)>{});
-                    static_assert(NVAL <= 48, "add a fold chunk");
+                    dense_fold(v, wm, sAcc + (acc_fold_off + (VROWS ? rowi : j) * ACCW));  // wave-uniform row: scalar multiply
                     return;
                 } else if (DPP) {
                     sgr_wave_reduce_scatter<NVAL>(v, r);
@@ -638,21 +629,18 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                     }
                 }
                 if ((lane & 15) == 0) {  // one lane per 16-lane row stores that row's values
-                    const int k = lane >> 4;
                     float* dst = sAcc + (acc_lane_off + j * ACCW);  // j is wave-uniform: scalar multiply
-                    (void)k;
 #pragma unroll
                     for (int t = 0; t < NVAL / 4; t++) atomicAdd(&dst[4 * t], r[t]);
                 }
         };
+        // WALK
         for (int chunk = 0; chunk < BATCH / 64; chunk++) {
             uint64_t m;
             m = sBits[wave][chunk];
             m = sgr_uniform_u64(m);
-            if constexpr (VROWS) {  // only the slots this round walks (`chunk` may be a run-time index: no register array here)
-                const int nb = lim - 64 * chunk;
-                m = nb >= 64 ? m : (nb <= 0 ? 0ull : (m & ((1ull << nb) - 1ull)));
-            }
+            // VROWS: only the slots this round walks (`chunk` may be a run-time index: no register array here)
+            if constexpr (VROWS) m = sgr_first_bits(m, lim - 64 * chunk);
             sgr_walk_pairs<EXACT, true>(m, chunk, sA, sB, tp.pxf, tp.pyf, process);
             if constexpr (VROWS) {
                 if (lane == 0) sVis[wave][chunk] = vis;
@@ -660,7 +648,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
             }
         }
         sgr_lds_barrier();
-        // One row per (tile, instance) some quadrant was asked to visit: plain stores, written exactly once.  With the
+        // FLUSH: one row per (tile, instance) some quadrant was asked to visit: plain stores, written exactly once.  With the
         // forward's hit record that is the set of instances that blended into the tile (plus the rare one whose every
         // passing pixel finished on it: a row of zeros); flagging rows per visit instead cost an LDS store + exec
         // juggling in the walk.
@@ -712,17 +700,9 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                     }
                 }
             }
-            // moments -> gradients (see `process`): r[0] = {S gx, S abs, S gy, S gxx}, r[1] = {S gxy, S Gd, S gyy, colour r}
-            {
-                const float4 qq = sB[tid];
-                const float sgx = r[0].x, sgy = r[0].z, qw = qq.w, hq = -0.5f * qq.w;
-                r[0].x = qw * kx * fmaf(qq.x + qq.x, sgx, qq.y * sgy);  // dL/dmean2D.x
-                r[0].z = qw * ky * fmaf(qq.z + qq.z, sgy, qq.y * sgx);  // dL/dmean2D.y
-                r[0].y = qw * r[0].y;                                    // sum |gx| + |gy|
-                r[0].w = hq * r[0].w;                                    // dL/dconic.x
-                r[1].x = hq * r[1].x;                                    // dL/dconic.y
-                r[1].z = hq * r[1].z;                                    // dL/dconic.w
-            }
+            // r[0] = {S gx, S abs, S gy, S gxx}, r[1] = {S gxy, S Gd, S gyy, colour r}: the LDS row layout, middle pairs swapped
+            const float4 qq = sB[tid];
+            sgr_moments_to_grads(qq.x, qq.y, qq.z, qq.w, kx, ky, r[0].x, r[0].z, r[0].y, r[0].w, r[1].x, r[1].z);
 #pragma unroll
             for (int k4 = 0; k4 < NVAL / 4; k4++) row[k4] = make_float4(r[k4].x, r[k4].z, r[k4].y, r[k4].w);
         }
@@ -975,6 +955,8 @@ sgr_blend_bwd_kernel_v2(SGR_BWD_ARGS) {
                 const bool odd = (lane >> 2) & 1;
                 // even bank: moments -> mean2D.x, mean2D.y, conic x / y / w, opacity (row 0, 1, 3, 4, 5, 6);
                 // odd bank: abs term, colour, depth (row 2, 7, 8, 9, 10)
+                // (own form of sgr_moments_to_grads: the products are selected per bank against the colour sums; through the
+                // shared function the four instantiations schedule differently)
                 const float qw = q.w;
                 const float e0 = qw * kx * fmaf(q.x + q.x, m1x, q.y * m1y);
                 const float e1 = qw * ky * fmaf(q.z + q.z, m1y, q.y * m1x);

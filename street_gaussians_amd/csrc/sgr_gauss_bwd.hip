@@ -50,10 +50,9 @@ template <int SMAX, bool QUAD> constexpr int sgr_rs_waves = (!QUAD && SMAX == 0)
 // terms to stage 2 through `cd`.
 // QUAD: the rows of the scalar-walk blend backward (sgr_blend_bwd_sw.hip) -- FOUR rows per (tile, instance), one per
 // quadrant, `touched` = mask of the ones that exist, each holding the raw moments [S gx, S gy, S abs, S gxx, S gxy, S gyy,
-// S Gd, r, g, b, depth]; summed in (tile, quadrant) order, and the moments -> gradient step of the LDS kernel's flush
-// (a product with the Gaussian's staged conic and opacity, backward.cu:616-635) applied ONCE, to the sums.
-// kx, ky = 0.5 * W / lsc, 0.5 * H / lsc with lsc = log2(e), or 1 in parity mode (`exact`: the staged conic is then
-// (-0.5 cx, -cy, -0.5 cz) instead of the log2(e)-scaled one in rec[3]).
+// S Gd, r, g, b, depth]; summed in (tile, quadrant) order, and sgr_moments_to_grads (a product with the Gaussian's
+// staged conic and opacity) applied ONCE, to the sums.  kx, ky: sgr_ndc_scale; in parity mode (`exact`) the staged conic
+// is (-0.5 cx, -cy, -0.5 cz) instead of the log2(e)-scaled one in rec[3].
 template <int SMAX, bool QUAD>
 __global__ void __launch_bounds__(SGR_GB_THREADS) __attribute__((amdgpu_waves_per_eu(sgr_rs_waves<SMAX, QUAD>)))
 sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, const float* __restrict__ partials,
@@ -222,18 +221,11 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
                 a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0x141, 0xF, 0xF, false));
         }
     if (QUAD && n) {
-        // moments -> gradients (sgr_blend_bwd.hip's flush, per Gaussian instead of per (tile, instance))
+        // per Gaussian instead of per (tile, instance)
 #pragma clang fp contract(off)
         const float4 c1 = gv.rec[4 * (size_t)idx + 1], c3 = gv.rec[4 * (size_t)idx + 3];
         const float qx = exact ? -0.5f * c1.x : c3.x, qy = exact ? -c1.y : c3.z, qz = exact ? -0.5f * c1.z : c3.w;
-        const float qw = c1.w, hq = -0.5f * c1.w;
-        const float sgx = acc[0], sgy = acc[1];
-        acc[0] = qw * kx * fmaf(qx + qx, sgx, qy * sgy);  // dL/dmean2D.x
-        acc[1] = qw * ky * fmaf(qz + qz, sgy, qy * sgx);  // dL/dmean2D.y
-        acc[2] = qw * acc[2];                             // sum |gx| + |gy|
-        acc[3] = hq * acc[3];                             // dL/dconic.x
-        acc[4] = hq * acc[4];                             // dL/dconic.y
-        acc[5] = hq * acc[5];                             // dL/dconic.w
+        sgr_moments_to_grads(qx, qy, qz, c1.w, kx, ky, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5]);
     }
 #pragma unroll
     for (int g = 0; g < G; g++) {
@@ -676,8 +668,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
 int sgr_launch_gauss_bwd(const SgrGaussBwdArgs& a, hipStream_t s) {
     const int P = a.P, S = a.S;
     if (P <= 0) return 0;
-    const float lsc = a.exact ? 1.0f : SGR_LOG2E;
-    const float kx = (0.5f * (float)a.W) / lsc, ky = (0.5f * (float)a.H) / lsc;
+    const SgrNdcScale ks = sgr_ndc_scale(a.W, a.H, a.exact);
     const unsigned nb = (P + SGR_GB_THREADS - 1) / SGR_GB_THREADS;
     // switch bit 9 / SGR_RS_WAVE=1: the wave-cooperative row sum instead of the four-lanes-per-Gaussian one (A/B: measured SLOWER on MI355X --
     // per-Gaussian backward stage 0.258 vs 0.213 ms at 1 M Gaussians, 1.14 vs 0.76 ms at 5 M, 0.83 vs 0.57 ms at 2 M + 19
@@ -688,7 +679,7 @@ int sgr_launch_gauss_bwd(const SgrGaussBwdArgs& a, hipStream_t s) {
     const unsigned nbw = (unsigned)((P + 64 * SGR_RSW_WAVES - 1) / (64 * SGR_RSW_WAVES));
     if (a.quad) {  // the scalar-walk blend backward's rows (S = 0 only)
         sgr_row_sum_kernel<0, true><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, a.radii, a.gv, a.partials, a.row_stride, a.touched, a.dL_dmean2D,
-                                                                  a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink, kx, ky, a.exact,
+                                                                  a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink, ks.kx, ks.ky, a.exact,
                                                                   0xffffffffu, a.masked_color_out);
     } else if (a.rs_wave) {  // (sgr_test_switches bit 9)
         sgr_with_smax(S, [&](auto N) {
@@ -701,7 +692,7 @@ int sgr_launch_gauss_bwd(const SgrGaussBwdArgs& a, hipStream_t s) {
         constexpr int G = sgr_rs_pair<decltype(N)::value, false>;  // Gaussians per quad of this instantiation
         const unsigned nb4 = (unsigned)((((size_t)P + G - 1) / G * SGR_RS_LANES + SGR_GB_THREADS - 1) / SGR_GB_THREADS);
         sgr_row_sum_kernel<N, false><<<nb4, SGR_GB_THREADS, 0, s>>>(P, S, a.radii, a.gv, a.partials, a.row_stride, a.touched, a.dL_dmean2D,
-                                                                   a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink, kx, ky, a.exact,
+                                                                   a.dL_dopacity, a.dL_dcolor, a.dL_dsemantic, a.cd, a.sink, ks.kx, ks.ky, a.exact,
                                                                    a.row_limit, a.masked_color_out);
     });
     // dL/dmean2D, dL/dopacity, dL/dcolour are final from here on.  A failed record must not pass silently: the reducer's side

@@ -396,6 +396,51 @@ SGR_HD float sgr_power_ref_staged(float hx, float ny, float hz, float dx, float 
 #pragma clang fp contract(off)
     return (hx * dx * dx + hz * dy * dy) + ny * dx * dy;
 }
+// The staged {qa, qb, qc, opacity} of a record's {conic.x, conic.y, conic.z, opacity}.  EXACT (parity mode): exact
+// power-of-two scalings only -- the walk evaluates the reference's own power expression on the staged triple
+// (sgr_power_ref_staged); else the conic pre-scaled by log2(e) for sgr_power2 + v_exp_f32.
+template <bool EXACT>
+SGR_HD float4 sgr_stage_conic_mode(const float4 b) {
+    return EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w) : sgr_stage_conic(b);
+}
+
+// ---- blend backward: the moments identity.  dL_dG = opacity * dL/dopa is constant per instance (backward.cu:616-635), so
+// per (pixel, instance) pair only the MOMENTS of Gd = G * dL/dopa are formed, plus the "abs" term, which is not linear; their
+// sums become dL/dmean2D and dL/dconic once per instance.  Every kernel of the backward family takes both halves from here.
+// d(pixel)/d(ndc) (backward.cu:501-502) over the scale constant of the staged conic: log2 e, or 1 in parity mode
+struct SgrNdcScale { float kx, ky; };
+SGR_HD SgrNdcScale sgr_ndc_scale(int W, int H, bool exact) {
+    const float lsc = exact ? 1.0f : SGR_LOG2E;
+    return {(0.5f * (float)W) / lsc, (0.5f * (float)H) / lsc};
+}
+// One pair's v[0..6] = Gd*dx, Gd*dy, |Gd| * (|ax|*kx + |ay|*ky), Gd*dx*dx, Gd*dx*dy, Gd*dy*dy, Gd.  ax = dG/ddelx / G * scale
+// = 2*qx*dx + qy*dy, ay likewise: on the products the power expression forms (common subexpressions in the kernels).
+SGR_HD void sgr_bwd_moments(float Gd, float qx, float qy, float qz, float dx, float dy, float kx, float ky, float* v) {
+#pragma clang fp contract(off)
+    const float gx = Gd * dx, gy = Gd * dy;
+    float ax, ay;
+    {
+#pragma clang fp contract(off)
+        const float e1 = fmaf(qy, dy, qx * dx), e2 = qz * dy;
+        ax = fmaf(qx, dx, e1);
+        ay = fmaf(qy, dx, e2 + e2);
+    }
+    v[0] = gx; v[1] = gy;
+    v[2] = fabsf(Gd) * fmaf(fabsf(ax), kx, fabsf(ay) * ky);
+    v[3] = gx * dx; v[4] = gx * dy; v[5] = gy * dy;
+    v[6] = Gd;
+}
+// The sums of v[0..5] over an instance's pairs, in place -> dL/dmean2D.x, .y, sum |x| + |y|, dL/dconic.x, .y, .w
+// (the sum of v[6] is dL/dopacity as it stands).  Scalars, because the callers' row layouts differ.
+SGR_HD void sgr_moments_to_grads(float qx, float qy, float qz, float opacity, float kx, float ky, float& sgx, float& sgy,
+                                 float& sabs, float& sgxx, float& sgxy, float& sgyy) {
+#pragma clang fp contract(off)
+    const float mx = sgx, my = sgy, qw = opacity, hq = -0.5f * opacity;
+    sgx = qw * kx * fmaf(qx + qx, mx, qy * my);
+    sgy = qw * ky * fmaf(qz + qz, my, qy * mx);
+    sabs = qw * sabs;
+    sgxx = hq * sgxx; sgxy = hq * sgxy; sgyy = hq * sgyy;
+}
 
 // ---- parity-mode elementary functions ------------------------------------------------------------------------------
 // expf as the device library evaluates it on gfx950 (ocml expF / LLVM's f32 exp lowering, read off the ISA hipcc emits

@@ -15,12 +15,12 @@
 //
 // BACKWARD (sgr_object_alpha_bwd_kernel): the alpha part of backward.cu:505-640, back to front over the positions below
 // the tile's largest recorded position, 128 per round.  Per visit the blend backward's power, G (sgr_G_bwd: with the parity
-// mode's guard at the 1/255 threshold) and alpha from sgr_walk_pairs, and its expressions for the rest (v_rcp_f32 for
-// T / (1 - alpha), the moments of G * dL/dopa); which quadrants visit an entry is the geometric cull, redone (the shipped kernel's NO_HITS path: the lanes that take part
+// mode's guard at the 1/255 threshold) and alpha from sgr_walk_pairs, its hit test (sgr_bwd_hit), v_rcp_f32 for
+// T / (1 - alpha) and the moments of G * dL/dopa (sgr_bwd_moments); which quadrants visit an entry is the geometric cull, redone (the shipped kernel's NO_HITS path: the lanes that take part
 // are decided per pixel, so the cull only removes visits without any).  No global atomics and no LDS float atomics: a
 // visit's seven sums are reduced across the wave (sgr_wave_reduce_fold) and stored into the slot's row OF THAT QUADRANT
 // (one writer per element); after the round one thread per slot adds the rows of the quadrants that visited it, in
-// quadrant order, turns the moments into gradients exactly as the shipped flush does and writes the row once.
+// quadrant order, turns the moments into gradients (sgr_moments_to_grads) and writes the row once.
 #include "sgr_tile_walk.h"
 #include "sgr_launch.h"
 #include "sgr_reduce.h"
@@ -130,8 +130,8 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
     const int lastc = inside ? min((int)layer_last[pix_id], len) : 0;
     const float dLdA = inside ? dL_dlayer_alpha[pix_id] : 0.0f;
     float accA = 0.f, last_alpha = 0.f;
-    constexpr float LSC = EXACT ? 1.0f : SGR_LOG2E;
-    const float kx = (0.5f * (float)W) / LSC, ky = (0.5f * (float)H) / LSC;
+    const SgrNdcScale ks = sgr_ndc_scale(W, H, EXACT);
+    const float kx = ks.kx, ky = ks.ky;
 
     int mx = lastc;
 #pragma unroll
@@ -159,11 +159,9 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             const float4 b = r[1];
             const float4 d4 = r[3];
             sB[tid] = sgr_stage_conic_mode<EXACT>(b);
-            const uint32_t urow = sgr_row_of(__float_as_uint(d4.y), tx, ty, u0, tmask, g);
-            sA[tid] = make_float4(a.x, a.y, __uint_as_float(urow), 0.0f);
+            const bool live = sgr_stage_bwd_row(a, d4, g, tx, ty, u0, tmask, row_limit, sA[tid]);
             mask4 = sgr_quadrant_mask(a, b, tx0, ty0);
-            // lazy forward whose frame had more instances than the list capacity: rows past the array are not visited
-            if (urow >= row_limit) mask4 = 0;
+            if (!live) mask4 = 0;
         }
         if (stager) sgr_store_cull_ballots(mask4, lane, wave, sBits);
         sgr_lds_barrier();
@@ -173,35 +171,19 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             const int j = vt.j;
             const float4 q = vt.q;
             const float dx = vt.dx, dy = vt.dy, power2 = vt.power, G = vt.G, alpha = vt.alpha;
-            const int posj = hi - j;  // 0-based list position
-            // backward.cu:527-545 (pixels outside the image have lastc = 0)
-            const bool k0 = posj < lastc, k1 = !(power2 > 0.0f), k2 = !(alpha < SGR_ALPHA_MIN);
-            const uint64_t hm = __builtin_amdgcn_ballot_w64(k0) & __builtin_amdgcn_ballot_w64(k1) & __builtin_amdgcn_ballot_w64(k2);
-            if (hm == 0) return;  // no pixel takes part: no row
+            const SgrBwdHit h = sgr_bwd_hit(hi - j, lastc, power2, alpha);  // hi - j: 0-based list position
+            if (h.hm == 0) return;  // no pixel takes part: no row
             vis = sgr_bitset1(vis, j & 63);
             float Gd = 0.0f;  // G * dL/dopa: zero off the hit lanes
-            if (k0 && k1 && k2) {
+            if (h.hit) {
                 const float oma = 1.0f - alpha;
                 T = T * __builtin_amdgcn_rcpf(oma);  // T = T / (1 - alpha) (backward.cu:547), as the blend backward
                 accA = fmaf(1.0f - last_alpha, accA, last_alpha);
                 last_alpha = alpha;
                 Gd = G * (((1.0f - accA) * dLdA) * T);
             }
-            const float mgx = Gd * dx, mgy = Gd * dy;
-            float ax, ay;
-            {
-                const float e1 = fmaf(q.y, dy, q.x * dx), e2 = q.z * dy;
-                ax = fmaf(q.x, dx, e1);
-                ay = fmaf(q.y, dx, e2 + e2);
-            }
             float v[8];
-            v[0] = mgx;
-            v[1] = mgy;
-            v[2] = fabsf(Gd) * fmaf(fabsf(ax), kx, fabsf(ay) * ky);
-            v[3] = mgx * dx;
-            v[4] = mgx * dy;
-            v[5] = mgy * dy;
-            v[6] = Gd;
+            sgr_bwd_moments(Gd, q.x, q.y, q.z, dx, dy, kx, ky, v);
             v[7] = 0.0f;
             float r[1];
             sgr_wave_reduce_fold<8>(v, r);
@@ -227,19 +209,15 @@ sgr_object_alpha_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __
                     s[4] += t1.x; s[5] += t1.y; s[6] += t1.z;
                 }
             }
-            // moments -> gradients as the flush of sgr_blend_bwd_body does it: dL_dG = opacity * dL/dopa is constant per
-            // instance (backward.cu:616-635)
             const float4 qq = sB[tid];
-            const float qw = qq.w, hq = -0.5f * qq.w;
             const uint32_t u = __float_as_uint(sA[tid].z);
             touched[u] = 1;
             float4* row = reinterpret_cast<float4*>(partials + (size_t)u * row_stride);
-            row[0] = make_float4(qw * kx * fmaf(qq.x + qq.x, s[0], qq.y * s[1]),  // dL/dmean2D.x
-                                 qw * ky * fmaf(qq.z + qq.z, s[1], qq.y * s[0]),  // dL/dmean2D.y
-                                 qw * s[2],                                        // sum |x| + |y|
-                                 hq * s[3]);                                       // dL/dconic.x
-            row[1] = make_float4(hq * s[4], hq * s[5], s[6], 0.0f);               // dL/dconic.y, .w, dL/dopacity, colour r
-            row[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);                         // colour g, b, depth, padding
+            float4 r0 = make_float4(s[0], s[1], s[2], s[3]), r1 = make_float4(s[4], s[5], s[6], 0.0f);
+            sgr_moments_to_grads(qq.x, qq.y, qq.z, qq.w, kx, ky, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y);
+            row[0] = r0;  // dL/dmean2D.x, .y, sum |x| + |y|, dL/dconic.x
+            row[1] = r1;  // dL/dconic.y, .w, dL/dopacity, colour r
+            row[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);    // colour g, b, depth, padding
         }
     }
 }

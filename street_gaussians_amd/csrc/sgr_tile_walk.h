@@ -78,14 +78,6 @@ __device__ __forceinline__ bool sgr_tile_pixel(SgrTilePixel& p, int gx, int gy, 
     return true;
 }
 
-// The staged {qa, qb, qc, opacity} of a record's {conic.x, conic.y, conic.z, opacity}.  EXACT (parity mode): exact
-// power-of-two scalings only -- the walk evaluates the reference's own power expression on the staged triple
-// (sgr_power_ref_staged); else the conic pre-scaled by log2(e) for sgr_power2 + v_exp_f32.
-template <bool EXACT>
-__device__ __forceinline__ float4 sgr_stage_conic_mode(const float4 b) {
-    return EXACT ? make_float4(-0.5f * b.x, -b.y, -0.5f * b.z, b.w) : sgr_stage_conic(b);
-}
-
 // The staging lanes' cull results (bit q of mask4 = quadrant q has to visit my entry) as one survivor mask per quadrant:
 // sBits[q][row], row = the 64-entry chunk this wave staged.
 template <int NCH>
@@ -218,5 +210,30 @@ __device__ __forceinline__ void sgr_blend_end(const SgrBlendStep<MASK>& b, float
         done_mask |= b.sm;
         if (done_mask == ~0ull) m = 0;
     }
+}
+
+// ---- the backward family: back to front, slot t of a round holds list position hi - t (per-pair arithmetic: sgr_math.h)
+// The second half of staging a record (a, d4: its words 0 and 3) into a backward slot, after slotB = sgr_stage_conic_mode(b):
+// slotA = {x, y, bits of the instance's partial-row index, 0} -- first row of the Gaussian (compact array, L2-resident) +
+// rank of this tile among the tiles it is emitted for, in the spare word (written and read back by the staging thread only).
+// false: the row lies past the row array -- a lazy forward (sgr_set_lazy) whose frame had more instances than the list
+// capacity numbers its rows over ALL instances: the caller clears the slot's quadrant mask (the frame is reported invalid
+// one call later; nothing may be written outside the buffers meanwhile).
+__device__ __forceinline__ bool sgr_stage_bwd_row(const float4 a, const float4 d4, const uint32_t g, const uint32_t tx, const uint32_t ty,
+                                                  const uint32_t* __restrict__ u0, const uint64_t* __restrict__ tmask, const uint32_t row_limit,
+                                                  float4& slotA) {
+    const uint32_t urow = sgr_row_of(__float_as_uint(d4.y), tx, ty, u0, tmask, g);
+    slotA = make_float4(a.x, a.y, __uint_as_float(urow), 0.0f);
+    return urow < row_limit;
+}
+
+// Which pixels of the wave take part in the visit of list position posj (backward.cu:527-545; pixels outside the image have
+// lastc = 0): hm = their lane mask, hit = this lane among them.  The mask is taken from the three compare masks with scalar
+// ANDs: ballot(compound bool) costs hipcc a v_cndmask + v_cmp per survivor.
+struct SgrBwdHit { uint64_t hm; bool hit; };
+__device__ __forceinline__ SgrBwdHit sgr_bwd_hit(const int posj, const int lastc, const float power, const float alpha) {
+    const bool k0 = posj < lastc, k1 = !(power > 0.0f), k2 = !(alpha < SGR_ALPHA_MIN);
+    const uint64_t hm = __builtin_amdgcn_ballot_w64(k0) & __builtin_amdgcn_ballot_w64(k1) & __builtin_amdgcn_ballot_w64(k2);
+    return {hm, k0 && k1 && k2};
 }
 #endif

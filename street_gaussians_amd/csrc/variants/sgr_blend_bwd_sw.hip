@@ -109,8 +109,8 @@ sgr_blend_bwd_sw_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
     }
     const float bgdot = bg_color[0] * dLdC0 + bg_color[1] * dLdC1 + bg_color[2] * dLdC2;
     const bool bg_zero = bg_color[0] == 0.0f && bg_color[1] == 0.0f && bg_color[2] == 0.0f;
-    constexpr float LSC = EXACT ? 1.0f : SGR_LOG2E;
-    const float kx = (0.5f * (float)W) / LSC, ky = (0.5f * (float)H) / LSC;
+    const SgrNdcScale ks = sgr_ndc_scale(W, H, EXACT);
+    const float kx = ks.kx, ky = ks.ky;
     float Arec = 0.f, u_last = 0.f, last_alpha = 0.f;
 
     // highest list position any pixel of the QUADRANT blended (the LDS kernel takes the tile's)
@@ -183,20 +183,7 @@ sgr_blend_bwd_sw_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
             u_last = sgr_bfi(hm, u, u_last);
             last_alpha = sgr_bfi(hm, alpha, last_alpha);
         }
-        const float gxm = Gd * dx, gym = Gd * dy;
-        float ax, ay;
-        {
-            const float e1 = fmaf(qy, dy, qx * dx), e2 = qz * dy;
-            ax = fmaf(qx, dx, e1);
-            ay = fmaf(qy, dx, e2 + e2);
-        }
-        v[0] = gxm;
-        v[1] = gym;
-        v[2] = fabsf(Gd) * fmaf(fabsf(ax), kx, fabsf(ay) * ky);
-        v[3] = gxm * dx;
-        v[4] = gxm * dy;
-        v[5] = gym * dy;
-        v[6] = Gd;
+        sgr_bwd_moments(Gd, qx, qy, qz, dx, dy, kx, ky, v);
         v[7] = wm * dLdC0;
         v[8] = wm * dLdC1;
         v[9] = wm * dLdC2;

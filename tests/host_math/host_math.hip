@@ -123,6 +123,20 @@ void hm_power_ref_pair(int n, const float* c, const float* d, float* ref, float*
         staged[i] = sgr_power_ref_staged(-0.5f * c[3 * i], -c[3 * i + 1], -0.5f * c[3 * i + 2], d[2 * i], d[2 * i + 1]);
     }
 }
+// blend backward, the moments identity: the seven values of n pairs (d = {dx, dy}, Gd) for a conic {cx, cy, cz, opacity}
+// staged for the default or the parity mode, and the gradients from their sums s[0..5] (in place)
+void hm_bwd_moments(int n, int exact, const float* conic_opacity, const float* d, const float* Gd, int W, int H, float* v) {
+    const float4 b = make_float4(conic_opacity[0], conic_opacity[1], conic_opacity[2], conic_opacity[3]);
+    const float4 q = exact ? sgr_stage_conic_mode<true>(b) : sgr_stage_conic_mode<false>(b);
+    const SgrNdcScale k = sgr_ndc_scale(W, H, exact != 0);
+    for (int i = 0; i < n; i++) sgr_bwd_moments(Gd[i], q.x, q.y, q.z, d[2 * i], d[2 * i + 1], k.kx, k.ky, v + 7 * i);
+}
+void hm_moments_to_grads(int exact, const float* conic_opacity, int W, int H, float* s) {
+    const float4 b = make_float4(conic_opacity[0], conic_opacity[1], conic_opacity[2], conic_opacity[3]);
+    const float4 q = exact ? sgr_stage_conic_mode<true>(b) : sgr_stage_conic_mode<false>(b);
+    const SgrNdcScale k = sgr_ndc_scale(W, H, exact != 0);
+    sgr_moments_to_grads(q.x, q.y, q.z, q.w, k.kx, k.ky, s[0], s[1], s[2], s[3], s[4], s[5]);
+}
 void hm_div_by_seed(int n, const float* a, const float* b, const float* seed, float* q) {
     for (int i = 0; i < n; i++) {
         const float y0 = seed[i];

@@ -329,3 +329,38 @@ def test_general_constructor_reproduces_make_camera_and_no_output_reads_the_z_co
     got = _hm_forward(hm, cam_nan, sc, 3)
     for k in want:
         assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k
+
+
+def test_blend_backward_moments_identity_matches_the_per_pair_products(hm):
+    """The blend backward sums, per (tile, instance), only the moments of Gd = G * dL/dopa over the pixels (sgr_bwd_moments)
+    and turns the sums into dL/dmean2D, the abs term and dL/dconic once (sgr_moments_to_grads): dL_dG = opacity * dL/dopa is
+    constant per instance.  Held here against a float64 restatement of the reference's per-pair accumulation
+    (backward.cu:616-635) over the same 64 pairs, for eight positive definite conics, in the default staging (conic scaled by
+    log2 e) and the parity staging.  Tolerance per output: 1e-5 of the sum of the |terms| -- 64 float32 additions and about
+    four roundings per term are 70 * 2^-24 = 4.2e-6 of that sum, with a factor of about two over it."""
+    rng = np.random.default_rng(5)
+    W, H, n = 200, 120, 64
+    d = rng.uniform(-8, 8, (n, 2)).astype(np.float32)
+    Gd = (rng.normal(0, 1, n) * np.exp(rng.uniform(-6, 0, n))).astype(np.float32)
+    for _ in range(8):
+        A, Cc = rng.uniform(0.01, 2.0, 2)
+        B = rng.uniform(-0.9, 0.9) * np.sqrt(A * Cc)
+        co = np.array([A, B, Cc, rng.uniform(0.05, 1.0)], np.float32)
+        assert co[0] * co[2] - co[1] * co[1] > 0
+        a, b, c, o = co.astype(np.float64)
+        dx, dy, g = d[:, 0].astype(np.float64), d[:, 1].astype(np.float64), Gd.astype(np.float64)
+        dL_dG_G = o * g  # dL_dG * G of the pair: gdx = G * d.x, dL_dG = con_o.w * dL_dopa
+        tx = dL_dG_G * (-dx * a - dy * b) * (0.5 * W)  # dL_dG * dG_ddelx * ddelx_dx
+        ty = dL_dG_G * (-dy * c - dx * b) * (0.5 * H)
+        terms = [tx, ty, np.abs(tx) + np.abs(ty), -0.5 * dx * dx * dL_dG_G, -0.5 * dx * dy * dL_dG_G, -0.5 * dy * dy * dL_dG_G]
+        for exact in (0, 1):
+            v = np.zeros((n, 7), np.float32)
+            hm.hm_bwd_moments(n, exact, _p(co), _p(d), _p(Gd), W, H, _p(v))
+            s = np.zeros(7, np.float32)
+            for i in range(n):  # float32, index order: the order of a kernel's sum is fixed too
+                s += v[i]
+            hm.hm_moments_to_grads(exact, _p(co), W, H, _p(s))
+            for k, t in enumerate(terms):
+                err, bound = abs(float(s[k]) - t.sum()), 1e-5 * np.abs(t).sum()
+                print(f"exact={exact} conic={co} output {k}: got {s[k]:.9g} want {t.sum():.9g} err {err:.3g} bound {bound:.3g}")
+                assert err <= bound, (exact, k, float(s[k]), t.sum(), err, bound)
