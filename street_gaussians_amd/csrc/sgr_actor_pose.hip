@@ -15,6 +15,7 @@
 #include "sgr_common.h"
 
 #pragma clang fp contract(off)
+#include "sgr_quat.h"  // below the pragma: its helpers take this file's state, so f<> and f<true> are the same here
 
 static constexpr int SGR_AP_THREADS = 256;
 static constexpr int SGR_AP_MAX_BLOCKS = 1024;
@@ -24,24 +25,6 @@ static_assert(sizeof(sgr_actor_pose_sample) == 32 && sizeof(sgr_actor_pose_recor
 static_assert(SGR_ACTOR_POSE_CONTRIB == 16 && SGR_ACTOR_POSE_PARTS == 23, "include/sgr_actor_pose.h");
 
 namespace {
-
-struct Q4 {
-    float w, x, y, z;
-};
-
-__device__ __forceinline__ Q4 qmul(const Q4 a, const Q4 b) {
-    Q4 o;
-    o.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    o.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    o.y = a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x;
-    o.z = a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w;
-    return o;
-}
-
-__device__ __forceinline__ Q4 qconj(const Q4 a) { return Q4{a.w, -a.x, -a.y, -a.z}; }
-__device__ __forceinline__ Q4 qadd(const Q4 a, const Q4 b) { return Q4{a.w + b.w, a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ float qdot(const Q4 a, const Q4 b) { return a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ Q4 qload(const float* p) { return Q4{p[0], p[1], p[2], p[3]}; }
 
 __device__ __forceinline__ Q4 mul_theta(const Q4 a, const float c, const float s) {
     return Q4{a.w * c - a.z * s, a.x * c + a.y * s, a.y * c - a.x * s, a.z * c + a.w * s};
@@ -62,15 +45,10 @@ struct Slerp {  // what the backward needs of one slerp
     float m, c2;
 };
 
-__device__ __forceinline__ Q4 normalize(const Q4 q, float& n) {
-    n = fmaxf(sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z), 1e-12f);
-    return Q4{q.w / n, q.x / n, q.y / n, q.z / n};
-}
-
 __device__ Q4 slerp_fwd(const Q4 q0, const Q4 q1, const float r, Slerp& S) {
     S.r = r;
-    S.a = normalize(q0, S.n0);
-    S.b = normalize(q1, S.n1);
+    S.a = qnormalize(q0, S.n0);
+    S.b = qnormalize(q1, S.n1);
     Q4 p = qmul(qconj(S.a), S.b);
     S.sg = p.w < 0.f ? -1.f : 1.f;
     p = Q4{p.w * S.sg, p.x * S.sg, p.y * S.sg, p.z * S.sg};
@@ -87,13 +65,6 @@ __device__ Q4 slerp_fwd(const Q4 q0, const Q4 q1, const float r, Slerp& S) {
     S.c2 = S.m < 1e-3f ? 0.5f - S.m * S.m / 48.f : sinf(hm) / S.m;
     const Q4 e{cosf(hm), S.v[0] * S.c2, S.v[1] * S.c2, S.v[2] * S.c2};
     return qmul(S.a, e);
-}
-
-// d normalize: g on the normalised quaternion a = q / n -> g on q
-__device__ __forceinline__ Q4 normalize_bwd(const Q4 a, const float n, const Q4 g) {
-    if (n <= 1e-12f) return Q4{g.w / n, g.x / n, g.y / n, g.z / n};  // the clamp_min holds: a = q / 1e-12
-    const float d = qdot(a, g);
-    return Q4{(g.w - a.w * d) / n, (g.x - a.x * d) / n, (g.y - a.y * d) / n, (g.z - a.z * d) / n};
 }
 
 __device__ void slerp_bwd(const Slerp& S, const Q4 gQ, Q4& g0, Q4& g1) {
@@ -131,8 +102,9 @@ __device__ void slerp_bwd(const Slerp& S, const Q4 gQ, Q4& g0, Q4& g1) {
     // p = conj(a) (x) b
     ga = qadd(ga, qconj(qmul(gp, qconj(S.b))));
     const Q4 gb = qmul(S.a, gp);
-    g0 = normalize_bwd(S.a, S.n0, ga);
-    g1 = normalize_bwd(S.b, S.n1, gb);
+    // the Slerp keeps only the clamped norms: n <= eps is "the clamp_min holds, a = q / 1e-12"
+    g0 = qnormalize_bwd(S.a, S.n0, ga, S.n0 <= SGR_Q_EPS);
+    g1 = qnormalize_bwd(S.b, S.n1, gb, S.n1 <= SGR_Q_EPS);
 }
 
 __device__ __forceinline__ bool cell_ok(const int c, const int n_cells) { return c >= 0 && c < n_cells; }

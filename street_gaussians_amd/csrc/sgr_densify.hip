@@ -15,6 +15,7 @@
 #include <string>
 
 #include "sgr_densify_rules.h"  // the work area and the two per-row decisions, shared with sgr_densify_scene.hip
+#include "sgr_quat.h"
 
 __global__ void __launch_bounds__(256)
 sgr_densify_flags_kernel(int N, sgr_densify_params p, const float* __restrict__ accum, const float* __restrict__ denom,
@@ -98,17 +99,13 @@ sgr_densify_children_kernel(int n_out, int n_split, const int32_t* __restrict__ 
     const size_t i = (size_t)src[o], z = (size_t)sample_row[o];
     const float s[3] = {expf(scaling[3 * i]), expf(scaling[3 * i + 1]), expf(scaling[3 * i + 2])};
     const float v[3] = {normals[3 * z] * s[0], normals[3 * z + 1] * s[1], normals[3 * z + 2] * s[2]};  // normal(0, std)
-    // quaternion_to_matrix(self._rotation[sel]) (general_utils.py:125-146): raw quaternion divided by its norm
-    float qw = rotation[4 * i], qx = rotation[4 * i + 1], qy = rotation[4 * i + 2], qz = rotation[4 * i + 3];
-    const float nrm = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= nrm; qx /= nrm; qy /= nrm; qz /= nrm;
-    const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qw * qz), 2.f * (qx * qz + qw * qy),
-                        2.f * (qx * qy + qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qw * qx),
-                        2.f * (qx * qz - qw * qy), 2.f * (qy * qz + qw * qx), 1.f - 2.f * (qx * qx + qy * qy)};
+    float R[9], nrm;
+    Q4 qn;
+    qtomat(qload(rotation + 4 * i), R, qn, nrm);  // quaternion_to_matrix(self._rotation[sel])
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        xyz_out[3 * (size_t)o + a] = R[3 * a] * v[0] + R[3 * a + 1] * v[1] + R[3 * a + 2] * v[2] + xyz[3 * i + a];  // :471
-        scaling_out[3 * (size_t)o + a] = logf(s[a] / (0.8f * (float)n_split));                                          // :472
+        xyz_out[3 * (size_t)o + a] = rot_row(R + 3 * a, v, xyz[3 * i + a]);      // :471
+        scaling_out[3 * (size_t)o + a] = logf(s[a] / (0.8f * (float)n_split));  // :472
     }
 }
 
@@ -160,7 +157,7 @@ sgr_reset_opacity_kernel(int N, float* __restrict__ opacity, float* __restrict__
 #pragma clang fp contract(off)
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));   // get_opacity
+    const float op = sigmoidf_(opacity[i]);                // get_opacity
     const float x = fminf(op, 0.01f);                      // torch.min(opacity, 0.01)
     opacity[i] = logf(x / (1.0f - x));                     // inverse_sigmoid (general_utils.py:28-29)
     if (exp_avg) exp_avg[i] = 0.0f;

@@ -8,6 +8,7 @@
 
 #include "../../include/sgr_densify.h"
 #include "sgr_common.h"
+#include "sgr_quat.h"
 
 struct DnWork {
     uint32_t *flags, *offA, *offB, *offS, *offC, *tmp, *totals;  // totals: nA nB nS nC nClone nPrunedCand
@@ -49,7 +50,7 @@ __device__ __forceinline__ uint32_t dn_decide_flags(const sgr_densify_params& p,
     const float dense = p.percent_dense * p.extent;
     const bool clone = (fabsf(g) >= p.max_grad) && (smax <= dense);  // :497-499 (norm of a 1-vector)
     const bool split = (g >= p.max_grad) && (smax > dense);          // :462-464
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));
+    const float op = sigmoidf_(opacity[i]);
     const bool low = op < p.min_opacity;                              // :533
     const float big = p.extent * p.percent_big_ws;
     const bool prune_self = !p.defer_prune && (low || (p.prune_big && smax > big));  // :536-540
@@ -106,7 +107,7 @@ __device__ __forceinline__ uint32_t dn_decide_prune(const sgr_densify_params& p,
                                                     const float* __restrict__ zn, size_t i) {
 #pragma clang fp contract(off)
     bool big = false, outside = false;
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));
+    const float op = sigmoidf_(opacity[i]);
     const bool low = op < p.min_opacity;
     const float s[3] = {expf(scaling[3 * i]), expf(scaling[3 * i + 1]), expf(scaling[3 * i + 2])};
     const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
@@ -118,19 +119,16 @@ __device__ __forceinline__ uint32_t dn_decide_prune(const sgr_densify_params& p,
             if (dist > 2.0f * sph.r) big = false;
         }
         if (variant == SGR_PRUNE_ACTOR) {  // gaussian_model_actor.py:231-249
-            float qw = rotation[4 * i], qx = rotation[4 * i + 1], qy = rotation[4 * i + 2], qz = rotation[4 * i + 3];
-            const float nrm = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-            qw /= nrm; qx /= nrm; qy /= nrm; qz /= nrm;
-            const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qw * qz), 2.f * (qx * qz + qw * qy),
-                                2.f * (qx * qy + qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qw * qx),
-                                2.f * (qx * qz - qw * qy), 2.f * (qy * qz + qw * qx), 1.f - 2.f * (qx * qx + qy * qy)};
+            float R[9], nrm;
+            Q4 qn;
+            qtomat<true>(qload(rotation + 4 * i), R, qn, nrm);
             const float c[3] = {x, y, z};
             bool inside = true;
             for (int m = 0; m < 2; m++) {
                 const float v[3] = {zn[3 * m] * s[0], zn[3 * m + 1] * s[1], zn[3 * m + 2] * s[2]};
 #pragma unroll
                 for (int a = 0; a < 3; a++) {
-                    const float w = R[3 * a] * v[0] + R[3 * a + 1] * v[1] + R[3 * a + 2] * v[2] + c[a];
+                    const float w = rot_row<true>(R + 3 * a, v, c[a]);
                     inside = inside && (w >= box.lo[a]) && (w <= box.hi[a]);
                 }
             }

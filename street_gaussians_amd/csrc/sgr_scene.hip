@@ -25,6 +25,7 @@
 #include "../../include/sgr_scene_step.h"
 #include "sgr_adam_math.h"
 #include "sgr_common.h"
+#include "sgr_quat.h"
 
 #define SGR_SC_THREADS 256
 #define SGR_SC_NPART 16  // per-chunk partials of an actor: G[9] (sum dx' x^T), T[3] (sum dx'), Q[4] (rotation path)
@@ -39,73 +40,35 @@ struct SgrSegDev {
     int32_t corr_first;  // static segment under a correction: ordinal of its first chunk among the corrected chunks
 };
 
-// ---- quaternion helpers (real part first; general_utils.py:220-238) ----
-struct Q4 { float w, x, y, z; };
-__device__ __forceinline__ Q4 qmul(const Q4 a, const Q4 b) {
-    return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-            a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-}
-__device__ __forceinline__ Q4 qconj(const Q4 a) { return {a.w, -a.x, -a.y, -a.z}; }
-__device__ __forceinline__ float qdot(const Q4 a, const Q4 b) { return a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z; }
-// torch.nn.functional.normalize: x / max(|x|, 1e-12)
-__device__ __forceinline__ Q4 qnormalize(const Q4 a, float& n) {
-    n = fmaxf(sqrtf(qdot(a, a)), 1e-12f);
-    return {a.w / n, a.x / n, a.y / n, a.z / n};
-}
-// y = x / max(|x|, eps): dx = (dy - y (y . dy)) / n   (for |x| > eps; the clamped branch is dy / eps)
-__device__ __forceinline__ Q4 qnormalize_bwd(const Q4 y, float n, const Q4 dy, bool clamped) {
-    if (clamped) return {dy.w / n, dy.x / n, dy.y / n, dy.z / n};
-    const float d = qdot(y, dy);
-    return {(dy.w - y.w * d) / n, (dy.x - y.x * d) / n, (dy.y - y.y * d) / n, (dy.z - y.z * d) / n};
-}
-// quaternion_to_matrix (general_utils.py:125-146): normalises by |q| (no eps), row-major R
-__device__ __forceinline__ void qtomat(const Q4 q, float (&R)[9], Q4& qn, float& norm) {
-    norm = sqrtf(qdot(q, q));
-    qn = {q.w / norm, q.x / norm, q.y / norm, q.z / norm};
-    const float r = qn.w, x = qn.x, y = qn.y, z = qn.z;
-    R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - r * z); R[2] = 2.f * (x * z + r * y);
-    R[3] = 2.f * (x * y + r * z); R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - r * x);
-    R[6] = 2.f * (x * z - r * y); R[7] = 2.f * (y * z + r * x); R[8] = 1.f - 2.f * (x * x + y * y);
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// ---- camera pose correction (include/sgr_scene_frame.h): the declared order, contraction off --------------------
-__device__ __forceinline__ float qlen_nc(const Q4 a) {
-#pragma clang fp contract(off)
-    return sqrtf(((a.w * a.w + a.x * a.x) + a.y * a.y) + a.z * a.z);
-}
-__device__ __forceinline__ Q4 qmul_nc(const Q4 a, const Q4 b) {
-#pragma clang fp contract(off)
-    return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-            a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-}
+// ---- camera pose correction (include/sgr_scene_frame.h): the declared order, contraction off (sgr_quat.h: f<true>) ----
 struct SgrCorr {
     Q4 raw, qc, qq;     // c[0:4], F.normalize(c[0:4]), qc / |qc|
     float nc, n2;       // max(|raw|, 1e-12), |qc|
     float R[9], t[3];
 };
 __device__ __forceinline__ SgrCorr corr_load(const float* __restrict__ c) {
-#pragma clang fp contract(off)
     SgrCorr k;
-    k.raw = {c[0], c[1], c[2], c[3]};
-    k.nc = fmaxf(qlen_nc(k.raw), 1e-12f);
-    k.qc = {k.raw.w / k.nc, k.raw.x / k.nc, k.raw.y / k.nc, k.raw.z / k.nc};
-    k.n2 = qlen_nc(k.qc);
-    k.qq = {k.qc.w / k.n2, k.qc.x / k.n2, k.qc.y / k.n2, k.qc.z / k.n2};
-    const float r = k.qq.w, x = k.qq.x, y = k.qq.y, z = k.qq.z;
-    k.R[0] = 1.f - 2.f * (y * y + z * z); k.R[1] = 2.f * (x * y - r * z); k.R[2] = 2.f * (x * z + r * y);
-    k.R[3] = 2.f * (x * y + r * z); k.R[4] = 1.f - 2.f * (x * x + z * z); k.R[5] = 2.f * (y * z - r * x);
-    k.R[6] = 2.f * (x * z - r * y); k.R[7] = 2.f * (y * z + r * x); k.R[8] = 1.f - 2.f * (x * x + y * y);
+    k.raw = qload(c);
+    k.qc = qnormalize<true>(k.raw, k.nc);
+    qtomat<true>(k.qc, k.R, k.qq, k.n2);
     k.t[0] = c[4]; k.t[1] = c[5]; k.t[2] = c[6];
     return k;
 }
-// x'_a = ((x_0 R_a0 + x_1 R_a1) + x_2 R_a2) + t_a
-__device__ __forceinline__ void corr_xyz(const SgrCorr& k, float (&x)[3]) {
-#pragma clang fp contract(off)
-    float y[3];
+
+// ---- the fixed-order sums of a 256-thread workgroup's 16 values: wave butterfly, then waves 0..3 in order -------------
+__device__ __forceinline__ void sum16_fixed(float (&v)[SGR_SC_NPART], float (&red)[SGR_SC_THREADS / 64][SGR_SC_NPART]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int a = 0; a < 3; a++) y[a] = ((x[0] * k.R[3 * a] + x[1] * k.R[3 * a + 1]) + x[2] * k.R[3 * a + 2]) + k.t[a];
-    x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
+    for (int k = 0; k < SGR_SC_NPART; k++) {
+        float a = v[k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m, 64);
+        if (lane == 0) red[wave][k] = a;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ float sum16_waves(const float (&red)[SGR_SC_THREADS / 64][SGR_SC_NPART], int k) {
+    return ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
 }
 
 // ---- forward: small attributes, one lane per Gaussian ---------------------------------------------------------
@@ -124,22 +87,19 @@ sgr_scene_fwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
     if (sg.kind == SGR_SEG_ACTOR) {
         if (sg.flip_mask && sg.flip_mask[i]) {  // street_gaussian_model.py:324-327, 354-356
             x[sg.flip_axis] = -x[sg.flip_axis];
-            q = qmul({sg.flip_quat[0], sg.flip_quat[1], sg.flip_quat[2], sg.flip_quat[3]}, q);
+            q = qmul(qload(sg.flip_quat), q);
         }
-        const Q4 po = {sg.pose[0], sg.pose[1], sg.pose[2], sg.pose[3]};
+        const Q4 po = qload(sg.pose);
         float R[9], pn;
         Q4 pq;
-        qtomat(po, R, pq, pn);  // :357
-        const float y0 = R[0] * x[0] + R[1] * x[1] + R[2] * x[2] + sg.pose[4];  // :358
-        const float y1 = R[3] * x[0] + R[4] * x[1] + R[5] * x[2] + sg.pose[5];
-        const float y2 = R[6] * x[0] + R[7] * x[1] + R[8] * x[2] + sg.pose[6];
-        x[0] = y0; x[1] = y1; x[2] = y2;
+        qtomat(po, R, pq, pn);          // :357
+        rot_apply(R, sg.pose + 4, x);   // :358
         float n2;
         q = qnormalize(qmul(po, q), n2);  // :328-329
     } else if (corr) {  // camera pose correction (camera_pose.py:89-114, street_gaussian_model.py:311-312, 340-341)
         const SgrCorr k = corr_load(corr);
-        corr_xyz(k, x);
-        q = qmul_nc(k.qc, q);
+        rot_apply<true>(k.R, k.t, x);
+        q = qmul<true>(k.qc, q);
     }
     means3D[3 * o] = x[0]; means3D[3 * o + 1] = x[1]; means3D[3 * o + 2] = x[2];
     *reinterpret_cast<float4*>(rotations + 4 * o) = make_float4(q.w, q.x, q.y, q.z);
@@ -244,6 +204,24 @@ __device__ __forceinline__ void sink_step(const float* param, const sgr_scene_st
     } while (0)
 
 // ---- backward: small attributes + per-chunk pose partials ------------------------------------------------------
+// One Gaussian's 16 partials of the rigid motion x' = R x + t, rot' = a (x) b, from dx (on x') and du (on the product):
+// G = dx x^T, T = dx, Q = du b* (d(a b)/da . dO = dO b*).  dx becomes R^T dx; returns a* du (d(a b)/db . dO = a* dO).
+__device__ __forceinline__ Q4 rigid_partials(const float (&R)[9], const float (&x)[3], const Q4 a, const Q4 b, const Q4 du,
+                                             float (&dx)[3], float (&part)[SGR_SC_NPART]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) part[3 * r + c] = dx[r] * x[c];
+        part[9 + r] = dx[r];
+    }
+    float dl[3];
+    rot_pullback(R, dx, dl);
+    dx[0] = dl[0]; dx[1] = dl[1]; dx[2] = dl[2];
+    const Q4 da = qmul(du, qconj(b));
+    part[12] = da.w; part[13] = da.x; part[14] = da.y; part[15] = da.z;
+    return qmul(qconj(a), du);
+}
+
 template <int STEP>
 __global__ void __launch_bounds__(SGR_SC_THREADS)
 sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __restrict__ segs, int S,
@@ -275,54 +253,29 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
         const Q4 qraw = {qr.x, qr.y, qr.z, qr.w};
         float n;
         const Q4 ql0 = qnormalize(qraw, n);
-        const bool clamped = sqrtf(qdot(qraw, qraw)) < 1e-12f;
-        if (sg.kind == SGR_SEG_ACTOR) {
+        const bool clamped = qlen(qraw) < SGR_Q_EPS;
+        if (sg.kind == SGR_SEG_ACTOR) {  // x' = R(po) x + t, rot' = normalize(po (x) ql), after the flip of x and ql0
             const bool flip = sg.flip_mask && sg.flip_mask[i];
-            const Q4 fq = {sg.flip_quat[0], sg.flip_quat[1], sg.flip_quat[2], sg.flip_quat[3]};
+            const Q4 fq = qload(sg.flip_quat);
             float x[3] = {sg.xyz[3 * i], sg.xyz[3 * i + 1], sg.xyz[3 * i + 2]};
             if (flip) x[sg.flip_axis] = -x[sg.flip_axis];
             const Q4 ql = flip ? qmul(fq, ql0) : ql0;
-            const Q4 po = {sg.pose[0], sg.pose[1], sg.pose[2], sg.pose[3]};
-            float R[9], pn;
+            const Q4 po = qload(sg.pose);
+            float R[9], pn, n2;
             Q4 pq;
             qtomat(po, R, pq, pn);
-            // x' = R x + t
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-#pragma unroll
-                for (int b = 0; b < 3; b++) part[3 * a + b] = dx[a] * x[b];
-                part[9 + a] = dx[a];
-            }
-            float dl[3] = {R[0] * dx[0] + R[3] * dx[1] + R[6] * dx[2], R[1] * dx[0] + R[4] * dx[1] + R[7] * dx[2],
-                           R[2] * dx[0] + R[5] * dx[1] + R[8] * dx[2]};
-            if (flip) dl[sg.flip_axis] = -dl[sg.flip_axis];
-            dx[0] = dl[0]; dx[1] = dl[1]; dx[2] = dl[2];
-            // r = normalize(po (x) ql)
-            float n2;
             const Q4 u = qmul(po, ql);
             const Q4 r = qnormalize(u, n2);
-            const Q4 du = qnormalize_bwd(r, n2, dq, sqrtf(qdot(u, u)) < 1e-12f);
-            const Q4 dpo = qmul(du, qconj(ql));   // d(a b)/da . dO = dO b*
-            part[12] = dpo.w; part[13] = dpo.x; part[14] = dpo.y; part[15] = dpo.z;
-            Q4 dql = qmul(qconj(po), du);          // d(a b)/db . dO = a* dO
-            if (flip) dql = qmul(qconj(fq), dql);
-            dq = dql;
+            const Q4 du = qnormalize_bwd(r, n2, dq, qlen(u) < SGR_Q_EPS);
+            dq = rigid_partials(R, x, po, ql, du, dx, part);
+            if (flip) {
+                dx[sg.flip_axis] = -dx[sg.flip_axis];
+                dq = qmul(qconj(fq), dq);
+            }
         } else if (corr) {  // x' = R x + t, rot' = qc (x) ql0: the same partials as an actor's, over the background
             const SgrCorr k = corr_load(corr);
             const float x[3] = {sg.xyz[3 * i], sg.xyz[3 * i + 1], sg.xyz[3 * i + 2]};
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-#pragma unroll
-                for (int b = 0; b < 3; b++) part[3 * a + b] = dx[a] * x[b];
-                part[9 + a] = dx[a];
-            }
-            const float dl[3] = {k.R[0] * dx[0] + k.R[3] * dx[1] + k.R[6] * dx[2],
-                                 k.R[1] * dx[0] + k.R[4] * dx[1] + k.R[7] * dx[2],
-                                 k.R[2] * dx[0] + k.R[5] * dx[1] + k.R[8] * dx[2]};
-            dx[0] = dl[0]; dx[1] = dl[1]; dx[2] = dl[2];
-            const Q4 dqc = qmul(dq, qconj(ql0));  // d(a b)/da . dO = dO b*
-            part[12] = dqc.w; part[13] = dqc.x; part[14] = dqc.y; part[15] = dqc.z;
-            dq = qmul(qconj(k.qc), dq);           // d(a b)/db . dO = a* dO
+            dq = rigid_partials(k.R, x, k.qc, ql0, dq, dx, part);
         }
         if (sink_wants<STEP>(gr.xyz, kxyz)) {
             SGR_SINK(gr.xyz, sg.xyz, kxyz, 3 * i, dx[0]);
@@ -383,20 +336,8 @@ sgr_scene_bwd_kernel(const SgrChunk* __restrict__ chunks, const SgrSegDev* __res
     if (sg.kind == SGR_SEG_ACTOR) dst = partials ? partials + (size_t)blockIdx.x * SGR_SC_NPART : nullptr;
     else if (corr && cpart) dst = cpart + (size_t)(sd.corr_first + (int)blockIdx.x - sd.first_chunk) * SGR_SC_NPART;
     if (dst == nullptr) return;
-    // chunk-wide sums in a fixed order: wave butterfly, then waves 0..3 in order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SGR_SC_NPART; k++) {
-        float v = part[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < SGR_SC_NPART) {
-        const int k = threadIdx.x;
-        dst[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
+    sum16_fixed(part, red);
+    if (threadIdx.x < SGR_SC_NPART) dst[threadIdx.x] = sum16_waves(red, threadIdx.x);
 }
 
 // one workgroup (one wave) per actor: sum its chunks in order, then chain into the 7 pose parameters
@@ -412,19 +353,10 @@ sgr_scene_pose_bwd_kernel(const SgrSegDev* __restrict__ segs, const float* __res
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
-    const float* G = tot;  // G[3a+b] = sum dx'_a x_b
-    const Q4 po = {sd.s.pose[0], sd.s.pose[1], sd.s.pose[2], sd.s.pose[3]};
     float R[9], pn;
     Q4 q;
-    qtomat(po, R, q, pn);
-    const float r = q.w, x = q.x, y = q.y, z = q.z;
-    // dL/d(normalised quaternion) through R(q) (general_utils.py:137-145)
-    Q4 dqn;
-    dqn.w = 2.f * (-z * G[1] + y * G[2] + z * G[3] - x * G[5] - y * G[6] + x * G[7]);
-    dqn.x = 2.f * (y * G[1] + z * G[2] + y * G[3] - 2.f * x * G[4] - r * G[5] + z * G[6] + r * G[7] - 2.f * x * G[8]);
-    dqn.y = 2.f * (-2.f * y * G[0] + x * G[1] + r * G[2] + x * G[3] + z * G[5] - r * G[6] + z * G[7] - 2.f * y * G[8]);
-    dqn.z = 2.f * (-2.f * z * G[0] - r * G[1] + x * G[2] + r * G[3] - 2.f * z * G[4] + y * G[5] + x * G[6] + y * G[7]);
-    const Q4 dpo = qnormalize_bwd(q, pn, dqn, false);
+    qtomat(qload(sd.s.pose), R, q, pn);
+    const Q4 dpo = qnormalize_bwd(q, pn, dquat_of_R(q, tot), false);  // tot[0:9] = G, through quaternion_to_matrix's own |q|
     sd.g.pose[0] = dpo.w + tot[12];
     sd.g.pose[1] = dpo.x + tot[13];
     sd.g.pose[2] = dpo.y + tot[14];
@@ -432,30 +364,6 @@ sgr_scene_pose_bwd_kernel(const SgrSegDev* __restrict__ segs, const float* __res
     sd.g.pose[4] = tot[9];
     sd.g.pose[5] = tot[10];
     sd.g.pose[6] = tot[11];
-}
-
-// dL/d(unit quaternion q) of x' = R(q) x from G[3a+b] = sum dx'_a x_b (general_utils.py:137-145)
-__device__ __forceinline__ Q4 dquat_of_R(const Q4 q, const float* G) {
-    const float r = q.w, x = q.x, y = q.y, z = q.z;
-    Q4 d;
-    d.w = 2.f * (-z * G[1] + y * G[2] + z * G[3] - x * G[5] - y * G[6] + x * G[7]);
-    d.x = 2.f * (y * G[1] + z * G[2] + y * G[3] - 2.f * x * G[4] - r * G[5] + z * G[6] + r * G[7] - 2.f * x * G[8]);
-    d.y = 2.f * (-2.f * y * G[0] + x * G[1] + r * G[2] + x * G[3] + z * G[5] - r * G[6] + z * G[7] - 2.f * y * G[8]);
-    d.z = 2.f * (-2.f * z * G[0] - r * G[1] + x * G[2] + r * G[3] - 2.f * z * G[4] + y * G[5] + x * G[6] + y * G[7]);
-    return d;
-}
-
-// the 16 sums of a workgroup's values in a fixed order: wave butterfly, then waves 0..3 in order (256 threads)
-__device__ __forceinline__ void sum16_fixed(float (&v)[SGR_SC_NPART], float (&red)[SGR_SC_THREADS / 64][SGR_SC_NPART]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SGR_SC_NPART; k++) {
-        float a = v[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m, 64);
-        if (lane == 0) red[wave][k] = a;
-    }
-    __syncthreads();
 }
 
 // correction, level 2: workgroup b sums the corrected chunks [256 b, 256 b + 256) (one per lane) in a fixed order
@@ -470,10 +378,7 @@ sgr_scene_corr_sum_kernel(const float* __restrict__ cpart, int nc, float* __rest
         v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
     }
     sum16_fixed(v, red);
-    if (threadIdx.x < SGR_SC_NPART) {
-        const int k = threadIdx.x;
-        gpart[(size_t)blockIdx.x * SGR_SC_NPART + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
+    if (threadIdx.x < SGR_SC_NPART) gpart[(size_t)blockIdx.x * SGR_SC_NPART + threadIdx.x] = sum16_waves(red, threadIdx.x);
 }
 
 // correction, level 3: one workgroup sums the ng groups (lane l: groups l, l + 256, ... in order), then one lane chains
@@ -492,11 +397,11 @@ sgr_scene_corr_final_kernel(const float* __restrict__ gpart, int ng, const float
     if (threadIdx.x != 0) return;
     float tot[SGR_SC_NPART];
 #pragma unroll
-    for (int k = 0; k < SGR_SC_NPART; k++) tot[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    for (int k = 0; k < SGR_SC_NPART; k++) tot[k] = sum16_waves(red, k);
     const SgrCorr c = corr_load(corr);
     Q4 dqc = qnormalize_bwd(c.qq, c.n2, dquat_of_R(c.qq, tot), false);  // quaternion_to_matrix's own |q| (no eps)
-    dqc = {dqc.w + tot[12], dqc.x + tot[13], dqc.y + tot[14], dqc.z + tot[15]};
-    const Q4 d = qnormalize_bwd(c.qc, c.nc, dqc, qlen_nc(c.raw) < 1e-12f);  // F.normalize
+    dqc = qadd(dqc, qload(tot + 12));
+    const Q4 d = qnormalize_bwd(c.qc, c.nc, dqc, qlen<true>(c.raw) < SGR_Q_EPS);  // F.normalize
     out[0] = d.w; out[1] = d.x; out[2] = d.y; out[3] = d.z;
     out[4] = tot[9]; out[5] = tot[10]; out[6] = tot[11];
 }

@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE.  Host (x86) build of the __host__ __device__ maths in
-// street_gaussians_amd/csrc/sgr_math.h, so the per-Gaussian formulas the gfx950 kernels run can be
-// checked against the oracle without a GPU (tests/test_host_math.py).  Built with
+// street_gaussians_amd/csrc/sgr_math.h and sgr_quat.h, so the formulas the gfx950 kernels run can be
+// checked against the oracle without a GPU (tests/test_host_math.py, tests/test_quat_cpu.py).  Built with
 // `hipcc -x hip --cuda-host-only`; never loaded by the product.
 #include "../../street_gaussians_amd/csrc/sgr_math.h"
+#include "../../street_gaussians_amd/csrc/sgr_quat.h"
 
 static SgrCam make_cam(const float* view, const float* proj, const float* campos, float tanx, float tany, int W, int H,
                        float mod) {
@@ -137,6 +138,58 @@ void hm_moments_to_grads(int exact, const float* conic_opacity, int W, int H, fl
     const SgrNdcScale k = sgr_ndc_scale(W, H, exact != 0);
     sgr_moments_to_grads(q.x, q.y, q.z, q.w, k.kx, k.ky, s[0], s[1], s[2], s[3], s[4], s[5]);
 }
+// ---- csrc/sgr_quat.h (tests/test_quat_cpu.py): n rows per call, nc = 1 the f<true> flavour, 0 the default one ----
+void hm_quat_mul(int n, int nc, const float* a, const float* b, float* o) {
+    for (int i = 0; i < n; i++) {
+        const Q4 r = nc ? qmul<true>(qload(a + 4 * i), qload(b + 4 * i)) : qmul(qload(a + 4 * i), qload(b + 4 * i));
+        o[4 * i] = r.w; o[4 * i + 1] = r.x; o[4 * i + 2] = r.y; o[4 * i + 3] = r.z;
+    }
+}
+void hm_quat_normalize(int n, int nc, const float* a, float* y, float* norm) {
+    for (int i = 0; i < n; i++) {
+        const Q4 r = nc ? qnormalize<true>(qload(a + 4 * i), norm[i]) : qnormalize(qload(a + 4 * i), norm[i]);
+        y[4 * i] = r.w; y[4 * i + 1] = r.x; y[4 * i + 2] = r.y; y[4 * i + 3] = r.z;
+    }
+}
+void hm_quat_normalize_bwd(int n, int nc, const float* y, const float* norm, const float* dy, const unsigned char* clamped,
+                           float* da) {
+    for (int i = 0; i < n; i++) {
+        const Q4 r = nc ? qnormalize_bwd<true>(qload(y + 4 * i), norm[i], qload(dy + 4 * i), clamped[i] != 0)
+                        : qnormalize_bwd(qload(y + 4 * i), norm[i], qload(dy + 4 * i), clamped[i] != 0);
+        da[4 * i] = r.w; da[4 * i + 1] = r.x; da[4 * i + 2] = r.y; da[4 * i + 3] = r.z;
+    }
+}
+void hm_quat_to_matrix(int n, int nc, const float* q, float* R, float* qn, float* norm) {
+    for (int i = 0; i < n; i++) {
+        float M[9];
+        Q4 u;
+        if (nc) qtomat<true>(qload(q + 4 * i), M, u, norm[i]);
+        else qtomat(qload(q + 4 * i), M, u, norm[i]);
+        for (int k = 0; k < 9; k++) R[9 * i + k] = M[k];
+        qn[4 * i] = u.w; qn[4 * i + 1] = u.x; qn[4 * i + 2] = u.y; qn[4 * i + 3] = u.z;
+    }
+}
+void hm_quat_rot_apply(int n, int nc, const float* R, const float* t, float* x) {  // x <- R x + t, in place
+    for (int i = 0; i < n; i++) {
+        float v[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
+        if (nc) rot_apply<true>(R + 9 * i, t + 3 * i, v);
+        else rot_apply(R + 9 * i, t + 3 * i, v);
+        x[3 * i] = v[0]; x[3 * i + 1] = v[1]; x[3 * i + 2] = v[2];
+    }
+}
+void hm_quat_rot_pullback(int n, int nc, const float* R, const float* g, float* o) {
+    for (int i = 0; i < n; i++) {
+        if (nc) rot_pullback<true>(R + 9 * i, g + 3 * i, o + 3 * i);
+        else rot_pullback(R + 9 * i, g + 3 * i, o + 3 * i);
+    }
+}
+void hm_quat_dquat_of_R(int n, int nc, const float* q, const float* G, float* d) {
+    for (int i = 0; i < n; i++) {
+        const Q4 r = nc ? dquat_of_R<true>(qload(q + 4 * i), G + 9 * i) : dquat_of_R(qload(q + 4 * i), G + 9 * i);
+        d[4 * i] = r.w; d[4 * i + 1] = r.x; d[4 * i + 2] = r.y; d[4 * i + 3] = r.z;
+    }
+}
+
 void hm_div_by_seed(int n, const float* a, const float* b, const float* seed, float* q) {
     for (int i = 0; i < n; i++) {
         const float y0 = seed[i];

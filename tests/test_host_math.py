@@ -4,6 +4,7 @@ off on both sides), per-Gaussian gradients within 1e-4 -- under the yawed make_c
 tests/cameras.py (pitch, roll, off-centre K, z-up basis, skew, a far translation).  No GPU needed."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -17,14 +18,24 @@ from street_gaussians_amd import synthetic as syn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_math", "host_math.hip")
-HDR = os.path.join(HERE, "..", "street_gaussians_amd", "csrc", "sgr_math.h")
 LIB = os.path.join(HERE, "_build", "libsgr_hostmath.so")
+
+
+def _sources(path, seen=None):
+    """`path` and every file it includes with quotes, transitively: what the host library is built from."""
+    seen = set() if seen is None else seen
+    path = os.path.realpath(path)
+    if path not in seen:
+        seen.add(path)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            _sources(os.path.join(os.path.dirname(path), inc), seen)
+    return seen
 
 
 @pytest.fixture(scope="module")
 def hm():
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(p) for p in _sources(SRC)):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--cuda-host-only", "-O2", "-fPIC", "-shared",
                                "-std=c++17", SRC, "-o", LIB])
     L = C.CDLL(LIB)
