@@ -3,7 +3,7 @@
 //
 // Forward: ONE map kernel, a 256-lane workgroup per 16x16 pixel tile.  The tile's mask is read once (the 26x26 halo's
 // bits stay in a register of the lane that stages them), then per channel the halo of image and gt is staged in LDS and
-// filtered separably like sgr_ssim_fwd_kernel (sgr_loss.hip): SSIM map value + its three partials, and from the staged
+// filtered separably with the steps of sgr_ssim.h: SSIM map value + its three partials, and from the staged
 // centre value |a - b| and (a - b)^2.  acc / acc_obj / depth / lidar_depth are read once per pixel: sky term, object term,
 // LiDAR key (written for the radix select of sgr_loss.hip, sgr_lidar_select_launch).  Six block sums per workgroup go to
 // the workspace in block order; one finishing workgroup reduces them in a fixed order and evaluates the eight scalars.
@@ -39,23 +39,19 @@ struct FlWeights { float w_l1, lambda_dssim, lambda_sky, sky_scale, lambda_reg, 
 __device__ __forceinline__ void fl_block_sums(float (&v)[SGR_FL_SUMS], float (*lds)[4], float* __restrict__ sums, size_t nblocks,
                                               size_t block) {
 #pragma unroll
-    for (int q = 0; q < SGR_FL_SUMS; q++) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[q] += __shfl_xor(v[q], m, 64);
-        if ((threadIdx.x & 63) == 0) lds[q][threadIdx.x >> 6] = v[q];
-    }
+    for (int q = 0; q < SGR_FL_SUMS; q++) wave_sums_to_lds(v[q], lds[q]);
     __syncthreads();
     if (threadIdx.x < SGR_FL_SUMS) {
         const int q = threadIdx.x;
-        sums[q * nblocks + block] = ((lds[q][0] + lds[q][1]) + lds[q][2]) + lds[q][3];
+        sums[q * nblocks + block] = lds4_total(lds[q]);
     }
 }
 
 __global__ void __launch_bounds__(256)
 sgr_frame_loss_map_kernel(int C, int H, int W, sgr_frame_loss_args in, SgrGauss11 g, float* __restrict__ partials, LdWork ld,
                           float* __restrict__ block_sums) {
-    __shared__ float sx[SGR_LS_IN][SGR_LS_IN + 1], sy[SGR_LS_IN][SGR_LS_IN + 1];
-    __shared__ float hb[5][SGR_LS_IN][SGR_LS_T + 1];
+    __shared__ SsimHalo sx, sy;
+    __shared__ SsimRows hb[5];
     __shared__ float red[SGR_FL_SUMS][4];
     __shared__ uint32_t cnt[4];
     const int x0 = blockIdx.x * SGR_LS_T, y0 = blockIdx.y * SGR_LS_T;
@@ -97,36 +93,17 @@ sgr_frame_loss_map_kernel(int C, int H, int W, sgr_frame_loss_args in, SgrGauss1
         }
         __syncthreads();
         const float ca = sx[ty + SGR_LS_R][tx + SGR_LS_R], cb = sy[ty + SGR_LS_R][tx + SGR_LS_R];
-        for (int e = threadIdx.x; e < SGR_LS_IN * SGR_LS_T; e += 256) {  // horizontal pass: 26 rows x 16 columns
-            const int r = e / SGR_LS_T, q = e - r * SGR_LS_T;
-            float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-                const float a = sx[r][q + k], b = sy[r][q + k], w = g.w[k];
-                m1 += w * a; m2 += w * b; s11 += w * a * a; s22 += w * b * b; s12 += w * a * b;
-            }
-            hb[0][r][q] = m1; hb[1][r][q] = m2; hb[2][r][q] = s11; hb[3][r][q] = s22; hb[4][r][q] = s12;
-        }
+        ssim_hpass5(threadIdx.x, sx, sy, g, hb);
         __syncthreads();
-        float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float w = g.w[k];
-            m1 += w * hb[0][ty + k][tx]; m2 += w * hb[1][ty + k][tx]; s11 += w * hb[2][ty + k][tx];
-            s22 += w * hb[3][ty + k][tx]; s12 += w * hb[4][ty + k][tx];
-        }
+        float mm[5];
+        ssim_vpass<5>(hb, g, ty, tx, mm);
         if (inside) {
-            // loss_utils.py:104-118
-            const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-            const float mu1_sq = m1 * m1, mu2_sq = m2 * m2, mu12 = m1 * m2;
-            const float sg1 = s11 - mu1_sq, sg2 = s22 - mu2_sq, sg12 = s12 - mu12;
-            const float A = 2.f * mu12 + C1, B = 2.f * sg12 + C2, Cc = mu1_sq + mu2_sq + C1, D = sg1 + sg2 + C2;
-            const float val = (A * B) / (Cc * D);
+            float val, part[3];
+            ssim_point(mm, val, part);
             const size_t oc = c * plane + o;
-            const float icd = 1.0f / (Cc * D);
-            partials[oc] = 2.f * m2 * (B - A) * icd - 2.f * m1 * val * (1.0f / Cc - 1.0f / D);  // dM/dmu1
-            partials[cp + oc] = -val / D;                                                        // dM/dsigma1^2
-            partials[2 * cp + oc] = 2.f * A * icd;                                                // dM/dsigma12
+            partials[oc] = part[0];
+            partials[cp + oc] = part[1];
+            partials[2 * cp + oc] = part[2];
             v[0] += val;
             if (m) {  // l1_loss / psnr: the masked pixels' C values (loss_utils.py:21-37, :61-78)
                 const float d = ca - cb;
@@ -151,14 +128,10 @@ sgr_frame_loss_map_kernel(int C, int H, int W, sgr_frame_loss_args in, SgrGauss1
             ld.key[o] = key;
         }
     }
-    if (in.lidar_depth) {
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) nl += __shfl_xor(nl, s, 64);
-        if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = nl;
-    }
+    if (in.lidar_depth) wave_sums_to_lds(nl, cnt);
     fl_block_sums(v, red, block_sums, (size_t)gridDim.x * gridDim.y, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
     // (fl_block_sums' barrier also orders cnt)  integers: the order of the adds does not matter
-    if (in.lidar_depth && threadIdx.x == 0) atomicAdd(&ld.state[0], cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+    if (in.lidar_depth && threadIdx.x == 0) atomicAdd(&ld.state[0], lds4_total(cnt));
 }
 
 // one workgroup: tot[q] = sum of sums[q][0..nblocks), lanes striding over the blocks, in a fixed order.  A trip covers
@@ -226,8 +199,8 @@ sgr_frame_loss_bwd_kernel(int C, int H, int W, sgr_frame_loss_args in, FlWeights
                           const float* __restrict__ partials, const float* __restrict__ head, LdWork ld,
                           const float* __restrict__ upstream, float* __restrict__ dimg, float* __restrict__ dacc,
                           float* __restrict__ ddepth, float* __restrict__ dobj) {
-    __shared__ float sp[3][SGR_LS_IN][SGR_LS_IN + 1];
-    __shared__ float hb[3][SGR_LS_IN][SGR_LS_T + 1];
+    __shared__ SsimHalo sp[3];
+    __shared__ SsimRows hb[3];
     const int x0 = blockIdx.x * SGR_LS_T, y0 = blockIdx.y * SGR_LS_T;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int x = x0 + tx, y = y0 + ty;
@@ -238,42 +211,18 @@ sgr_frame_loss_bwd_kernel(int C, int H, int W, sgr_frame_loss_args in, FlWeights
         const bool m = inside && (!in.mask || in.mask[o]);
         const float w_ssim = -wt.lambda_dssim;  // the loss holds 1 - ssim
         for (int c = 0; c < C; c++) {
-            for (int e = threadIdx.x; e < SGR_LS_IN * SGR_LS_IN; e += 256) {
-                const int r = e / SGR_LS_IN, q = e - r * SGR_LS_IN;
-                const int yy = y0 + r - SGR_LS_R, xx = x0 + q - SGR_LS_R;
-                float a = 0.f, b = 0.f, d = 0.f;
-                if (xx >= 0 && xx < W && yy >= 0 && yy < H) {
-                    const size_t oo = c * plane + (size_t)yy * W + xx;
-                    a = partials[oo]; b = partials[cp + oo]; d = partials[2 * cp + oo];
-                }
-                sp[0][r][q] = a; sp[1][r][q] = b; sp[2][r][q] = d;
-            }
+            ssim_stage_partials(threadIdx.x, partials, c, plane, cp, x0, y0, H, W, sp);
             __syncthreads();
-            for (int e = threadIdx.x; e < SGR_LS_IN * SGR_LS_T; e += 256) {
-                const int r = e / SGR_LS_T, q = e - r * SGR_LS_T;
-                float a = 0.f, b = 0.f, d = 0.f;
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const float w = g.w[k];
-                    a += w * sp[0][r][q + k]; b += w * sp[1][r][q + k]; d += w * sp[2][r][q + k];
-                }
-                hb[0][r][q] = a; hb[1][r][q] = b; hb[2][r][q] = d;
-            }
+            ssim_hpass<3>(threadIdx.x, sp, g, hb);
             __syncthreads();
             if (inside) {
                 float out = 0.f;
                 if (m) {
-                    float a = 0.f, b = 0.f, d = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; k++) {
-                        const float w = g.w[k];
-                        a += w * hb[0][ty + k][tx]; b += w * hb[1][ty + k][tx]; d += w * hb[2][ty + k][tx];
-                    }
+                    float f[3];
+                    ssim_vpass<3>(hb, g, ty, tx, f);
                     const float xv = in.image[c * plane + o], yv = in.gt[c * plane + o];
-                    out = w_ssim * ((a + 2.f * xv * b + yv * d) * (up / (float)cp));
-                    const float df = xv - yv;
-                    const float sg = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);  // torch: sign(0) = 0
-                    out += wt.w_l1 * up * sg / head[4];
+                    out = w_ssim * ssim_grad(f[0], f[1], f[2], xv, yv, up / (float)cp);
+                    out += wt.w_l1 * up * l1_sign(xv - yv) / head[4];
                 }
                 dimg[c * plane + o] = out;
             }
@@ -337,7 +286,7 @@ sgr_mse_finish_kernel(const float* __restrict__ block_sums, size_t nblocks, floa
 }
 
 static int fl_check(int C, int H, int W, const sgr_frame_loss_args* a, bool& sky, bool& obj, bool& lidar) {
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!a || !a->image || !a->gt) return sgr_set_error(SGR_E_INVALID, "args, image and gt are required");
     if (a->sky_mask && !a->acc) return sgr_set_error(SGR_E_INVALID, "the sky term needs acc and sky_mask");
     if (!a->acc_obj != !a->obj_bound) return sgr_set_error(SGR_E_INVALID, "the object term needs acc_obj and obj_bound");
@@ -377,12 +326,11 @@ int sgr_frame_loss_forward(int C, int H, int W, const sgr_frame_loss_args* args,
     if (const int rc = fl_check(C, H, W, args, sky, obj, lidar)) return rc;
     if (!terms || !saved || !workspace) return sgr_set_error(SGR_E_INVALID, "terms, saved and workspace are required");
     const FlSaved s = fl_carve((char*)sgr_align_up((size_t)saved, 256), (size_t)C, (size_t)H * W);
-    static const SgrGauss11 g = make_window();
     const dim3 grid = tile_grid(1, H, W);
     const size_t nblocks = (size_t)grid.x * grid.y;
     if (lidar)  // hist [4][256] and state [16] lie back to back (ld_carve): one clear
         SGR_HIP(hipMemsetAsync(s.ld.hist, 0, (size_t)((char*)(s.ld.state + 16) - (char*)s.ld.hist), stream));
-    sgr_frame_loss_map_kernel<<<grid, 256, 0, stream>>>(C, H, W, *args, g, s.partials, s.ld, workspace);
+    sgr_frame_loss_map_kernel<<<grid, 256, 0, stream>>>(C, H, W, *args, ssim_window(), s.partials, s.ld, workspace);
     if (lidar) sgr_lidar_select_launch(H * W, s.ld, args->keep, s.head, stream);
     sgr_frame_loss_finish_kernel<<<1, 256, 0, stream>>>(C, H, W, workspace, nblocks, fl_weights(args), sky, obj, lidar, s.head,
                                                         terms);
@@ -403,9 +351,9 @@ int sgr_frame_loss_backward(int C, int H, int W, const sgr_frame_loss_args* args
     if (dL_dacc_obj && !obj) return sgr_set_error(SGR_E_INVALID, "dL_dacc_obj: the object term is off");
     if (!dL_dimage && !dL_dacc && !dL_ddepth && !dL_dacc_obj) return 0;
     const FlSaved s = fl_carve((char*)sgr_align_up((size_t)const_cast<char*>(saved), 256), (size_t)C, (size_t)H * W);
-    static const SgrGauss11 g = make_window();
-    sgr_frame_loss_bwd_kernel<<<tile_grid(1, H, W), 256, 0, stream>>>(C, H, W, *args, fl_weights(args), g, s.partials, s.head,
-                                                                     s.ld, upstream, dL_dimage, dL_dacc, dL_ddepth, dL_dacc_obj);
+    sgr_frame_loss_bwd_kernel<<<tile_grid(1, H, W), 256, 0, stream>>>(C, H, W, *args, fl_weights(args), ssim_window(), s.partials,
+                                                                     s.head, s.ld, upstream, dL_dimage, dL_dacc, dL_ddepth,
+                                                                     dL_dacc_obj);
     SGR_HIP(hipGetLastError());
     return 0;
 }
@@ -418,7 +366,7 @@ size_t sgr_mse_workspace_floats(int C, int H, int W) {
 int sgr_mse_forward(int C, int H, int W, const float* a, const float* b, const uint8_t* mask, float* out, float* workspace,
                     void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!a || !b || !out || !workspace) return sgr_set_error(SGR_E_INVALID, "a, b, out and workspace are required");
     const size_t plane = (size_t)H * W, nblocks = (plane + 255) / 256;
     sgr_mse_map_kernel<<<(unsigned)nblocks, 256, 0, stream>>>(C, plane, a, b, mask, workspace);

@@ -12,15 +12,15 @@
 
 #include "../../include/sgr_loss.h"
 #include "sgr_common.h"
-#include "sgr_loss_internal.h"  // the window, tile geometry, block sum and per-pixel terms shared with sgr_frame_loss.hip
+#include "sgr_loss_internal.h"  // the SSIM steps, block sum and per-pixel terms shared with sgr_frame_loss.hip
 
 template <bool WITH_PARTIALS>
 __global__ void __launch_bounds__(256)
 sgr_ssim_fwd_kernel(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
                     const uint8_t* __restrict__ mask, SgrGauss11 g, float* __restrict__ partials,
                     float* __restrict__ block_sums) {
-    __shared__ float sx[SGR_LS_IN][SGR_LS_IN + 1], sy[SGR_LS_IN][SGR_LS_IN + 1];
-    __shared__ float hb[5][SGR_LS_IN][SGR_LS_T + 1];
+    __shared__ SsimHalo sx, sy;
+    __shared__ SsimRows hb[5];
     __shared__ float lds4[4];
     const int c = blockIdx.z, x0 = blockIdx.x * SGR_LS_T, y0 = blockIdx.y * SGR_LS_T;
     const size_t plane = (size_t)H * W;
@@ -38,40 +38,21 @@ sgr_ssim_fwd_kernel(int H, int W, const float* __restrict__ img1, const float* _
         sy[r][q] = b;
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < SGR_LS_IN * SGR_LS_T; e += 256) {  // horizontal pass: 26 rows x 16 columns
-        const int r = e / SGR_LS_T, q = e - r * SGR_LS_T;
-        float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float a = sx[r][q + k], b = sy[r][q + k], w = g.w[k];
-            m1 += w * a; m2 += w * b; s11 += w * a * a; s22 += w * b * b; s12 += w * a * b;
-        }
-        hb[0][r][q] = m1; hb[1][r][q] = m2; hb[2][r][q] = s11; hb[3][r][q] = s22; hb[4][r][q] = s12;
-    }
+    ssim_hpass5(threadIdx.x, sx, sy, g, hb);
     __syncthreads();
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-        const float w = g.w[k];
-        m1 += w * hb[0][ty + k][tx]; m2 += w * hb[1][ty + k][tx]; s11 += w * hb[2][ty + k][tx];
-        s22 += w * hb[3][ty + k][tx]; s12 += w * hb[4][ty + k][tx];
-    }
+    float m[5];
+    ssim_vpass<5>(hb, g, ty, tx, m);
     const int x = x0 + tx, y = y0 + ty;
     float val = 0.f;
     if (x < W && y < H) {
-        // loss_utils.py:104-118
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float mu1_sq = m1 * m1, mu2_sq = m2 * m2, mu12 = m1 * m2;
-        const float sg1 = s11 - mu1_sq, sg2 = s22 - mu2_sq, sg12 = s12 - mu12;
-        const float A = 2.f * mu12 + C1, B = 2.f * sg12 + C2, Cc = mu1_sq + mu2_sq + C1, D = sg1 + sg2 + C2;
-        val = (A * B) / (Cc * D);
+        float part[3];
+        ssim_point(m, val, part);
         if (WITH_PARTIALS) {
             const size_t o = c * plane + (size_t)y * W + x, cp = (size_t)gridDim.z * plane;
-            const float icd = 1.0f / (Cc * D);
-            partials[o] = 2.f * m2 * (B - A) * icd - 2.f * m1 * val * (1.0f / Cc - 1.0f / D);  // dM/dmu1
-            partials[cp + o] = -val / D;                                                            // dM/dsigma1^2
-            partials[2 * cp + o] = 2.f * A * icd;                                                    // dM/dsigma12
+            partials[o] = part[0];
+            partials[cp + o] = part[1];
+            partials[2 * cp + o] = part[2];
         }
     }
     const float s = block_sum_256(val, lds4);
@@ -102,51 +83,26 @@ sgr_ssim_bwd_kernel(int H, int W, int C, const float* __restrict__ img1, const f
                     const uint8_t* __restrict__ mask, SgrGauss11 g, const float* __restrict__ partials,
                     const float* __restrict__ upstream, float* __restrict__ dimg1, float w_ssim, float w_l1,
                     const float* __restrict__ l1_out) {
-    __shared__ float sp[3][SGR_LS_IN][SGR_LS_IN + 1];
-    __shared__ float hb[3][SGR_LS_IN][SGR_LS_T + 1];
+    __shared__ SsimHalo sp[3];
+    __shared__ SsimRows hb[3];
     const int c = blockIdx.z, x0 = blockIdx.x * SGR_LS_T, y0 = blockIdx.y * SGR_LS_T;
     const size_t plane = (size_t)H * W, cp = (size_t)C * plane;
-    for (int e = threadIdx.x; e < SGR_LS_IN * SGR_LS_IN; e += 256) {
-        const int r = e / SGR_LS_IN, q = e - r * SGR_LS_IN;
-        const int y = y0 + r - SGR_LS_R, x = x0 + q - SGR_LS_R;
-        float a = 0.f, b = 0.f, d = 0.f;
-        if (x >= 0 && x < W && y >= 0 && y < H) {
-            const size_t o = c * plane + (size_t)y * W + x;
-            a = partials[o]; b = partials[cp + o]; d = partials[2 * cp + o];
-        }
-        sp[0][r][q] = a; sp[1][r][q] = b; sp[2][r][q] = d;
-    }
+    ssim_stage_partials(threadIdx.x, partials, c, plane, cp, x0, y0, H, W, sp);
     __syncthreads();
-    for (int e = threadIdx.x; e < SGR_LS_IN * SGR_LS_T; e += 256) {
-        const int r = e / SGR_LS_T, q = e - r * SGR_LS_T;
-        float a = 0.f, b = 0.f, d = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float w = g.w[k];
-            a += w * sp[0][r][q + k]; b += w * sp[1][r][q + k]; d += w * sp[2][r][q + k];
-        }
-        hb[0][r][q] = a; hb[1][r][q] = b; hb[2][r][q] = d;
-    }
+    ssim_hpass<3>(threadIdx.x, sp, g, hb);
     __syncthreads();
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int x = x0 + tx, y = y0 + ty;
     if (x >= W || y >= H) return;
-    float a = 0.f, b = 0.f, d = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-        const float w = g.w[k];
-        a += w * hb[0][ty + k][tx]; b += w * hb[1][ty + k][tx]; d += w * hb[2][ty + k][tx];
-    }
+    float f[3];
+    ssim_vpass<3>(hb, g, ty, tx, f);
     const size_t o = (size_t)y * W + x;
     float out = 0.f;
     if (!mask || mask[o]) {
         const float xv = img1[c * plane + o], yv = img2[c * plane + o];
-        out = w_ssim * ((a + 2.f * xv * b + yv * d) * (upstream[0] / (float)cp));
-        if (l1_out != nullptr) {  // fused colour loss: + w_l1 * d l1_loss / d img1  (loss_utils.py:21-37)
-            const float df = xv - yv;
-            const float sg = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
-            out += w_l1 * upstream[0] * sg / l1_out[1];
-        }
+        out = w_ssim * ssim_grad(f[0], f[1], f[2], xv, yv, upstream[0] / (float)cp);
+        // fused colour loss: + w_l1 * d l1_loss / d img1  (loss_utils.py:21-37)
+        if (l1_out != nullptr) out += w_l1 * upstream[0] * l1_sign(xv - yv) / l1_out[1];
     }
     dimg1[c * plane + o] = out;
 }
@@ -176,10 +132,7 @@ sgr_l1_bwd_kernel(int C, size_t plane, const float* __restrict__ a, const float*
     if (i >= (size_t)C * plane) return;
     const size_t p = i % plane;
     float g = 0.f;
-    if (!mask || mask[p]) {
-        const float d = a[i] - b[i];
-        g = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (upstream[0] / out[1]);  // torch: sign(0) = 0
-    }
+    if (!mask || mask[p]) g = l1_sign(a[i] - b[i]) * (upstream[0] / out[1]);
     da[i] = g;
 }
 
@@ -222,11 +175,9 @@ sgr_lidar_err_kernel(int n, const float* __restrict__ depth, const float* __rest
         }
         w.key[i] = key;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
+    wave_sums_to_lds(c, cnt);
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&w.state[0], cnt[0] + cnt[1] + cnt[2] + cnt[3]);  // integers: order-independent
+    if (threadIdx.x == 0) atomicAdd(&w.state[0], lds4_total(cnt));  // integers: order-independent
 }
 __global__ void sgr_lidar_k_kernel(LdWork w, double keep) {
     const uint32_t count = w.state[0];
@@ -285,7 +236,7 @@ __global__ void __launch_bounds__(256)
 sgr_lidar_final_kernel(LdWork w, float* __restrict__ out) {
     __shared__ float lds4[4];
     float a = 0.f;
-    for (int i = threadIdx.x; i < SGR_L1_BLOCKS_; i += 256) a += w.sums[i];
+    for (int i = threadIdx.x; i < SGR_L1_BLOCKS; i += 256) a += w.sums[i];
     const float below = block_sum_256(a, lds4);
     if (threadIdx.x == 0) {
         const uint32_t k = w.state[1];
@@ -312,14 +263,12 @@ sgr_lidar_bwd_kernel(int n, const float* __restrict__ depth, const float* __rest
 void sgr_lidar_select_launch(int n, const LdWork& w, double keep, float* out, hipStream_t stream) {
     sgr_lidar_k_kernel<<<1, 1, 0, stream>>>(w, keep);
     for (int pass = 3; pass >= 0; pass--) {
-        sgr_lidar_hist_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, pass, w);
+        sgr_lidar_hist_kernel<<<SGR_L1_BLOCKS, 256, 0, stream>>>(n, pass, w);
         sgr_lidar_select_kernel<<<1, 1, 0, stream>>>(pass, w);
     }
-    sgr_lidar_sum_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, w);
+    sgr_lidar_sum_kernel<<<SGR_L1_BLOCKS, 256, 0, stream>>>(n, w);
     sgr_lidar_final_kernel<<<1, 256, 0, stream>>>(w, out);
 }
-
-#define SGR_L1_BLOCKS 1024
 
 extern "C" {
 
@@ -331,12 +280,11 @@ size_t sgr_ssim_workspace_floats(int C, int H, int W) {
 int sgr_ssim_forward(int C, int H, int W, const float* img1, const float* img2, const uint8_t* mask, float* out_ssim,
                      float* partials, float* workspace, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!img1 || !img2 || !out_ssim || !workspace) return sgr_set_error(SGR_E_INVALID, "img1, img2, out_ssim and workspace are required");
-    static const SgrGauss11 g = make_window();
     const dim3 grid = tile_grid(C, H, W);
-    if (partials) sgr_ssim_fwd_kernel<true><<<grid, 256, 0, stream>>>(H, W, img1, img2, mask, g, partials, workspace);
-    else sgr_ssim_fwd_kernel<false><<<grid, 256, 0, stream>>>(H, W, img1, img2, mask, g, nullptr, workspace);
+    if (partials) sgr_ssim_fwd_kernel<true><<<grid, 256, 0, stream>>>(H, W, img1, img2, mask, ssim_window(), partials, workspace);
+    else sgr_ssim_fwd_kernel<false><<<grid, 256, 0, stream>>>(H, W, img1, img2, mask, ssim_window(), nullptr, workspace);
     sgr_final_sum_kernel<<<1, 256, 0, stream>>>(workspace, (size_t)grid.x * grid.y * grid.z,
                                                 1.0f / ((float)C * (float)H * (float)W), nullptr, out_ssim, 0);
     SGR_HIP(hipGetLastError());
@@ -346,12 +294,11 @@ int sgr_ssim_forward(int C, int H, int W, const float* img1, const float* img2, 
 int sgr_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const uint8_t* mask,
                       const float* partials, const float* upstream, float* dL_dimg1, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!img1 || !img2 || !partials || !upstream || !dL_dimg1)
         return sgr_set_error(SGR_E_INVALID, "img1, img2, partials, upstream and dL_dimg1 are required");
-    static const SgrGauss11 g = make_window();
-    sgr_ssim_bwd_kernel<<<tile_grid(C, H, W), 256, 0, stream>>>(H, W, C, img1, img2, mask, g, partials, upstream, dL_dimg1,
-                                                                1.0f, 0.0f, nullptr);
+    sgr_ssim_bwd_kernel<<<tile_grid(C, H, W), 256, 0, stream>>>(H, W, C, img1, img2, mask, ssim_window(), partials, upstream,
+                                                                dL_dimg1, 1.0f, 0.0f, nullptr);
     SGR_HIP(hipGetLastError());
     return 0;
 }
@@ -360,12 +307,11 @@ int sgr_color_loss_backward(int C, int H, int W, const float* img1, const float*
                             const float* partials, const float* l1_out, float w_l1, float w_ssim, const float* upstream,
                             float* dL_dimg1, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!img1 || !img2 || !partials || !l1_out || !upstream || !dL_dimg1)
         return sgr_set_error(SGR_E_INVALID, "img1, img2, partials, l1_out, upstream and dL_dimg1 are required");
-    static const SgrGauss11 g = make_window();
-    sgr_ssim_bwd_kernel<<<tile_grid(C, H, W), 256, 0, stream>>>(H, W, C, img1, img2, mask, g, partials, upstream, dL_dimg1,
-                                                                w_ssim, w_l1, l1_out);
+    sgr_ssim_bwd_kernel<<<tile_grid(C, H, W), 256, 0, stream>>>(H, W, C, img1, img2, mask, ssim_window(), partials, upstream,
+                                                                dL_dimg1, w_ssim, w_l1, l1_out);
     SGR_HIP(hipGetLastError());
     return 0;
 }
@@ -378,7 +324,7 @@ size_t sgr_l1_workspace_floats(int C, int H, int W) {
 int sgr_l1_forward(int C, int H, int W, const float* a, const float* b, const uint8_t* mask, float* out, float* workspace,
                    void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!a || !b || !out || !workspace) return sgr_set_error(SGR_E_INVALID, "a, b, out and workspace are required");
     const size_t plane = (size_t)H * W;
     sgr_l1_fwd_kernel<<<SGR_L1_BLOCKS, 256, 0, stream>>>(C, plane, a, b, mask, workspace, workspace + SGR_L1_BLOCKS);
@@ -390,7 +336,7 @@ int sgr_l1_forward(int C, int H, int W, const float* a, const float* b, const ui
 int sgr_l1_backward(int C, int H, int W, const float* a, const float* b, const uint8_t* mask, const float* out,
                     const float* upstream, float* dL_da, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C <= 0 || H <= 0 || W <= 0) return sgr_set_error(SGR_E_INVALID, "C, H, W must be positive");
+    if (const int rc = ls_check_dims(C, H, W)) return rc;
     if (!a || !b || !out || !upstream || !dL_da) return sgr_set_error(SGR_E_INVALID, "a, b, out, upstream and dL_da are required");
     const size_t n = (size_t)C * H * W;
     sgr_l1_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(C, (size_t)H * W, a, b, mask, out, upstream, dL_da);
@@ -430,7 +376,7 @@ int sgr_lidar_depth_forward(int n, const float* depth, const float* acc, const f
     const LdWork w = ld_carve((char*)sgr_align_up((size_t)work, 256), (size_t)n);
     SGR_HIP(hipMemsetAsync(w.hist, 0, 4 * 256 * sizeof(uint32_t), stream));
     SGR_HIP(hipMemsetAsync(w.state, 0, 16 * sizeof(uint32_t), stream));
-    sgr_lidar_err_kernel<<<SGR_L1_BLOCKS_, 256, 0, stream>>>(n, depth, acc, lidar_depth, mask, w);
+    sgr_lidar_err_kernel<<<SGR_L1_BLOCKS, 256, 0, stream>>>(n, depth, acc, lidar_depth, mask, w);
     sgr_lidar_select_launch(n, w, keep, out, stream);
     SGR_HIP(hipGetLastError());
     return 0;

@@ -1,27 +1,12 @@
 // sgr_loss_internal.h -- what sgr_loss.hip (the stand-alone image-space losses) and sgr_frame_loss.hip (all of them in one
-// op) share: the SSIM window and tile geometry, the block reduction, the per-pixel arithmetic of the accumulation and LiDAR
-// terms, and the LiDAR term's radix select, whose kernels live in sgr_loss.hip behind sgr_lidar_select_launch.
+// op) share: the SSIM steps (sgr_ssim.h), the tile grid, the block reduction, the per-pixel arithmetic of the accumulation
+// and LiDAR terms, and the LiDAR term's radix select, whose kernels live in sgr_loss.hip behind sgr_lidar_select_launch.
 #pragma once
 #include <math.h>
 
+#include "../../include/sgr.h"
 #include "sgr_common.h"
-
-#define SGR_LS_T 16           // output tile edge
-#define SGR_LS_R 5            // window radius (window_size 11)
-#define SGR_LS_IN (SGR_LS_T + 2 * SGR_LS_R)  // 26
-
-struct SgrGauss11 { float w[11]; };
-// gaussian(11, 1.5) of loss_utils.py:70-72, evaluated like the reference: exp() in double, float32 tensor, / sum
-static inline SgrGauss11 make_window() {
-    SgrGauss11 g;
-    float v[11], s = 0.f;
-    for (int x = 0; x < 11; x++) {
-        v[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
-        s += v[x];
-    }
-    for (int x = 0; x < 11; x++) g.w[x] = v[x] / s;
-    return g;
-}
+#include "sgr_ssim.h"
 
 static inline dim3 tile_grid(int C, int H, int W) {
     return dim3((W + SGR_LS_T - 1) / SGR_LS_T, (H + SGR_LS_T - 1) / SGR_LS_T, C);
@@ -34,20 +19,20 @@ struct LdWork {
     uint32_t* state;  // [0] count  [1] k  [2] prefix  [3] k remaining  [4] count below threshold  [5] ties
     float* sums;      // [SGR_L1_BLOCKS]
 };
-#define SGR_L1_BLOCKS_ 1024
+#define SGR_L1_BLOCKS 1024  // workgroups of every grid-stride reduction of the family
 static inline LdWork ld_carve(char* base, size_t n) {
     LdWork w;
     char* p = base;
     sgr_carve(p, w.key, n ? n : 1);
     sgr_carve(p, w.hist, 4 * 256);
     sgr_carve(p, w.state, 16);
-    sgr_carve(p, w.sums, SGR_L1_BLOCKS_);
+    sgr_carve(p, w.sums, SGR_L1_BLOCKS);
     return w;
 }
 static inline size_t ld_work_bytes(size_t n) {
     char* base = (char*)4096;
     LdWork w = ld_carve(base, n ? n : 1);
-    return (size_t)((char*)(w.sums + SGR_L1_BLOCKS_) - base) + 512;
+    return (size_t)((char*)(w.sums + SGR_L1_BLOCKS) - base) + 512;
 }
 
 #ifdef __HIPCC__
@@ -56,12 +41,27 @@ static inline size_t ld_work_bytes(size_t n) {
 // out[1] = k, out[2] = threshold, out[3] = weight of the errors equal to the threshold (sgr_loss.h).  Defined in sgr_loss.hip.
 void sgr_lidar_select_launch(int n, const LdWork& w, double keep, float* out, hipStream_t stream);
 
-__device__ __forceinline__ float block_sum_256(float v, float* lds4) {
+static inline int ls_check_dims(int C, int H, int W) {
+    return (C <= 0 || H <= 0 || W <= 0) ? sgr_set_error(SGR_E_INVALID, "C, H, W must be positive") : 0;
+}
+// sum of a 256-lane workgroup (float, or a count): each wave's sum to lds4[wave]; after a barrier, the four in a fixed order
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {  // own function: inside wave_sums_to_lds it moves the reducers' instructions
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ void wave_sums_to_lds(T v, T* lds4) {
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+}
+template <typename T>
+__device__ __forceinline__ T lds4_total(const T* lds4) { return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3]; }
+__device__ __forceinline__ float block_sum_256(float v, float* lds4) {
+    wave_sums_to_lds(v, lds4);
     __syncthreads();
-    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+    return lds4_total(lds4);
 }
 
 // ---- accumulation terms (train.py:106-121); mode: SGR_BCE_SKY 0, SGR_BCE_OBJECT 1 -------------------------------------
@@ -96,7 +96,7 @@ __device__ __forceinline__ void lidar_grad(uint32_t key, const float* __restrict
     ga = 0.f;
     if (wgt > 0.f) {
         const float den = acc + 1e-10f, diff = depth / den - l;
-        const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
+        const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);  // not l1_sign(): the call moves the up * wgt multiply
         const float g = up * wgt * sgn / out[1];
         gd = g / den;
         ga = -g * depth / (den * den);

@@ -1,9 +1,26 @@
 // TEST INFRASTRUCTURE.  Host (x86) build of the __host__ __device__ maths in
-// street_gaussians_amd/csrc/sgr_math.h and sgr_quat.h, so the formulas the gfx950 kernels run can be
-// checked against the oracle without a GPU (tests/test_host_math.py, tests/test_quat_cpu.py).  Built with
-// `hipcc -x hip --cuda-host-only`; never loaded by the product.
+// street_gaussians_amd/csrc/sgr_math.h, sgr_quat.h and sgr_ssim.h, so the formulas the gfx950 kernels run can be
+// checked against the oracle without a GPU (tests/test_host_math.py, tests/test_quat_cpu.py, tests/test_ssim_host_cpu.py).
+// Built with `hipcc -x hip --cuda-host-only`; never loaded by the product.
 #include "../../street_gaussians_amd/csrc/sgr_math.h"
 #include "../../street_gaussians_amd/csrc/sgr_quat.h"
+#include "../../street_gaussians_amd/csrc/sgr_ssim.h"
+
+// forward staging of one lane as sgr_ssim_fwd_kernel does it (the kernels keep theirs: they differ in how they read the mask)
+static void ssim_stage_images(int tid, const float* p1, const float* p2, const unsigned char* mask, int x0, int y0, int H, int W,
+                              SsimHalo& sx, SsimHalo& sy) {
+    for (int e = tid; e < SGR_LS_IN * SGR_LS_IN; e += 256) {
+        const int r = e / SGR_LS_IN, q = e - r * SGR_LS_IN;
+        const int y = y0 + r - SGR_LS_R, x = x0 + q - SGR_LS_R;
+        float a = 0.f, b = 0.f;
+        if (x >= 0 && x < W && y >= 0 && y < H) {
+            const size_t o = (size_t)y * W + x;
+            if (!mask || mask[o]) { a = p1[o]; b = p2[o]; }
+        }
+        sx[r][q] = a;
+        sy[r][q] = b;
+    }
+}
 
 static SgrCam make_cam(const float* view, const float* proj, const float* campos, float tanx, float tany, int W, int H,
                        float mod) {
@@ -187,6 +204,57 @@ void hm_quat_dquat_of_R(int n, int nc, const float* q, const float* G, float* d)
     for (int i = 0; i < n; i++) {
         const Q4 r = nc ? dquat_of_R<true>(qload(q + 4 * i), G + 9 * i) : dquat_of_R(qload(q + 4 * i), G + 9 * i);
         d[4 * i] = r.w; d[4 * i + 1] = r.x; d[4 * i + 2] = r.y; d[4 * i + 3] = r.z;
+    }
+}
+
+// ---- csrc/sgr_ssim.h (tests/test_ssim_host_cpu.py): the steps sgr_ssim_fwd_kernel / sgr_ssim_bwd_kernel run, lane by lane ----
+// mean SSIM of two [C][H][W] images (mask [H][W] or null) and d(mean SSIM)/d img1: per 16x16 tile every step for tid = 0..255
+// in sequence (a loop's end stands for the kernel's barrier).  Own text: the forward staging loop and the final mean.
+void hm_ssim_tiles(int C, int H, int W, const float* img1, const float* img2, const unsigned char* mask, float* partials,
+                   double* ssim, float* grad) {
+    static SsimHalo sx, sy, sp[3];
+    static SsimRows hb[5];
+    const SgrGauss11& g = ssim_window();
+    const size_t plane = (size_t)H * W, cp = (size_t)C * plane;
+    double sum = 0.0;
+    for (int pass = 0; pass < 2; pass++)  // 0: map value and partials of every tile, 1: the gradient from the partial maps
+        for (int c = 0; c < C; c++)
+            for (int y0 = 0; y0 < H; y0 += SGR_LS_T)
+                for (int x0 = 0; x0 < W; x0 += SGR_LS_T) {
+                    for (int tid = 0; tid < 256; tid++) {
+                        if (pass) ssim_stage_partials(tid, partials, c, plane, cp, x0, y0, H, W, sp);
+                        else ssim_stage_images(tid, img1 + c * plane, img2 + c * plane, mask, x0, y0, H, W, sx, sy);
+                    }
+                    for (int tid = 0; tid < 256; tid++) {
+                        if (pass) ssim_hpass<3>(tid, sp, g, hb);
+                        else ssim_hpass5(tid, sx, sy, g, hb);
+                    }
+                    for (int tid = 0; tid < 256; tid++) {
+                        const int tx = tid & 15, ty = tid >> 4, x = x0 + tx, y = y0 + ty;
+                        if (x >= W || y >= H) continue;
+                        const size_t o = c * plane + (size_t)y * W + x;
+                        if (pass) {
+                            float f[3];
+                            ssim_vpass<3>(hb, g, ty, tx, f);
+                            const bool m = !mask || mask[(size_t)y * W + x];
+                            grad[o] = m ? ssim_grad(f[0], f[1], f[2], img1[o], img2[o], 1.0f / (float)cp) : 0.f;
+                        } else {
+                            float m5[5], val, part[3];
+                            ssim_vpass<5>(hb, g, ty, tx, m5);
+                            ssim_point(m5, val, part);
+                            for (int k = 0; k < 3; k++) partials[k * cp + o] = part[k];
+                            sum += val;
+                        }
+                    }
+                }
+    *ssim = sum / (double)cp;
+}
+void hm_ssim_point(int n, const float* m, float* val, float* part) {
+    for (int i = 0; i < n; i++) {
+        float m5[5], p[3];
+        for (int k = 0; k < 5; k++) m5[k] = m[5 * i + k];
+        ssim_point(m5, val[i], p);
+        for (int k = 0; k < 3; k++) part[3 * i + k] = p[k];
     }
 }
 
