@@ -276,28 +276,7 @@ int sgr_sort_pass_count(int end_bit);  // passes (= buffer flips) of a sort on k
 void sgr_launch_tile_sort(int T, const uint2* ranges, uint32_t* vals_in, uint32_t* vals_out, const uint32_t* dkeys,
                           const uint32_t* header, uint32_t* gk0, uint32_t* gk1, hipStream_t s);
 
-// ---- wave / block scan primitives (sgr_scan_sort.hip, sgr_preprocess.hip) ----
-__device__ __forceinline__ uint32_t sgr_wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan of one value per thread over a 256-thread block; returns block total in `total`
-__device__ __forceinline__ uint32_t sgr_block_excl_scan256(uint32_t v, uint32_t* lds4, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t inc = sgr_wave_incl_scan(v, lane);
-    if (lane == 63) lds4[wave] = inc;
-    __syncthreads();
-    const uint32_t w0 = lds4[0], w1 = lds4[1], w2 = lds4[2], w3 = lds4[3];
-    __syncthreads();
-    const uint32_t base = (wave > 0 ? w0 : 0) + (wave > 1 ? w1 : 0) + (wave > 2 ? w2 : 0);
-    total = w0 + w1 + w2 + w3;
-    return base + inc - v;
-}
+// (the wave / workgroup scans and the other device steps of the binning chain: sgr_radix.h)
 
 // XCD-aware workgroup -> tile map.  The dispatcher places workgroup b on XCD b % 8 (observed, used for speed only),
 // and each XCD has a private 4 MiB L2.  A splat's instances live in neighbouring tiles, so neighbouring tiles

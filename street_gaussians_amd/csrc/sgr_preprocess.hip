@@ -7,6 +7,7 @@
 // instance with three 16-byte loads.
 #include "sgr_math.h"
 #include "sgr_launch.h"
+#include "sgr_radix.h"
 
 #include <cstdlib>
 
@@ -498,7 +499,7 @@ sgr_tile_order_kernel(const uint2* __restrict__ ranges, uint32_t T, uint32_t* __
     __shared__ uint32_t smax;
     __shared__ unsigned long long ssum;
     __shared__ uint32_t sw[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     hist[tid] = 0u;
     if (tid == 0) { smax = 0u; ssum = 0ull; }
     __syncthreads();
@@ -526,14 +527,8 @@ sgr_tile_order_kernel(const uint2* __restrict__ ranges, uint32_t T, uint32_t* __
         atomicAdd(&hist[1023u - min(1023u, (uint32_t)((float)len * sc))], 1u);
     }
     __syncthreads();
-    const uint32_t c = hist[tid];
-    const uint32_t inc = sgr_wave_incl_scan(c, lane);
-    if (lane == 63) sw[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; w++) base += sw[w];
-    __syncthreads();
-    hist[tid] = base + inc - c;
+    uint32_t total;
+    hist[tid] = sgr_block_excl_scan<16>(hist[tid], sw, total);
     __syncthreads();
     for (uint32_t t = tid; t < T; t += 1024) {
         const uint32_t len = ranges[t].y - ranges[t].x;

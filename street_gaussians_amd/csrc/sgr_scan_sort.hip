@@ -19,6 +19,7 @@
 //     1.09 vs 0.69 ms): 8 workgroups x 256 CUs publish at the same moment and the look-back walks device-scope words
 //     that live beyond the per-XCD L2s; the launches it removes are cheaper than that.  Kept for the A/B.
 #include "sgr_common.h"
+#include "sgr_radix.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -45,11 +46,8 @@ __global__ void __launch_bounds__(256) sgr_scan_reduce_kernel(const uint32_t* __
     unsigned b = blockIdx.x;
     if (b >= nb) { b -= nb; in = in2; gather = nullptr; block_sums += nb + 1; if (sub) sub += 8 * nb; stride = stride2; }
     const size_t base = (size_t)b * SGR_SCAN_ITEMS + (size_t)threadIdx.x * 8;
-    uint32_t s = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (base + i < n) s += gather ? in[(size_t)gather[base + i] * stride] : in[(base + i) * stride];
-    uint32_t total;
+    uint32_t v[8], total;
+    const uint32_t s = sgr_load8_sum(v, base, n, [&](size_t i) { return gather ? in[(size_t)gather[i] * stride] : in[i * stride]; });
     const uint32_t ex = sgr_block_excl_scan256(s, lds4, total);
     if (threadIdx.x == 0) block_sums[b] = total;
     // (sgr_launch_scan_head) where each 256-element sub-block -- 32 threads' elements -- starts inside this block
@@ -85,21 +83,9 @@ __global__ void __launch_bounds__(256) sgr_scan_final_kernel(const uint32_t* __r
     unsigned b = blockIdx.x;
     if (b >= nb) { b -= nb; in = in2; out = out2; gather = nullptr; block_sums += nb + 1; inclusive = false; }
     const size_t base = (size_t)b * SGR_SCAN_ITEMS + (size_t)threadIdx.x * 8;
-    uint32_t v[8];
-    uint32_t s = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        v[i] = (base + i < n) ? (gather ? in[(size_t)gather[base + i] * stride] : in[(base + i) * stride]) : 0;
-        s += v[i];
-    }
-    uint32_t total;
-    uint32_t run = sgr_block_excl_scan256(s, lds4, total) + block_sums[b];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        if (inclusive) run += v[i];
-        if (base + i < n) out[base + i] = run;
-        if (!inclusive) run += v[i];
-    }
+    uint32_t v[8], total;
+    const uint32_t s = sgr_load8_sum(v, base, n, [&](size_t i) { return gather ? in[(size_t)gather[i] * stride] : in[i * stride]; });
+    sgr_store8_prefix(v, base, n, sgr_block_excl_scan256(s, lds4, total) + block_sums[b], inclusive, out);
 }
 
 // out may alias in.  tmp needs sgr_scan_tmp_count(n) words (twice that with a second sequence); tmp[nblocks] receives
@@ -181,19 +167,9 @@ sgr_sort_rowscan_kernel(uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t*
     uint32_t carry = 0;
     for (uint32_t start = 0; start < nblocks; start += 256 * 8) {
         const uint32_t base = start + threadIdx.x * 8;
-        uint32_t v[8], s = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            v[i] = (base + i < nblocks) ? row[base + i] : 0u;
-            s += v[i];
-        }
-        uint32_t total;
-        uint32_t run = carry + sgr_block_excl_scan256(s, lds4, total);
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            if (base + i < nblocks) row[base + i] = run;
-            run += v[i];
-        }
+        uint32_t v[8], total;
+        const uint32_t s = sgr_load8_sum(v, base, nblocks, [&](uint32_t i) { return row[i]; });
+        sgr_store8_prefix(v, base, nblocks, carry + sgr_block_excl_scan256(s, lds4, total), false, row);
         carry += total;
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
@@ -225,7 +201,6 @@ sgr_sort_scatter_kernel(const K* __restrict__ kin, const uint32_t* __restrict__ 
                         uint32_t pass_tag, const uint2* __restrict__ aux_in, uint2* __restrict__ aux_out, int aux16,
                         const uint32_t* __restrict__ dev_n) {
     constexpr int NB = 1 << BITS;
-    constexpr int BPT = NB > 256 ? NB / 256 : 1;  // bins per thread in the prefix section (9-bit digits: 2)
     static_assert(!(ONE && NB > 256), "the one-sweep form has one status word per thread");
     constexpr uint32_t ITEMS = 256u * IPT;
     __shared__ uint32_t cnt[4][NB];    // per wave: count of each digit, then its block-local start for that wave
@@ -275,25 +250,7 @@ sgr_sort_scatter_kernel(const K* __restrict__ kin, const uint32_t* __restrict__ 
     for (int s = 0; s < IPT; s++) {
         const bool valid = base + s * 64 + lane < n;
         const uint32_t d = (uint32_t)(key[s] >> shift) & (uint32_t)(NB - 1);
-        // the lanes that share this lane's digit: per bit, keep the lanes whose bit equals mine -- m &= ballot XNOR (my bit
-        // spread over the word).  On 32-bit halves with v_bfe_i32 / v_xor / v_and: a `bit ? bal : ~bal` select compiles to
-        // v_cndmask on VCC, 23 cycles per wave instruction back to back on gfx950 (profiles/r5/valu_rates2.jsonl)
-        const uint64_t vm = __builtin_amdgcn_ballot_w64(valid);
-        uint32_t mlo = (uint32_t)vm, mhi = (uint32_t)(vm >> 32);
-#pragma unroll
-        for (int b = 0; b < BITS; b++) {
-            const int y = __builtin_amdgcn_sbfe((int)d, b, 1);  // 0 or -1
-            const uint64_t bal = __builtin_amdgcn_ballot_w64(y != 0);
-            mlo &= ~((uint32_t)bal ^ (uint32_t)y);
-            mhi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)y);
-        }
-        const uint32_t prefix = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));  // set bits of m below this lane
-        // every lane of the group reads the wave's counter of the digit, its lowest lane moves it on by the group's size
-        const uint32_t prev = valid ? cnt[wave][d] : 0u;
-        __builtin_amdgcn_wave_barrier();
-        if (valid && prefix == 0) cnt[wave][d] = prev + (uint32_t)(__builtin_popcount(mlo) + __builtin_popcount(mhi));
-        rnk[s] = prev + prefix;
-        __builtin_amdgcn_wave_barrier();
+        rnk[s] = sgr_ballot_rank<BITS>(cnt[wave], d, valid);
     }
     __syncthreads();
     if constexpr (!ONE) {
@@ -302,108 +259,50 @@ sgr_sort_scatter_kernel(const K* __restrict__ kin, const uint32_t* __restrict__ 
         // bins of a lane are prefixed in order.  gbase = where this block's keys of the digit start in the output
         // (keys of lower digits anywhere + keys of the digit in earlier blocks), lstart / cnt[w] = where they start in LDS.
         if (wave == 0) {
-            uint32_t c[BPL][4], tot[BPL];
-            uint32_t sum_t = 0, sum_g = 0;
+            uint32_t c[BPL][4], sum_g = 0;
+            const uint32_t sum_t = sgr_bin_counts<4, NB, BPL>(cnt, lane, c);
 #pragma unroll
-            for (int j = 0; j < BPL; j++) {
-                const int bin = lane * BPL + j;
-#pragma unroll
-                for (int w = 0; w < 4; w++) c[j][w] = bin < NB ? cnt[w][bin] : 0u;
-                tot[j] = c[j][0] + c[j][1] + c[j][2] + c[j][3];
-                sum_t += tot[j];
-                sum_g += pre_total[j];
-            }
+            for (int j = 0; j < BPL; j++) sum_g += pre_total[j];
             uint32_t g = sgr_wave_incl_scan(sum_g, lane) - sum_g;
-            uint32_t ls = sgr_wave_incl_scan(sum_t, lane) - sum_t;
-#pragma unroll
-            for (int j = 0; j < BPL; j++) {
-                const int bin = lane * BPL + j;
-                if (bin < NB) {
-                    gbase[bin] = pre_before[j] + g;
-                    lstart[bin] = ls;
-                    cnt[0][bin] = ls;
-                    cnt[1][bin] = ls + c[j][0];
-                    cnt[2][bin] = ls + c[j][0] + c[j][1];
-                    cnt[3][bin] = ls + c[j][0] + c[j][1] + c[j][2];
-                }
+            const uint32_t ls = sgr_wave_incl_scan(sum_t, lane) - sum_t;
+            sgr_bin_starts<4, NB, BPL>(cnt, lane, c, ls, [&](int bin, int j, uint32_t start) {
+                gbase[bin] = pre_before[j] + g;
+                lstart[bin] = start;
                 g += pre_total[j];
-                ls += tot[j];
-            }
-        }
-    } else
-    if constexpr (BPT == 1) {
-        const bool bin = tid < NB;
-        const uint32_t c0 = bin ? cnt[0][tid] : 0u, c1 = bin ? cnt[1][tid] : 0u, c2 = bin ? cnt[2][tid] : 0u,
-                       c3 = bin ? cnt[3][tid] : 0u;
-        uint32_t all;
-        // digit base over the whole array (contains a barrier), then the block-local digit starts (another scan)
-        uint32_t before = 0;  // keys of digit `tid` in the blocks before this one
-        if (ONE) {
-            const unsigned long long tag = (unsigned long long)pass_tag << 56;
-            const uint32_t c = c0 + c1 + c2 + c3;
-            unsigned long long* mine = status + (size_t)block * 256 + tid;
-            __hip_atomic_store(mine, tag | (block == 0 ? SGR_OS_PREFIX : SGR_OS_AGG) | c, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            unsigned long long sum = 0;
-            uint32_t spins = 0;
-            for (uint32_t pb = block; pb > 0;) {
-                const unsigned long long w = __hip_atomic_load(status + (size_t)(pb - 1) * 256 + tid, __ATOMIC_RELAXED,
-                                                               __HIP_MEMORY_SCOPE_AGENT);
-                if ((w >> 56) != pass_tag) {  // not published yet
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > (1u << 22)) { atomicOr(err, 1u); break; }
-                    continue;
-                }
-                sum += w & SGR_OS_VALUE;
-                if (w & SGR_OS_PREFIX) break;
-                pb--;
-            }
-            if (block > 0)
-                __hip_atomic_store(mine, tag | SGR_OS_PREFIX | (sum + c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            before = (uint32_t)sum;
-        } else if (bin) {
-            before = hist_scanned[(size_t)tid * nblocks + block];
-        }
-        const uint32_t g = before + sgr_block_excl_scan256(bin ? totals[tid] : 0u, lds4, all);
-        const uint32_t ls = sgr_block_excl_scan256(c0 + c1 + c2 + c3, lds4, all);
-        if (bin) {
-            gbase[tid] = g;
-            lstart[tid] = ls;
-            cnt[0][tid] = ls;
-            cnt[1][tid] = ls + c0;
-            cnt[2][tid] = ls + c0 + c1;
-            cnt[3][tid] = ls + c0 + c1 + c2;
+            });
         }
     } else {
-        // more bins than threads (9-bit digits): every thread owns BPT CONSECUTIVE bins, the two block scans run over the
-        // threads' sums and the bins of a thread are prefixed in order
-        uint32_t c[BPT][4], tot[BPT], gt[BPT], before[BPT];
-        uint32_t sum_t = 0, sum_g = 0, all;
-#pragma unroll
-        for (int j = 0; j < BPT; j++) {
-            const int bin = tid * BPT + j;
-#pragma unroll
-            for (int w = 0; w < 4; w++) c[j][w] = cnt[w][bin];
-            tot[j] = c[j][0] + c[j][1] + c[j][2] + c[j][3];
-            gt[j] = totals[bin];
-            before[j] = hist_scanned[(size_t)bin * nblocks + block];
-            sum_t += tot[j];
-            sum_g += gt[j];
+        // one sweep: thread d owns digit d.  Its count of this block is published and the predecessors' are looked back
+        // over; then the digit base over the whole array (a block scan: contains a barrier) and the block-local digit
+        // starts (another one)
+        uint32_t c[1][4], all;
+        const uint32_t sum_t = sgr_bin_counts<4, NB, 1>(cnt, tid, c);
+        const unsigned long long tag = (unsigned long long)pass_tag << 56;
+        unsigned long long* mine = status + (size_t)block * 256 + tid;
+        __hip_atomic_store(mine, tag | (block == 0 ? SGR_OS_PREFIX : SGR_OS_AGG) | sum_t, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        unsigned long long sum = 0;  // keys of digit `tid` in the blocks before this one
+        uint32_t spins = 0;
+        for (uint32_t pb = block; pb > 0;) {
+            const unsigned long long w = __hip_atomic_load(status + (size_t)(pb - 1) * 256 + tid, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT);
+            if ((w >> 56) != pass_tag) {  // not published yet
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > (1u << 22)) { atomicOr(err, 1u); break; }
+                continue;
+            }
+            sum += w & SGR_OS_VALUE;
+            if (w & SGR_OS_PREFIX) break;
+            pb--;
         }
-        uint32_t g = sgr_block_excl_scan256(sum_g, lds4, all);
-        uint32_t ls = sgr_block_excl_scan256(sum_t, lds4, all);
-#pragma unroll
-        for (int j = 0; j < BPT; j++) {
-            const int bin = tid * BPT + j;
-            gbase[bin] = before[j] + g;
-            lstart[bin] = ls;
-            cnt[0][bin] = ls;
-            cnt[1][bin] = ls + c[j][0];
-            cnt[2][bin] = ls + c[j][0] + c[j][1];
-            cnt[3][bin] = ls + c[j][0] + c[j][1] + c[j][2];
-            g += gt[j];
-            ls += tot[j];
-        }
+        if (block > 0)
+            __hip_atomic_store(mine, tag | SGR_OS_PREFIX | (sum + sum_t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t g = (uint32_t)sum + sgr_block_excl_scan256(tid < NB ? totals[tid] : 0u, lds4, all);
+        const uint32_t ls = sgr_block_excl_scan256(sum_t, lds4, all);
+        sgr_bin_starts<4, NB, 1>(cnt, tid, c, ls, [&](int bin, int, uint32_t start) {
+            gbase[bin] = g;
+            lstart[bin] = start;
+        });
     }
     __syncthreads();
 #pragma unroll

@@ -17,8 +17,8 @@
 // the device: sgr_test_lds_atomic_order, tests/test_gpu_primitives.py; end to end by the equal-depth cases of
 // tests/test_gpu_tile_sort.py).  Measured on MI355X (profiles/r6/ab_tile_sort.md), the stage at 4.8 M / 7.8 M / 28 M
 // instances: 65 / 88 / 295 us -- bound by the LDS atomic unit, ~2.5 clocks per lane: passes x R x 2.5 / 256 CUs.  The
-// alternatives built and measured at 4.8 M: a wave64 ballot match instead of the atomic (-DSGR_TS_ATOMIC=0: 9 ballots leave
-// the lanes sharing the digit, the group's lowest lane advances the counter) 76 us, 93 us with its select on VCC; atomics on
+// alternatives built and measured at 4.8 M: a wave64 ballot match instead of the atomic (-DSGR_TS_ATOMIC=0: sgr_ballot_rank
+// of sgr_radix.h, the ranking of the global sort's scatter, with 9 ballots) 76 us, 93 us with its select on VCC; atomics on
 // even and ballots on odd steps (-DSGR_TS_MIX=1) 68 us; a histogram atomic + a ranking atomic per key 73 us; workgroup-wide
 // two-sweep passes with barriers 137 us.
 //   lists of up to 1024 entries   one WAVE per tile (four tiles per workgroup), no barriers;
@@ -26,6 +26,7 @@
 //   beyond                        the same passes over a ping-pong in HBM (the tile's own slices of the binning buffer).
 #include "sgr_common.h"
 #include "sgr_launch.h"
+#include "sgr_radix.h"
 
 #define SGR_TS_BITS 9
 #define SGR_TS_NB (1 << SGR_TS_BITS)
@@ -41,37 +42,13 @@
 #define SGR_TS_ATOMIC 1  // 1: rank with one returning LDS atomic per key (the fastest form measured); 0: wave64 ballot match
 #endif
 // Rank of this lane's key among the wave's keys of digit d seen so far (earlier steps + lower lanes), and the counter moved on
-// by the step's count.  Every lane of the wave calls it (valid = holds a key).  Wave64 ballot match: BITS ballots leave the set
-// of lanes that share the digit; all of them read the counter, the lowest one writes it back advanced by the group's size.
+// by the step's count.  Every lane of the wave calls it (valid = holds a key).
 #ifndef SGR_TS_MIX
 #define SGR_TS_MIX 0  // 1 (with SGR_TS_ATOMIC=0): even steps rank with the returning LDS atomic, odd steps with the ballot match -- both advance the same
 #endif                // counters, and the two forms run on different pipes of the CU (LDS atomic unit / VALU)
-__device__ __forceinline__ uint32_t sgr_ts_count_rank(uint32_t* c, uint32_t d, bool valid, int lane, bool atomic_step) {
-#if SGR_TS_ATOMIC
-    (void)lane; (void)atomic_step;
-    return valid ? atomicAdd(&c[d], 1u) : 0u;
-#else
-    if (SGR_TS_MIX && atomic_step) return valid ? atomicAdd(&c[d], 1u) : 0u;
-    // the lanes that share this lane's digit: per bit, keep the lanes whose bit equals mine -- m &= ballot XNOR (my bit spread
-    // over the word).  Written on 32-bit halves with v_bfe_i32 / v_xnor / v_and: a `bit ? bal : ~bal` select compiles to
-    // v_cndmask on VCC, 23 cycles per wave instruction back to back on gfx950 (profiles/r5/valu_rates2.jsonl)
-    const uint64_t vm = __builtin_amdgcn_ballot_w64(valid);
-    uint32_t mlo = (uint32_t)vm, mhi = (uint32_t)(vm >> 32);
-#pragma unroll
-    for (int b = 0; b < SGR_TS_BITS; b++) {
-        const int y = __builtin_amdgcn_sbfe((int)d, b, 1);  // 0 or -1
-        const uint64_t bal = __builtin_amdgcn_ballot_w64(y != 0);  // (lanes without a key are not in vm: their bit does not matter)
-        mlo &= ~((uint32_t)bal ^ (uint32_t)y);
-        mhi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)y);
-    }
-    const uint32_t prefix = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));  // set bits of m below this lane
-    const uint64_t m = ((uint64_t)mhi << 32) | mlo;
-    const uint32_t before = valid ? c[d] : 0u;
-    __builtin_amdgcn_wave_barrier();
-    if (valid && prefix == 0) c[d] = before + (uint32_t)__popcll(m);
-    __builtin_amdgcn_wave_barrier();
-    return before + prefix;
-#endif
+__device__ __forceinline__ uint32_t sgr_ts_count_rank(uint32_t* c, uint32_t d, bool valid, bool atomic_step) {
+    if (SGR_TS_ATOMIC || (SGR_TS_MIX && atomic_step)) return valid ? atomicAdd(&c[d], 1u) : 0u;
+    return sgr_ballot_rank<SGR_TS_BITS>(c, d, valid);
 }
 
 __device__ __forceinline__ int sgr_ts_npass(const uint32_t* header) {
@@ -122,23 +99,14 @@ sgr_tile_sort_wave_kernel(int T, const uint2* __restrict__ ranges, const uint32_
         for (int s = 0; s < SGR_TS_STEPS_W; s++) {
             rnk[s] = 0u;
             if (s * 64u < n)  // wave-uniform
-                rnk[s] = sgr_ts_count_rank(c, (key[s] >> shift) & (SGR_TS_NB - 1), s * 64u + lane < n, lane, (s & 1) == 0);
+                rnk[s] = sgr_ts_count_rank(c, (key[s] >> shift) & (SGR_TS_NB - 1), s * 64u + lane < n, (s & 1) == 0);
         }
         __builtin_amdgcn_wave_barrier();
         {   // counts -> first slots: lane l owns bins [l * NB / 64, (l + 1) * NB / 64)
             constexpr int BPL = SGR_TS_NB / 64;
-            uint32_t cc[BPL], sum = 0;
-#pragma unroll
-            for (int j = 0; j < BPL; j++) {
-                cc[j] = c[lane * BPL + j];
-                sum += cc[j];
-            }
-            uint32_t run = sgr_wave_incl_scan(sum, lane) - sum;
-#pragma unroll
-            for (int j = 0; j < BPL; j++) {
-                c[lane * BPL + j] = run;
-                run += cc[j];
-            }
+            uint32_t cc[BPL][1];
+            const uint32_t sum = sgr_bin_counts<1, SGR_TS_NB, BPL>(&c, lane, cc);
+            sgr_bin_starts<1, SGR_TS_NB, BPL>(&c, lane, cc, sgr_wave_incl_scan(sum, lane) - sum);
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -164,52 +132,13 @@ sgr_tile_sort_wave_kernel(int T, const uint2* __restrict__ ranges, const uint32_
 }
 
 // ---- one workgroup per tile --------------------------------------------------------------------------------------------
-template <int WAVES>
-__device__ __forceinline__ uint32_t sgr_ts_block_excl_scan(uint32_t v, uint32_t* sw, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t inc = sgr_wave_incl_scan(v, lane);
-    if (lane == 63) sw[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) {
-        const uint32_t t = sw[w];
-        base += w < wave ? t : 0u;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
-}
-
-// cnt[w][d] (per-wave digit counts) -> the first slot of digit d for wave w: digits ascending, waves ascending inside a digit
+// cnt[w][d] (per-wave digit counts) -> the first slot of digit d for wave w: thread d owns digit d (16 waves: half of them idle)
 template <int WAVES>
 __device__ __forceinline__ void sgr_ts_starts(uint32_t (*cnt)[SGR_TS_NB], uint32_t* sw) {
-    constexpr int THREADS = 64 * WAVES, BPT = SGR_TS_NB > THREADS ? SGR_TS_NB / THREADS : 1;
-    const int tid = threadIdx.x;
-    uint32_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < BPT; j++) {
-        const int bin = tid * BPT + j;
-        if (bin < SGR_TS_NB) {
-#pragma unroll
-            for (int w = 0; w < WAVES; w++) sum += cnt[w][bin];
-        }
-    }
-    uint32_t total;
-    uint32_t run = sgr_ts_block_excl_scan<WAVES>(sum, sw, total);
-#pragma unroll
-    for (int j = 0; j < BPT; j++) {
-        const int bin = tid * BPT + j;
-        if (bin < SGR_TS_NB) {
-#pragma unroll
-            for (int w = 0; w < WAVES; w++) {
-                const uint32_t t = cnt[w][bin];
-                cnt[w][bin] = run;
-                run += t;
-            }
-        }
-    }
+    static_assert(64 * WAVES >= SGR_TS_NB, "one bin per thread");
+    uint32_t c[1][WAVES], total;
+    const uint32_t sum = sgr_bin_counts<WAVES, SGR_TS_NB, 1>(cnt, threadIdx.x, c);
+    sgr_bin_starts<WAVES, SGR_TS_NB, 1>(cnt, threadIdx.x, c, sgr_block_excl_scan<WAVES>(sum, sw, total));
 }
 
 // BIG = false: 8 waves, lists of SGR_TS_WAVE_CAP + 1 .. SGR_TS_MED_CAP entries; BIG = true: 16 waves, everything longer (in LDS
@@ -254,7 +183,7 @@ sgr_tile_sort_block_kernel(const uint2* __restrict__ ranges, uint32_t* vals_in, 
             for (int s = 0; s < SGR_TS_STEPS; s++) {
                 rnk[s] = 0u;
                 if (s0 + s * 64 < s1)  // wave-uniform
-                    rnk[s] = sgr_ts_count_rank(cnt[wave], (key[s] >> shift) & (SGR_TS_NB - 1), s0 + s * 64 + lane < s1, lane, (s & 1) == 0);
+                    rnk[s] = sgr_ts_count_rank(cnt[wave], (key[s] >> shift) & (SGR_TS_NB - 1), s0 + s * 64 + lane < s1, (s & 1) == 0);
             }
             __syncthreads();
             sgr_ts_starts<WAVES>(cnt, sw);
@@ -298,7 +227,7 @@ sgr_tile_sort_block_kernel(const uint2* __restrict__ ranges, uint32_t* vals_in, 
             for (uint32_t base = s0; base < s1; base += 64) {
                 const uint32_t i = base + lane;
                 const bool valid = i < s1;
-                const uint32_t r = sgr_ts_count_rank(cnt[wave], ((valid ? ks[i] : 0u) >> shift) & (SGR_TS_NB - 1), valid, lane, true);
+                const uint32_t r = sgr_ts_count_rank(cnt[wave], ((valid ? ks[i] : 0u) >> shift) & (SGR_TS_NB - 1), valid, true);
                 if (valid) rk[i] = r;
             }
             __syncthreads();

@@ -1,10 +1,12 @@
 // TEST INFRASTRUCTURE.  Host (x86) build of the __host__ __device__ maths in
-// street_gaussians_amd/csrc/sgr_math.h, sgr_quat.h and sgr_ssim.h, so the formulas the gfx950 kernels run can be
-// checked against the oracle without a GPU (tests/test_host_math.py, tests/test_quat_cpu.py, tests/test_ssim_host_cpu.py).
+// street_gaussians_amd/csrc/sgr_math.h, sgr_quat.h, sgr_ssim.h and sgr_radix.h, so the formulas the gfx950 kernels run can be
+// checked against the oracle without a GPU (tests/test_host_math.py, tests/test_quat_cpu.py, tests/test_ssim_host_cpu.py,
+// tests/test_radix_host_cpu.py).
 // Built with `hipcc -x hip --cuda-host-only`; never loaded by the product.
 #include "../../street_gaussians_amd/csrc/sgr_math.h"
 #include "../../street_gaussians_amd/csrc/sgr_quat.h"
 #include "../../street_gaussians_amd/csrc/sgr_ssim.h"
+#include "../../street_gaussians_amd/csrc/sgr_radix.h"
 
 // forward staging of one lane as sgr_ssim_fwd_kernel does it (the kernels keep theirs: they differ in how they read the mask)
 static void ssim_stage_images(int tid, const float* p1, const float* p2, const unsigned char* mask, int x0, int y0, int H, int W,
@@ -34,6 +36,26 @@ static SgrCam make_cam(const float* view, const float* proj, const float* campos
     c.gx = (W + 15) / 16; c.gy = (H + 15) / 16;
     c.scale_modifier = mod;
     return c;
+}
+
+// ---- csrc/sgr_radix.h (tests/test_radix_host_cpu.py): digit counts -> first slots as the radix kernels run it, owner by owner.
+// cnt [waves][bins] in place; the exclusive scan of the owners' sums (the kernels' wave / block scan) is this harness's own.
+// first[d] = what per_bin reports for digit d (0xffffffff where it was not called).  Returns 0 for a (waves, bins, bins per
+// owner) no kernel instantiates.
+template <int WAVES, int NB, int BPO>
+static int bin_starts_run(int owners, unsigned* cnt_flat, unsigned* first) {
+    auto cnt = reinterpret_cast<uint32_t (*)[NB]>(cnt_flat);
+    auto c = new uint32_t[owners][BPO][WAVES];
+    uint32_t* sum = new uint32_t[owners];
+    for (int o = 0; o < owners; o++) sum[o] = sgr_bin_counts<WAVES, NB, BPO>(cnt, o, c[o]);
+    uint32_t run = 0;
+    for (int o = 0; o < owners; o++) {
+        sgr_bin_starts<WAVES, NB, BPO>(cnt, o, c[o], run, [&](int bin, int j, uint32_t start) { (void)j; first[bin] = start; });
+        run += sum[o];
+    }
+    delete[] c;
+    delete[] sum;
+    return 1;
 }
 
 extern "C" {
@@ -256,6 +278,18 @@ void hm_ssim_point(int n, const float* m, float* val, float* part) {
         ssim_point(m5, val[i], p);
         for (int k = 0; k < 3; k++) part[3 * i + k] = p[k];
     }
+}
+
+// ---- csrc/sgr_radix.h (tests/test_radix_host_cpu.py): bin_starts_run above, per (waves, bins, bins per owner) of a kernel ----
+int hm_bin_starts(int waves, int bins, int owners, int bpo, unsigned* cnt, unsigned* first) {
+    for (int d = 0; d < bins; d++) first[d] = 0xffffffffu;
+#define HM_BS(W, NB, BPO) if (waves == W && bins == NB && bpo == BPO) return bin_starts_run<W, NB, BPO>(owners, cnt, first)
+    HM_BS(4, 32, 1); HM_BS(4, 64, 1); HM_BS(4, 128, 2); HM_BS(4, 256, 4); HM_BS(4, 512, 8);  // the scatter, wave 0's lanes
+    HM_BS(4, 256, 1);                                                                         // its one-sweep form, 256 threads
+    HM_BS(1, 512, 8);                                                                         // one wave per tile
+    HM_BS(8, 512, 1); HM_BS(16, 512, 1);                                                      // one workgroup per tile
+#undef HM_BS
+    return 0;
 }
 
 void hm_div_by_seed(int n, const float* a, const float* b, const float* seed, float* q) {

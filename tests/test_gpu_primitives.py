@@ -69,12 +69,17 @@ def test_sort_pairs_stable(n, end_bit, dup, one_sweep, sort_mode):
 
 
 # max_bits 9: digits of NINE bits (512 bins, two per thread in the scatter's prefix section) -- the forward's depth sort runs
-# on 27 key bits in three such passes below 750 k Gaussians and in four 7-bit passes above
+# on 27 key bits in three such passes below 750 k Gaussians and in four 7-bit passes above.
+# The last four: the scatter instantiations no other case reaches -- digit width = ceil(end_bit / passes), 16 keys per
+# thread from 3 M 32-bit keys: 6 bits x 8 keys (4097 = 2 * 2048 + 1), then 5, 6 and 7 bits x 16 keys with a ragged last block
+# (3 000 001 = 732 * 4096 + 1729)
 @pytest.mark.parametrize("n,end_bit,dup,max_bits", [(1, 14, False, 8), (4097, 14, True, 8), (2_500_000, 14, True, 8),
                                                     (1_000_000, 32, False, 8), (20_000_003, 15, False, 8),
                                                     (1_000_001, 27, False, 8), (1_000_001, 27, False, 9),
                                                     (300_000, 27, True, 9), (70_001, 18, True, 9), (5000, 9, False, 9),
-                                                    (5000, 9, False, 8), (40_000, 32, False, 9)])
+                                                    (5000, 9, False, 8), (40_000, 32, False, 9),
+                                                    (4097, 11, True, 8), (3_000_001, 10, True, 8),
+                                                    (3_000_001, 12, False, 8), (3_000_001, 14, True, 8)])
 @pytest.mark.parametrize("one_sweep", [False, True])
 def test_sort_pairs32_stable(n, end_bit, dup, max_bits, one_sweep, sort_mode):
     L, check = _lib()

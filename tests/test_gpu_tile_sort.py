@@ -2,9 +2,10 @@
 emission, stable tile sort, one radix sort by depth per tile in LDS) must produce the SAME sorted lists as the default chain
 (depth pre-sort of the Gaussians, depth-order emission, stable tile sort) -- which the rest of the suite holds entry for
 entry against the oracle and the reference's kernels (rasterizer_impl.cu:70-138,286-321): keys, point_list, ranges,
-n_contrib, every image and every gradient bit for bit.  Covers the three code paths of the kernel (one-wave rank sort for
-lists up to 64 entries, 256-thread LDS sort up to 2048, 1024-thread LDS sort up to 7168, the HBM ping-pong beyond), equal
-depths (the tie order is ascending Gaussian id), far depths (32-bit keys) and the reference's tile rects."""
+n_contrib, every image and every gradient bit for bit.  Covers the code paths of the kernels (one wave per tile for lists
+up to 1024 entries, SGR_TS_WAVE_CAP; the 512-thread LDS sort up to 4096, SGR_TS_MED_CAP; the 1024-thread LDS sort up to
+8192, SGR_TS_BIG_CAP; the HBM ping-pong beyond), equal depths (the tie order is ascending Gaussian id), far depths (32-bit
+keys) and the reference's tile rects."""
 import numpy as np
 import pytest
 import torch
@@ -46,13 +47,13 @@ def _same(a, b, label):
 
 
 def _scene(name):
-    if name == "mid":  # a few hundred entries per tile: the 256-thread LDS sort and the one-wave rank sort
+    if name == "mid":  # a few hundred entries per tile: one wave per tile
         cam = syn.make_camera(480, 320, fx=512.5, yaw_deg=2.0)
         return cam, syn.make_scene(40000, cam, S=3, seed=3), 3
-    if name == "fat_tiles":  # 12 x 8 tiles, ~60 k splats of ~10 px: thousands of entries per tile -> the 1024-thread LDS sort
+    if name == "fat_tiles":  # 12 x 8 tiles, ~60 k splats of ~10 px: thousands of entries per tile -> the workgroup-per-tile LDS sorts
         cam = syn.make_camera(192, 128, fx=200.0)
         return cam, syn.make_scene(60000, cam, S=0, seed=5, scale_px=0.02, zmin=1.0, zmax=20.0), 0
-    if name == "beyond_lds":  # > 7168 entries in a tile: the HBM ping-pong
+    if name == "beyond_lds":  # the longest lists: past 8192 entries (SGR_TS_BIG_CAP) a tile takes the HBM ping-pong
         cam = syn.make_camera(64, 48, fx=70.0)
         return cam, syn.make_scene(50000, cam, S=0, seed=6, scale_px=0.03, zmin=1.0, zmax=12.0), 0
     if name == "equal_depths":  # a wall of splats at a handful of depths: almost every comparison is a tie
