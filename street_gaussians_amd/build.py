@@ -23,7 +23,7 @@ SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_
 # `python tools/build_variant.py <name> -DSGR_WITH_VARIANTS=1` builds a library that contains them (sgr_has_variants() = 1),
 # and the tests of those paths run only against such a build.
 VARIANT_SOURCES = [os.path.join("variants", "sgr_blend_bwd_sw.hip")]
-HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_ssim.h", "sgr_math.h", "sgr_launch.h", "sgr_tile_walk.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", "sgr_quat.h", "sgr_radix.h", os.path.join("..", "..", "include", "sgr.h"),
+HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_ssim.h", "sgr_math.h", "sgr_launch.h", "sgr_tile_walk.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", "sgr_quat.h", "sgr_radix.h", "sgr_pergauss.h", os.path.join("..", "..", "include", "sgr.h"),
            os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h"),

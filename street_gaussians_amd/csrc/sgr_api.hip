@@ -16,6 +16,7 @@
 #include "../../include/sgr_layers.h"
 #include "../../include/sgr_object_alpha.h"
 #include "sgr_launch.h"  // every launcher of the kernel translation units
+#include "sgr_pergauss.h"  // the packed tile rect word (sgr_export_kernel)
 
 static thread_local std::string g_err;
 
@@ -1186,10 +1187,10 @@ __global__ void sgr_export_kernel(int which, int P, SgrGeomView gv, void* dst) {
             const uint2 a = gv.header[6] == 3u ? make_uint2(gv.aux_ref[i].x, gv.aux_ref[i].y) : gv.aux[i];
             // (a masked rect of at most 64 tiles does not store its height: the highest set bit of the mask gives the last row
             // that matters, and rows above it hold no emitted tile)
-            const uint32_t x0 = a.y & 1023u, y0 = (a.y >> 10) & 1023u, w = (a.y >> 20) & 1023u;
-            uint32_t h = w ? a.x / w : 0u;
-            if (a.y & SGR_RECT_MASKED) h = (63u - (uint32_t)__clzll((long long)gv.tmask[i])) / w + 1u;
-            ((uint4*)dst)[i] = a.x ? make_uint4(x0, y0, x0 + w, y0 + h) : make_uint4(0u, 0u, 0u, 0u);
+            const SgrRect r = sgr_unpack_rect(a.y);
+            uint32_t h = r.w ? a.x / r.w : 0u;
+            if (r.masked) h = (63u - (uint32_t)__clzll((long long)gv.tmask[i])) / r.w + 1u;
+            ((uint4*)dst)[i] = a.x ? make_uint4(r.x0, r.y0, r.x0 + r.w, r.y0 + h) : make_uint4(0u, 0u, 0u, 0u);
         } break;
         case 18:  // tile mask (0 = every tile of the rect is emitted)
             ((uint64_t*)dst)[i] = (gv.header[6] != 3u && gv.aux[i].x && (gv.aux[i].y & SGR_RECT_MASKED)) ? gv.tmask[i] : 0ull;

@@ -40,6 +40,16 @@
 #define SGR_DEPTH_KEY_BITS 27           // key bits the depth sort looks at unless a depth >= 0.2 * 2^16 shows up
 #define SGR_LOG2E 1.4426950408889634f
 
+// One expression text in two contraction flavours, inside `template <bool NC = false>` (sgr_quat.h, sgr_pergauss.h):
+// `#pragma clang fp contract` is lexical, so a helper keeps the state of the place where it is defined, not of its caller;
+// f<true> evaluates operation by operation, f<> takes the state of the including translation unit.
+#define SGR_FP_FLAVOURS(...)                                  \
+    if constexpr (NC) {                                       \
+        _Pragma("clang fp contract(off)") __VA_ARGS__         \
+    } else {                                                  \
+        __VA_ARGS__                                           \
+    }
+
 struct SgrGeomView {
     float4* rec;  // [4P]
     uint2* aux;               // per Gaussian {tiles_touched, packed tile rect}; {0, 0} when culled.  Rect word: x0 | y0 << 10 |

@@ -7,7 +7,7 @@
 // written exactly once (zeros for culled Gaussians and for SH coefficients above the active degree),
 // so the caller allocates the gradient tensors uninitialised instead of the reference's eleven
 // torch::zeros (rasterize_points.cu:166-176).
-#include "sgr_math.h"
+#include "sgr_pergauss.h"
 #include "sgr_launch.h"
 
 #include <cstdlib>
@@ -84,6 +84,12 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
     float (&acc)[4 * NV] = accs[0];  // (the two-in-flight forms: one Gaussian per quad)
     const int idx = idx0;
     const uint32_t n = ns[0], u0 = u0s[0];
+    auto add_row = [&](const float4 (&t)[NV]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k4 = 0; k4 < NV; k4++) {
+            acc[4 * k4] += t[k4].x; acc[4 * k4 + 1] += t[k4].y; acc[4 * k4 + 2] += t[k4].z; acc[4 * k4 + 3] += t[k4].w;
+        }
+    };
     if constexpr (G > 1 || R != 2) {
         // Flags first, rows together: a lane asks for the flag bytes of its next R rows (q, q + 4, ...) of each Gaussian in one go,
         // then for every touched row among them, and adds them in ascending order -- the additions of the two-in-flight walk.
@@ -171,22 +177,11 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
                 }
 #pragma unroll
             for (int b = 0; b < 4; b++)
-                if ((h >> b) & 1u) {
-#pragma unroll
-                    for (int k4 = 0; k4 < NV; k4++) {
-                        acc[4 * k4] += t[b][k4].x; acc[4 * k4 + 1] += t[b][k4].y; acc[4 * k4 + 2] += t[b][k4].z; acc[4 * k4 + 3] += t[b][k4].w;
-                    }
-                }
+                if ((h >> b) & 1u) add_row(t[b]);
         }
     } else if (n) {
         const uint8_t* flag = touched + u0;
         const float* rows = partials + (size_t)u0 * row_stride;
-        auto add_row = [&](const float4 (&t)[NV]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k4 = 0; k4 < NV; k4++) {
-                acc[4 * k4] += t[k4].x; acc[4 * k4 + 1] += t[k4].y; acc[4 * k4 + 2] += t[k4].z; acc[4 * k4 + 3] += t[k4].w;
-            }
-        };
         uint32_t i = (uint32_t)q;
         for (; i + SGR_RS_LANES < n; i += 2 * SGR_RS_LANES) {
             const uint8_t f0 = flag[i], f1 = flag[i + SGR_RS_LANES];
@@ -242,24 +237,8 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
             // street_gaussian_model.py:551-571) while dL/dmean2D and the radius are in registers: visibility = radii > 0
             const int r = radii[idx];
             if (sink.accum != nullptr && r > 0) {
-#pragma clang fp contract(off)
-                // persistent row of this Gaussian: identity, or through the frame's segment map (binary search over the
-                // segment starts, kernel arguments -> scalar loads)
-                long row = idx;
-                if (sink.nseg > 0) {
-                    int lo = 0, hi = sink.nseg - 1;
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        if (sink.start[mid] <= idx) lo = mid; else hi = mid - 1;
-                    }
-                    row = (idx >= sink.start[lo] && idx < sink.start[lo] + sink.count[lo]) ? (long)idx + sink.shift[lo] : -1;
-                }
-                if (row >= 0) {
-                    sink.accum[2 * (size_t)row] += sqrtf(acc[0] * acc[0] + acc[1] * acc[1]);  // norm of grad[:, :2]
-                    sink.accum[2 * (size_t)row + 1] += fabsf(acc[2]);                          // norm of grad[:, 2:]
-                    sink.denom[row] += 1.0f;
-                    sink.max_radii[row] = fmaxf(sink.max_radii[row], (float)r);
-                }
+                const long row = sgr_stat_sink_row(sink, idx);
+                if (row >= 0) sgr_stat_sink_add<true>(sink, row, acc[0], acc[1], acc[2], r);
             }
         } else if (q == 1) {
             dL_dopacity[idx] = acc[6];
@@ -271,9 +250,7 @@ sgr_row_sum_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView gv, 
                 // channels the forward clamped at zero get none) -- the payload of the view-sharded exchange, written here
                 // instead of by a launch of its own (sgr_masked_color_grad)
                 const uint32_t cl = n ? gv.clamped[idx] : 0u;  // (culled Gaussians: acc = 0 anyway, `clamped` is not written for them)
-                masked_out[3 * idx + 0] = (cl & 1u) ? 0.f : acc[7];
-                masked_out[3 * idx + 1] = (cl & 2u) ? 0.f : acc[8];
-                masked_out[3 * idx + 2] = (cl & 4u) ? 0.f : acc[9];
+                sgr_mask_clamped(cl, acc + 7, masked_out + 3 * idx);
             }
         } else if (q == 2) {
             cd[idx] = make_float4(acc[3], acc[4], acc[5], acc[10]);
@@ -406,22 +383,8 @@ sgr_row_sum_wave_kernel(int P, int S, const int* __restrict__ radii, SgrGeomView
     // densification statistics of this view (see sgr_row_sum_kernel)
     const int r = radii[idx];
     if (sink.accum != nullptr && r > 0) {
-#pragma clang fp contract(off)
-        long row = idx;
-        if (sink.nseg > 0) {
-            int lo = 0, hi = sink.nseg - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (sink.start[mid] <= idx) lo = mid; else hi = mid - 1;
-            }
-            row = (idx >= sink.start[lo] && idx < sink.start[lo] + sink.count[lo]) ? (long)idx + sink.shift[lo] : -1;
-        }
-        if (row >= 0) {
-            sink.accum[2 * (size_t)row] += sqrtf(acc[0] * acc[0] + acc[1] * acc[1]);
-            sink.accum[2 * (size_t)row + 1] += fabsf(acc[2]);
-            sink.denom[row] += 1.0f;
-            sink.max_radii[row] = fmaxf(sink.max_radii[row], (float)r);
-        }
+        const long row = sgr_stat_sink_row(sink, idx);
+        if (row >= 0) sgr_stat_sink_add<true>(sink, row, acc[0], acc[1], acc[2], r);
     }
 }
 
@@ -466,7 +429,6 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
     // never written and is not touched: the row is read and contracted as before.
     const bool has_jac = shs != nullptr && gv.header[SGR_HDR_JAC] != 0u;
     const int g0 = blockIdx.x * SGR_GB_THREADS + wave * 64;
-    const int nrow4 = max(0, min(64, P - g0)) * 12;  // float4s of this wave's rows
     const int ncoef = (D + 1) * (D + 1);
     float acc[SGR_ROW_BASE_N];
 #pragma unroll
@@ -487,11 +449,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         acc[9] = dL_dcolor[3 * idx + 2];
     }
     if (hoist) {
-        if (scales != nullptr) {
-            sc_top[0] = scales[3 * idx]; sc_top[1] = scales[3 * idx + 1]; sc_top[2] = scales[3 * idx + 2];
-            const float4 q = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)idx);
-            rot_top[0] = q.x; rot_top[1] = q.y; rot_top[2] = q.z; rot_top[3] = q.w;
-        }
+        if (scales != nullptr) sgr_load_scale_rot(scales, rotations, idx, sc_top, rot_top);
         if (shs != nullptr) cl_top = gv.clamped[idx];
     }
 
@@ -514,11 +472,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
             for (int i = 0; i < 3; i++) sc[i] = sc_top[i];
 #pragma unroll
             for (int i = 0; i < 4; i++) rot[i] = rot_top[i];
-        } else if (scales != nullptr) {
-            sc[0] = scales[3 * idx]; sc[1] = scales[3 * idx + 1]; sc[2] = scales[3 * idx + 2];
-            const float4 q = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)idx);
-            rot[0] = q.x; rot[1] = q.y; rot[2] = q.z; rot[3] = q.w;
-        }
+        } else if (scales != nullptr) sgr_load_scale_rot(scales, rotations, idx, sc, rot);
         if (cov3D_precomp) {
 #pragma unroll
             for (int i = 0; i < 6; i++) cov3D[i] = cov3D_precomp[6 * (size_t)idx + i];
@@ -533,16 +487,8 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         if (scales != nullptr) sgr_cov3d_backward(sc, cam.scale_modifier, rot, dcov, dscale, drot);
         if (shs != nullptr) {
             const uint32_t cl = hoist ? cl_top : gv.clamped[idx];
-            dRGB[0] = (cl & 1u) ? 0.f : acc[7];
-            dRGB[1] = (cl & 2u) ? 0.f : acc[8];
-            dRGB[2] = (cl & 4u) ? 0.f : acc[9];
-            dir_orig[0] = p[0] - cam.campos[0];
-            dir_orig[1] = p[1] - cam.campos[1];
-            dir_orig[2] = p[2] - cam.campos[2];
-            const float len = sqrtf(dir_orig[0] * dir_orig[0] + dir_orig[1] * dir_orig[1] + dir_orig[2] * dir_orig[2]);
-            dir[0] = dir_orig[0] / len;
-            dir[1] = dir_orig[1] / len;
-            dir[2] = dir_orig[2] / len;
+            sgr_mask_clamped(cl, acc + 7, dRGB);
+            sgr_view_dir(p, cam.campos, dir_orig, dir);
         }
     }
 
@@ -565,14 +511,9 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         };
         if (stage && !has_jac) {
             const uint64_t vis = __ballot(visible);
-            const float4* src = reinterpret_cast<const float4*>(shs) + (size_t)g0 * 12;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-#pragma unroll
-                for (int it = 0; it < 6; it++) {
-                    const int f = h * 384 + it * 64 + lane;
-                    if (f < nrow4 && ((vis >> (f / 12)) & 1ull)) sSH[wave][f - h * 384] = src[f];
-                }
+                sgr_rows_to_lds<12>(sSH[wave], shs, P, g0, h, lane, vis);
                 __builtin_amdgcn_wave_barrier();
                 if ((lane >> 5) == h && visible) {
 #pragma unroll
@@ -622,7 +563,6 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
         if (skip_sh) {
             // sgr_backward_extras.skip_sh_grad: the factored exchange rebuilds dL/dSH of all views (sgr_sh_grad_from_views)
         } else if (stage) {
-            float4* dst = reinterpret_cast<float4*>(dL_dsh) + (size_t)g0 * 12;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 if ((lane >> 5) == h) {
@@ -630,11 +570,7 @@ sgr_gauss_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, con
                     for (int i = 0; i < 12; i++) sSH[wave][(lane & 31) * 12 + i] = elem4(i);
                 }
                 __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int it = 0; it < 6; it++) {
-                    const int f = h * 384 + it * 64 + lane;
-                    if (f < nrow4) dst[f] = sSH[wave][f - h * 384];
-                }
+                sgr_rows_from_lds<32>(dL_dsh, sSH[wave], P, g0, h, lane);
                 __builtin_amdgcn_wave_barrier();
             }
         } else if (!live) {

@@ -349,15 +349,6 @@ SGR_HD uint32_t sgr_select_bit(uint64_t m, uint32_t k) {
     }
     return pos;
 }
-// Partial-gradient row of instance (Gaussian g, tile (tx, ty)): the Gaussian's first row + the rank of the tile among the
-// tiles it is emitted for (its index inside the rect when there is no mask).
-SGR_HD uint32_t sgr_row_of(uint32_t rect, uint32_t tx, uint32_t ty, const uint32_t* __restrict__ u0,
-                           const uint64_t* __restrict__ tmask, uint32_t g) {
-    const uint32_t rx0 = rect & 1023u, ry0 = (rect >> 10) & 1023u, rw = (rect >> 20) & 1023u;
-    uint32_t j = (ty - ry0) * rw + (tx - rx0);
-    if (rect & 0x80000000u) j = (uint32_t)__builtin_popcountll(tmask[g] & ((1ull << j) - 1ull));
-    return u0[g] + j;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Per-(pixel, Gaussian) evaluation shared by the forward and backward blend kernels.  The conic is
@@ -677,3 +668,8 @@ SGR_HD void sgr_cov3d_backward(const float* scale, float mod, const float* rot, 
                  4 * z * (SGR_MT(1, 1) + SGR_MT(0, 0));
 #undef SGR_MT
 }
+
+// The steps of the per-Gaussian kernels built on the above -- the packed tile rect word with sgr_row_of, the partial-gradient
+// row of an instance, among them -- so that every includer of this header sees them as before (sgr_pergauss.h includes this
+// header first: either order of inclusion works).
+#include "sgr_pergauss.h"

@@ -7,7 +7,7 @@
 // backward.cu:40-44).  Every rank knows all means and all camera centres, so it is enough to ALL-GATHER the 3 floats of
 // dRGB_v per Gaussian and rebuild  sum_v Y(dir_v) (x) dRGB_v  locally, in view order (deterministic, identical on
 // every rank): 12 B per Gaussian and view on the wire instead of a 192 B all-reduce.
-#include "sgr_math.h"
+#include "sgr_pergauss.h"
 #include "sgr_launch.h"
 
 #define SGR_MV_THREADS 256
@@ -19,7 +19,7 @@ sgr_masked_color_grad_kernel(int P, const uint32_t* __restrict__ clamped, const 
     const int i = blockIdx.x * SGR_MV_THREADS + threadIdx.x;  // one float per lane: coalesced
     if (i >= 3 * P) return;
     const int g = i / 3, c = i - 3 * g;
-    out[i] = ((clamped[g] >> c) & 1u) ? 0.0f : dL_dcolor[i];
+    out[i] = sgr_mask_clamped1(clamped[g], c, dL_dcolor[i]);
 }
 
 // dL_dsh[g][k][c] = sum_v Y_k(dir_v(g)) * drgb[v][g][c]   (k < (D+1)^2; zero above)
@@ -64,11 +64,10 @@ sgr_sh_grad_from_views_kernel(int P, int D, int M, int V, const float* __restric
             if (v0 + j >= V) break;
             const float d0 = d[j][0], d1 = d[j][1], d2 = d[j][2];
             if (d0 == 0.f && d1 == 0.f && d2 == 0.f) continue;  // culled / fully clamped / not rendered in this view
-            // same expressions as the per-view backward (sgr_gauss_bwd.hip)
-            const float ox = pp[j][0] - cc[j][0], oy = pp[j][1] - cc[j][1], oz = pp[j][2] - cc[j][2];
-            const float len = sqrtf(ox * ox + oy * oy + oz * oz);
-            float Y[16];
-            sgr_sh_basis(D, ox / len, oy / len, oz / len, Y);
+            // sgr_view_dir<>: the text, and in this file the contraction, of the per-view backward (sgr_gauss_bwd.hip)
+            float dir_orig[3], dir[3], Y[16];
+            sgr_view_dir(pp[j], cc[j], dir_orig, dir);
+            sgr_sh_basis(D, dir[0], dir[1], dir[2], Y);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 if (k < ncoef) {
@@ -83,17 +82,11 @@ sgr_sh_grad_from_views_kernel(int P, int D, int M, int V, const float* __restric
         // rows of 48 floats: the wave's 64 rows are one contiguous 12 KB block -> coalesced 1 KB stores through LDS
         __shared__ float4 sRow[SGR_MV_THREADS / 64][64 * 12];
         const int g0 = blockIdx.x * SGR_MV_THREADS + wave * 64;
-        const int nrow4 = max(0, min(64, P - g0)) * 12;
 #pragma unroll
         for (int i = 0; i < 12; i++)
             sRow[wave][lane * 12 + i] = make_float4(acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]);
         __builtin_amdgcn_wave_barrier();
-        float4* dst = reinterpret_cast<float4*>(dL_dsh) + (size_t)g0 * 12;
-#pragma unroll
-        for (int it = 0; it < 12; it++) {
-            const int f = it * 64 + lane;
-            if (f < nrow4) dst[f] = sRow[wave][f];
-        }
+        sgr_rows_from_lds<64>(dL_dsh, sRow[wave], P, g0, 0, lane);
     } else if (live) {
         float* dsh = dL_dsh + (size_t)idx * M * 3;
 #pragma unroll

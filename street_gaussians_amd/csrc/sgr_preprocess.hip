@@ -5,7 +5,7 @@
 // (rasterizer_impl.cu:54-111, forward.cu:155-334).  One Gaussian per lane, 256-lane workgroups; the
 // outputs are packed into three float4 records per Gaussian so that the tile kernels gather each
 // instance with three 16-byte loads.
-#include "sgr_math.h"
+#include "sgr_pergauss.h"
 #include "sgr_launch.h"
 #include "sgr_radix.h"
 
@@ -14,10 +14,6 @@
 #ifndef SGR_PRE_THREADS
 #define SGR_PRE_THREADS 256
 #endif
-
-__device__ __forceinline__ uint32_t sgr_pack_rect(uint32_t x0, uint32_t y0, uint32_t w) {
-    return x0 | (y0 << 10) | (w << 20);
-}
 
 // ---- K1 -------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(SGR_PRE_THREADS)
@@ -51,9 +47,8 @@ sgr_preprocess_geom(const int idx, const float (&p)[3], const float* __restrict_
 #pragma unroll
             for (int i = 0; i < 6; i++) cov3D[i] = cov3D_precomp[6 * (size_t)idx + i];
         } else {
-            const float sc[3] = {scales[3 * idx], scales[3 * idx + 1], scales[3 * idx + 2]};
-            const float4 q = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)idx);
-            const float rot[4] = {q.x, q.y, q.z, q.w};
+            float sc[3], rot[4];
+            sgr_load_scale_rot(scales, rotations, idx, sc, rot);
             sgr_cov3d(sc, cam.scale_modifier, rot, cov3D);  // not stored: the backward recomputes it (same function)
         }
         pr = sgr_project(p, cov3D, cam);
@@ -86,9 +81,8 @@ sgr_filter_kernel(int P, const float* __restrict__ means3D, const float* __restr
 }
 
 // The colour Jacobian of one Gaussian (sgr_math.h: sgr_sh_color_jacobian) from the SH row the colour was just evaluated
-// from, stored for the per-Gaussian backward (SgrGeomView::jac).  Called from inside the colour evaluation's
-// `fp contract(off)` scope, but a pragma is lexical: these products contract as the translation unit's default says, and
-// the colour's own operations are untouched.
+// from, stored for the per-Gaussian backward (SgrGeomView::jac).  The colour's own operations are op by op where they are
+// written (sgr_pergauss.h); a pragma is lexical, so these products contract as the translation unit's default says.
 __device__ __forceinline__ void sgr_store_color_jacobian(int D, float x, float y, float z, const float* row,
                                                          float* __restrict__ dst) {
     float J[9];
@@ -127,34 +121,21 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     const bool ok = live && pr.ok;
 
     // A/B form (switch bit 6): the rows of the wave's surviving Gaussians through LDS, HALF the wave's rows at a time
-    // (6.5 KB per wave), each lane folding its row into r, g, b as it reads it -- the same operations in the same order
-    // as the direct form below.
+    // (6.5 KB per wave), each lane folding its row into r, g, b as it reads it -- sgr_sh_fold4, the step the
+    // direct form below runs.
     const bool stage = stage_sh && shs != nullptr && colors_precomp == nullptr && M == 16;
     float rgb_s[3] = {0.f, 0.f, 0.f};
     if (stage) {
-#pragma clang fp contract(off)
-        float Y[16];
-        float dx = p[0] - cam.campos[0], dy = p[1] - cam.campos[1], dz = p[2] - cam.campos[2];
-        {
-            const float t0 = dx * dx, t1 = dy * dy, t2 = dz * dz;
-            const float len = sqrtf(t0 + t1 + t2);
-            dx = dx / len; dy = dy / len; dz = dz / len;
-            sgr_sh_basis(D, dx, dy, dz, Y);
-        }
+        float Y[16], dir_orig[3], dir[3];
+        sgr_view_dir<true>(p, cam.campos, dir_orig, dir);
+        sgr_sh_basis(D, dir[0], dir[1], dir[2], Y);
         const int ncoef = (D + 1) * (D + 1);
         const int n4 = (ncoef * 3 + 3) >> 2;
         const uint64_t vis = __ballot(ok);
         const int g0 = blockIdx.x * SGR_PRE_THREADS + wave * 64;
-        const int nrow4 = max(0, min(64, P - g0)) * 12;  // float4s of this wave's rows
-        const float4* src = reinterpret_cast<const float4*>(shs) + (size_t)g0 * 12;
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-#pragma unroll
-            for (int it = 0; it < 6; it++) {
-                const int f = h * 384 + it * 64 + lane;
-                const int row = f / 12;
-                if (f < nrow4 && ((vis >> row) & 1ull)) sSH[wave][f - h * 384 + (row - 32 * h)] = src[f];
-            }
+            sgr_rows_to_lds<13>(sSH[wave], shs, P, g0, h, lane, vis);
             __builtin_amdgcn_wave_barrier();
             if ((lane >> 5) == h && ok) {
 #pragma unroll
@@ -162,16 +143,12 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                     if (i < n4) {
                         const float4 t = sSH[wave][(lane & 31) * 13 + i];
                         const float e[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const int k = (4 * i + j) / 3, ch = (4 * i + j) % 3;
-                            if (k < ncoef) rgb_s[ch] = (k == 0) ? Y[0] * e[j] : rgb_s[ch] + Y[k] * e[j];
-                        }
+                        sgr_sh_fold4(i, e, Y, ncoef, rgb_s);
                     }
                 }
                 // (J from the staged row itself, a second read of LDS: held in registers for it, the row costs a wave of occupancy)
                 if (want_jac)
-                    sgr_store_color_jacobian(D, dx, dy, dz, reinterpret_cast<const float*>(&sSH[wave][(lane & 31) * 13]),
+                    sgr_store_color_jacobian(D, dir[0], dir[1], dir[2], reinterpret_cast<const float*>(&sSH[wave][(lane & 31) * 13]),
                                              gv.jac + 9 * (size_t)idx);
             }
             __builtin_amdgcn_wave_barrier();
@@ -194,20 +171,16 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
             rgb[1] = colors_precomp[3 * idx + 1];
             rgb[2] = colors_precomp[3 * idx + 2];
         } else {
-#pragma clang fp contract(off)
-            float dx = p[0] - cam.campos[0], dy = p[1] - cam.campos[1], dz = p[2] - cam.campos[2];
-            const float t0 = dx * dx, t1 = dy * dy, t2 = dz * dz;
-            const float len = sqrtf(t0 + t1 + t2);
-            dx = dx / len; dy = dy / len; dz = dz / len;
-            float Y[16];
-            sgr_sh_basis(D, dx, dy, dz, Y);
+            float Y[16], dir_orig[3], dir[3];
+            sgr_view_dir<true>(p, cam.campos, dir_orig, dir);
+            sgr_sh_basis(D, dir[0], dir[1], dir[2], Y);
             const int ncoef = (D + 1) * (D + 1);
             const float* sh = shs + (size_t)idx * M * 3;
-            float r = 0.f, g = 0.f, b = 0.f;
+            rgb[0] = rgb[1] = rgb[2] = 0.f;
             if (stage) {
-                r = rgb_s[0]; g = rgb_s[1]; b = rgb_s[2];
+                rgb[0] = rgb_s[0]; rgb[1] = rgb_s[1]; rgb[2] = rgb_s[2];
             } else if (((M * 3) & 3) == 0 && M <= 16) {
-                // row stride is a multiple of 16 B: the row as float4 (12 at SH degree 3)
+                // row stride is a multiple of 16 B: the row as float4 (12 at SH degree 3), requested together, then folded
                 const float4* sh4 = reinterpret_cast<const float4*>(sh);
                 const int n4 = (ncoef * 3 + 3) >> 2;
                 float buf[48];
@@ -219,74 +192,24 @@ sgr_preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    if (k < ncoef) {
-                        if (k == 0) { r = Y[0] * buf[0]; g = Y[0] * buf[1]; b = Y[0] * buf[2]; }
-                        else { r = r + Y[k] * buf[3 * k]; g = g + Y[k] * buf[3 * k + 1]; b = b + Y[k] * buf[3 * k + 2]; }
-                    }
-                }
-                if (want_jac) sgr_store_color_jacobian(D, dx, dy, dz, buf, gv.jac + 9 * (size_t)idx);
+                for (int i = 0; i < 12; i++) sgr_sh_fold4(i, buf + 4 * i, Y, ncoef, rgb);
+                if (want_jac) sgr_store_color_jacobian(D, dir[0], dir[1], dir[2], buf, gv.jac + 9 * (size_t)idx);
             } else {
-                for (int k = 0; k < ncoef; k++) {
-                    if (k == 0) { r = Y[0] * sh[0]; g = Y[0] * sh[1]; b = Y[0] * sh[2]; }
-                    else { r = r + Y[k] * sh[3 * k]; g = g + Y[k] * sh[3 * k + 1]; b = b + Y[k] * sh[3 * k + 2]; }
-                }
+                sgr_sh_fold_row(sh, Y, ncoef, rgb);
                 // (rows that are not 16-byte aligned: the coefficients a second time, from the cache)
-                if (want_jac) sgr_store_color_jacobian(D, dx, dy, dz, sh, gv.jac + 9 * (size_t)idx);
+                if (want_jac) sgr_store_color_jacobian(D, dir[0], dir[1], dir[2], sh, gv.jac + 9 * (size_t)idx);
             }
-            r += 0.5f; g += 0.5f; b += 0.5f;
-            clamped = (r < 0 ? 1u : 0u) | (g < 0 ? 2u : 0u) | (b < 0 ? 4u : 0u);
-            rgb[0] = fmaxf(r, 0.0f); rgb[1] = fmaxf(g, 0.0f); rgb[2] = fmaxf(b, 0.0f);
+            sgr_sh_finish(rgb, clamped);
         }
 
         const float opacity = opacities[idx];
         float hx, hy;
         sgr_extent(opacity, pr.cov_a, pr.cov_c, pr.con_x, pr.con_y, pr.con_z, hx, hy);
-        // Tile rect of the Gaussian.  The reference takes the square of ceil(3 sigma_max) pixels around the centre
-        // (auxiliary.h:46-57 getRect) and so emits a (tile, Gaussian) instance for many tiles in which the Gaussian cannot pass
-        // the alpha >= 1/255 test of the blend (forward.cu:428-430): low opacity, anisotropy.  Those instances change nothing in
-        // any output (the blend skips them) but are duplicated, sorted, staged and given a partial-gradient row.  `tight`
-        // intersects the reference rect with the tiles of the box [px -+ hx] x [py -+ hy] outside of which alpha < 1/255
-        // (sgr_extent: conservative, the box the quadrant cull of the blend kernels has used since round 1): 0.72 of the
-        // reference's instances on the benchmark scene; every image bit-identical, the gradients equal up to the grouping of the
-        // row sum's additions (tests).  A Gaussian keeps at
-        // least one tile, so that "radius > 0" still implies "owns a row".  rn = the reference's count (reported, header[5]).
-        uint32_t x0 = pr.rx0, x1 = pr.rx1, y0 = pr.ry0, y1 = pr.ry1;
-        const uint32_t rn = (x1 - x0) * (y1 - y0);
-        if (tight) {
-            // pixel x of tile t: 16 t .. 16 t + 15; pixels that can pass lie in [px - hx, px + hx]  (NaN extents: fmaxf / fminf
-            // return the other operand = the reference rect)
-            const float inv = 1.0f / SGR_BLOCK_X;
-            static_assert(SGR_BLOCK_X == SGR_BLOCK_Y, "square tiles");
-            float fx0 = fmaxf(floorf((pr.px - hx) * inv), (float)x0), fx1 = fminf(floorf((pr.px + hx) * inv) + 1.0f, (float)x1);
-            float fy0 = fmaxf(floorf((pr.py - hy) * inv), (float)y0), fy1 = fminf(floorf((pr.py + hy) * inv) + 1.0f, (float)y1);
-            if (!(fx0 < fx1)) { fx0 = fminf(fmaxf(floorf(pr.px * inv), (float)x0), (float)(x1 - 1)); fx1 = fx0 + 1.0f; }
-            if (!(fy0 < fy1)) { fy0 = fminf(fmaxf(floorf(pr.py * inv), (float)y0), (float)(y1 - 1)); fy1 = fy0 + 1.0f; }
-            x0 = (uint32_t)fx0; x1 = (uint32_t)fx1; y0 = (uint32_t)fy0; y1 = (uint32_t)fy1;
-        }
-        // tight == 3 (marked-list mode): the reference's rect is what gets emitted (aux_ref); the cut-down rect + mask below
-        // say which of those instances are live and number the Gaussian's partial-gradient rows
-        const uint32_t w = x1 - x0, h = y1 - y0;
-        uint32_t rect = sgr_pack_rect(x0, y0, w);
-        uint32_t nemit = w * h;
-        if (tight > 1 && w >= 2u && h >= 2u && nemit <= 64u) {  // (a single row or column of tiles IS its bounding box)
-            // ... and inside that rect only the tiles the alpha >= 1/255 ellipse reaches (the rect is its bounding box: the
-            // corners go): a 64-bit tile mask for rects of up to 64 tiles (sgr_math.h: sgr_tile_mask), bit 31 of the rect word
-            // says "masked".  duplicate emits the set tiles, the backward numbers a Gaussian's rows by the rank of the tile in
-            // the mask.  0.61 instead of 0.72 of the reference's instances on the benchmark scene.
-            uint64_t tm = sgr_tile_mask(pr.px, pr.py, pr.con_x, pr.con_y, pr.con_z, opacity, x0, y0, x1, y1);
-            if (tm == 0) {  // reaches no tile (opacity below 1/255 ...): the centre's tile, so that the Gaussian owns a row
-                const uint32_t cx = (uint32_t)fminf(fmaxf(floorf(pr.px * (1.0f / SGR_BLOCK_X)), (float)x0), (float)(x1 - 1));
-                const uint32_t cy = (uint32_t)fminf(fmaxf(floorf(pr.py * (1.0f / SGR_BLOCK_Y)), (float)y0), (float)(y1 - 1));
-                tm = 1ull << ((cy - y0) * w + (cx - x0));
-            }
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(tm);
-            if (cnt != nemit) {
-                rect |= SGR_RECT_MASKED;
-                gv.tmask[idx] = tm;
-                nemit = cnt;
-            }
-        }
+        // Tile rect of the Gaussian (sgr_pergauss.h: sgr_tight_rect).  rn = the reference's count (reported, header[5]).
+        const uint32_t rn = (pr.rx1 - pr.rx0) * (pr.ry1 - pr.ry0);
+        const SgrTightRect tr = sgr_tight_rect(pr, hx, hy, opacity, tight);
+        const uint32_t rect = tr.rect, nemit = tr.nemit;
+        if (rect & SGR_RECT_MASKED) gv.tmask[idx] = tr.tmask;
         nref = rn;
         float4* rec = gv.rec + 4 * (size_t)idx;
         rec[0] = make_float4(pr.px, pr.py, hx, hy);
@@ -415,30 +338,12 @@ sgr_duplicate_kernel(int P, SgrGeomView gv, const uint32_t* __restrict__ order, 
 #pragma unroll
         for (int step = 32; step >= 1; step >>= 1)
             if (sOff[wave][o + step] <= s) o += step;
+        // (marked-list mode emits the reference's rect, whose word never says "masked": sMask is the cut-down rect's there)
         const uint32_t r = sRect[wave][o];
-        const uint32_t x0 = r & 1023u, y0 = (r >> 10) & 1023u, w = (r >> 20) & 1023u;
-        uint32_t k = s - sOff[wave][o];
-        if (!marks && (r & SGR_RECT_MASKED)) k = sgr_select_bit(sMask[wave][o], k);  // the k-th tile of the mask, as an index into the rect
-        // k / w with one v_rcp_f32 and an exact fix-up (k < 2^20)
-        uint32_t q = (uint32_t)((float)k * __builtin_amdgcn_rcpf((float)w));
-        int rem = (int)k - (int)(q * w);
-        if (rem < 0) { q--; rem += (int)w; }
-        if (rem >= (int)w) { q++; rem -= (int)w; }
-        const uint32_t tx = x0 + (uint32_t)rem, ty = y0 + q;
-        keys[s] = (K)(ty * (uint32_t)gx + tx);
+        const uint2 t = sgr_slot_tile(r, sMask[wave][o], s - sOff[wave][o], __builtin_amdgcn_rcpf((float)sgr_unpack_rect(r).w));
+        keys[s] = (K)(t.y * (uint32_t)gx + t.x);
         uint32_t v = sIdx[wave][o];
-        if (marks) {
-            // live = inside the cut-down rect and, with a mask, one of its set tiles (index j inside that rect: below the
-            // number of its tiles without a mask -- which bounds the row -- or a set bit with one)
-            const uint32_t lr = sLive[wave][o];
-            const uint32_t lx0 = lr & 1023u, ly0 = (lr >> 10) & 1023u, lw = (lr >> 20) & 1023u;
-            const uint32_t dxl = tx - lx0, dyl = ty - ly0;  // (wrap around for tiles left of / above the rect: >= lw / huge)
-            const uint32_t j = dyl * lw + dxl;
-            bool live = dxl < lw && ty >= ly0;
-            if (lr & SGR_RECT_MASKED) live = live && j < 64u && ((sMask[wave][o] >> (j & 63u)) & 1ull);
-            else live = live && j < sLiveN[wave][o];
-            if (!live) v |= SGR_DEAD;
-        }
+        if (marks && !sgr_mark_live(sLive[wave][o], sLiveN[wave][o], sMask[wave][o], t.x, t.y)) v |= SGR_DEAD;
         vals[s] = v;
     }
 }

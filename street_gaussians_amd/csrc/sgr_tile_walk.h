@@ -13,7 +13,7 @@
 // kernel, whose `#pragma clang fp contract(off)` and source order of float operations these functions keep.
 #ifndef SGR_TILE_WALK_H
 #define SGR_TILE_WALK_H
-#include "sgr_math.h"
+#include "sgr_pergauss.h"  // sgr_row_of
 
 #define SGR_TILE_THREADS 256
 #ifndef SGR_EXACT_TRIM

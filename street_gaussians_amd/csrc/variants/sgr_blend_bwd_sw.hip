@@ -19,7 +19,7 @@
 //     (order-free) by the lanes that scanned the entry.
 // Bit-reproducible like the LDS kernel: every float sum has a fixed order (lanes of a wave by the reduction tree, rows of
 // a Gaussian by (tile, quadrant) in the row sum).
-#include "../sgr_math.h"
+#include "../sgr_pergauss.h"  // sgr_row_of
 #include "../sgr_launch.h"
 #include "../sgr_reduce.h"
 

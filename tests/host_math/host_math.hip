@@ -1,9 +1,10 @@
 // TEST INFRASTRUCTURE.  Host (x86) build of the __host__ __device__ maths in
-// street_gaussians_amd/csrc/sgr_math.h, sgr_quat.h, sgr_ssim.h and sgr_radix.h, so the formulas the gfx950 kernels run can be
-// checked against the oracle without a GPU (tests/test_host_math.py, tests/test_quat_cpu.py, tests/test_ssim_host_cpu.py,
-// tests/test_radix_host_cpu.py).
+// street_gaussians_amd/csrc/sgr_math.h, sgr_pergauss.h, sgr_quat.h, sgr_ssim.h and sgr_radix.h, so the formulas the gfx950
+// kernels run can be checked against the oracle without a GPU (tests/test_host_math.py, tests/test_pergauss_host_cpu.py,
+// tests/test_quat_cpu.py, tests/test_ssim_host_cpu.py, tests/test_radix_host_cpu.py).
 // Built with `hipcc -x hip --cuda-host-only`; never loaded by the product.
 #include "../../street_gaussians_amd/csrc/sgr_math.h"
+#include "../../street_gaussians_amd/csrc/sgr_pergauss.h"
 #include "../../street_gaussians_amd/csrc/sgr_quat.h"
 #include "../../street_gaussians_amd/csrc/sgr_ssim.h"
 #include "../../street_gaussians_amd/csrc/sgr_radix.h"
@@ -76,20 +77,17 @@ void hm_forward(int P, int D, int M, const float* means, const float* scales, co
         means2D[2 * i] = pr.px; means2D[2 * i + 1] = pr.py;
         conic[3 * i] = pr.con_x; conic[3 * i + 1] = pr.con_y; conic[3 * i + 2] = pr.con_z;
         sgr_extent(opac[i], pr.cov_a, pr.cov_c, pr.con_x, pr.con_y, pr.con_z, extents[2 * i], extents[2 * i + 1]);
-        // SH colour exactly as sgr_preprocess_kernel does it
-        float dx = means[3 * i] - cam.campos[0], dy = means[3 * i + 1] - cam.campos[1], dz = means[3 * i + 2] - cam.campos[2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        dx /= len; dy /= len; dz /= len;
-        float Y[16];
-        sgr_sh_basis(D, dx, dy, dz, Y);
-        const float* sh = shs + (size_t)i * M * 3;
+        // SH colour: the calls sgr_preprocess_kernel makes (sgr_pergauss.h)
+        float dor[3], dir[3], Y[16];
+        sgr_view_dir<true>(means + 3 * i, cam.campos, dor, dir);
+        sgr_sh_basis(D, dir[0], dir[1], dir[2], Y);
         float c[3] = {0, 0, 0};
-        for (int k = 0; k < (D + 1) * (D + 1); k++)
-            for (int ch = 0; ch < 3; ch++) c[ch] = (k == 0) ? Y[0] * sh[ch] : c[ch] + Y[k] * sh[3 * k + ch];
+        sgr_sh_fold_row(shs + (size_t)i * M * 3, Y, (D + 1) * (D + 1), c);
+        uint32_t cl;
+        sgr_sh_finish(c, cl);
         for (int ch = 0; ch < 3; ch++) {
-            c[ch] += 0.5f;
-            clamped[3 * i + ch] = c[ch] < 0;
-            rgb[3 * i + ch] = fmaxf(c[ch], 0.f);
+            clamped[3 * i + ch] = (cl >> ch) & 1u;
+            rgb[3 * i + ch] = c[ch];
         }
     }
 }
@@ -107,11 +105,10 @@ void hm_backward(int P, int D, int M, const float* means, const float* scales, c
         sgr_cov2d_backward(means + 3 * i, cov3D + 6 * i, cam, dconic[4 * i], dconic[4 * i + 1], dconic[4 * i + 3], dcov, dmean);
         sgr_proj_depth_backward(means + 3 * i, cam, dmean2D[3 * i], dmean2D[3 * i + 1], ddepth[i], dmean);
         sgr_cov3d_backward(scales + 3 * i, mod, rots + 4 * i, dcov, dscale + 3 * i, drot + 4 * i);
-        float dRGB[3];
-        for (int ch = 0; ch < 3; ch++) dRGB[ch] = clamped[3 * i + ch] ? 0.f : dcolor[3 * i + ch];
-        float dor[3] = {means[3 * i] - cam.campos[0], means[3 * i + 1] - cam.campos[1], means[3 * i + 2] - cam.campos[2]};
-        const float len = sqrtf(dor[0] * dor[0] + dor[1] * dor[1] + dor[2] * dor[2]);
-        const float dir[3] = {dor[0] / len, dor[1] / len, dor[2] / len};
+        float dRGB[3], dor[3], dir[3];
+        const uint32_t cl = (clamped[3 * i] ? 1u : 0u) | (clamped[3 * i + 1] ? 2u : 0u) | (clamped[3 * i + 2] ? 4u : 0u);
+        sgr_mask_clamped(cl, dcolor + 3 * i, dRGB);
+        sgr_view_dir(means + 3 * i, cam.campos, dor, dir);
         float Y[16];
         sgr_sh_basis(D, dir[0], dir[1], dir[2], Y);
         const float* sh = shs + (size_t)i * M * 3;
@@ -152,6 +149,44 @@ void hm_tile_masks_per_tile(int n, const float* means2D, const float* conic_opac
 unsigned hm_select_bit(unsigned long long m, unsigned k) { return sgr_select_bit(m, k); }
 unsigned hm_row_of(unsigned rect, unsigned tx, unsigned ty, const unsigned* u0, const unsigned long long* tmask, unsigned g) {
     return sgr_row_of(rect, tx, ty, u0, (const uint64_t*)tmask, g);
+}
+
+// ---- csrc/sgr_pergauss.h (tests/test_pergauss_host_cpu.py) ----
+// slot k of a rect word -> its tile {tx, ty}, with the caller's reciprocal of the rect's width
+void hm_slot_tile(unsigned rect, unsigned long long mask, unsigned k, float rcp_w, unsigned* txy) {
+    const uint2 t = sgr_slot_tile(rect, (uint64_t)mask, k, rcp_w);
+    txy[0] = t.x; txy[1] = t.y;
+}
+int hm_mark_live(unsigned live_rect, unsigned live_n, unsigned long long mask, unsigned tx, unsigned ty) {
+    return sgr_mark_live(live_rect, live_n, (uint64_t)mask, tx, ty) ? 1 : 0;
+}
+// the preprocess's rect decision per Gaussian of a scene: ref = the reference rect {x0, y0, x1, y1} (zeros when culled),
+// out = {rect word, nemit} and the mask as sgr_tight_rect returns it
+void hm_tight_rects(int P, const float* means, const float* scales, const float* rots, const float* opac, const float* view,
+                    const float* proj, float tanx, float tany, int W, int H, float mod, int tight, unsigned* ref, unsigned* out,
+                    unsigned long long* tmask) {
+    const SgrCam cam = make_cam(view, proj, nullptr, tanx, tany, W, H, mod);
+    for (int i = 0; i < P; i++) {
+        float cov3D[6], hx, hy;
+        sgr_cov3d(scales + 3 * i, mod, rots + 4 * i, cov3D);
+        const SgrProj pr = sgr_project(means + 3 * i, cov3D, cam);
+        for (int k = 0; k < 4; k++) ref[4 * i + k] = 0u;
+        out[2 * i] = out[2 * i + 1] = 0u;
+        tmask[i] = 0ull;
+        if (!pr.ok) continue;
+        sgr_extent(opac[i], pr.cov_a, pr.cov_c, pr.con_x, pr.con_y, pr.con_z, hx, hy);
+        const SgrTightRect t = sgr_tight_rect(pr, hx, hy, opac[i], tight);
+        ref[4 * i] = pr.rx0; ref[4 * i + 1] = pr.ry0; ref[4 * i + 2] = pr.rx1; ref[4 * i + 3] = pr.ry1;
+        out[2 * i] = t.rect; out[2 * i + 1] = t.nemit;
+        tmask[i] = t.tmask;
+    }
+}
+// persistent rows of n indices through a segment map (nseg == 0: identity)
+void hm_stat_sink_rows(int nseg, const int* start, const int* count, const int* shift, int n, const int* idx, long long* rows) {
+    SgrStatSink sink;
+    sink.nseg = nseg;
+    for (int s = 0; s < nseg; s++) { sink.start[s] = start[s]; sink.count[s] = count[s]; sink.shift[s] = shift[s]; }
+    for (int i = 0; i < n; i++) rows[i] = sgr_stat_sink_row(sink, idx[i]);
 }
 
 float hm_power2(float qa, float qb, float qc, float dx, float dy) { return sgr_power2(qa, qb, qc, dx, dy); }

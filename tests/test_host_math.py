@@ -103,7 +103,7 @@ def test_forward_geometry_bit_exact_and_backward_close(hm, deg, margin, scale_px
     front = depths > 0.2
     assert (cov3D[front] == fw.cov3D[front]).all()
     assert (clamped[vis] == fw.clamped[vis]).all() and fw.clamped.sum() > 0
-    assert np.abs(rgb[vis] - fw.rgb[vis]).max() <= 1e-6
+    assert (rgb[vis] == fw.rgb[vis]).all()  # the preprocess's own fold (sgr_pergauss.h, op by op) has the oracle's bits
 
     # conservative extents: every (pixel, Gaussian) pair the oracle's blend accepts lies inside the box
     pl, rg = fw.point_list, fw.ranges
