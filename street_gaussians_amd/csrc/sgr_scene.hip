@@ -487,7 +487,11 @@ sgr_scene_stats_kernel(const SgrChunk* __restrict__ chunks, const SgrStatSegDev*
     if (r <= 0) return;  // visibility_filter = radii > 0 (street_gaussian_renderer.py)
     const float gx = dmeans2D[3 * o], gy = dmeans2D[3 * o + 1], gz = dmeans2D[3 * o + 2];
     if (sg.xyz_gradient_accum) {
-        sg.xyz_gradient_accum[2 * i] += sqrtf(gx * gx + gy * gy);  // street_gaussian_model.py:567
+        // op by op, as the rasterizer's statistics sink forms it (sgr_stat_sink_add<true>, sgr_pergauss.h): the two routes
+        // to the statistics give the same bits
+        float n2;
+        { _Pragma("clang fp contract(off)") n2 = gx * gx + gy * gy; }
+        sg.xyz_gradient_accum[2 * i] += sqrtf(n2);                  // street_gaussian_model.py:567
         sg.xyz_gradient_accum[2 * i + 1] += fabsf(gz);              // :568 (norm of one component)
     }
     if (sg.denom) sg.denom[i] += 1.0f;                               // :569
