@@ -92,6 +92,11 @@ def _signatures():
         "sgr_frame_loss_finish_span": (i, []),
         "sgr_frame_loss_forward": (i, [i, i, i, vp, vp, vp, vp, vp]),
         "sgr_frame_loss_backward": (i, [i, i, i] + [vp] * 10),
+        "sgr_semantic_loss_workspace_floats": (sz, [i, i, i]),
+        "sgr_semantic_loss_block_pixels": (i, []),
+        "sgr_semantic_loss_finish_span": (i, []),
+        "sgr_semantic_loss_forward": (i, [i, i, i, vp, vp, i, i, i, vp, vp, vp, vp]),
+        "sgr_semantic_loss_backward": (i, [i, i, i, vp, vp, i, i, i, vp, vp, vp, vp]),
         "sgr_mse_workspace_floats": (sz, [i, i, i]),
         "sgr_mse_forward": (i, [i, i, i, vp, vp, vp, vp, vp, vp]),
         "sgr_densify_work_bytes": (sz, [i]),

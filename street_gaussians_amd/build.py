@@ -16,18 +16,18 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsgr_hip.so")
 SOURCES = ["sgr_preprocess.hip", "sgr_scan_sort.hip", "sgr_tile_sort.hip", "sgr_blend_fwd.hip", "sgr_blend_layers.hip", "sgr_object_alpha.hip", "sgr_blend_bwd.hip", "sgr_gauss_bwd.hip", "sgr_gauss_bwd_strict.hip",
-           "sgr_knn.hip", "sgr_multiview.hip", "sgr_scene.hip", "sgr_loss.hip", "sgr_frame_loss.hip", "sgr_densify.hip", "sgr_densify_scene.hip", "sgr_texture.hip", "sgr_sky.hip", "sgr_optim.hip", "sgr_actor_pose.hip", "sgr_api.hip"]
+           "sgr_knn.hip", "sgr_multiview.hip", "sgr_scene.hip", "sgr_loss.hip", "sgr_frame_loss.hip", "sgr_semantic_loss.hip", "sgr_densify.hip", "sgr_densify_scene.hip", "sgr_texture.hip", "sgr_sky.hip", "sgr_optim.hip", "sgr_actor_pose.hip", "sgr_api.hip"]
 # Designs that were built, measured slower on MI355X and kept as A/B records: the scalar-walk blend
 # backward (its own file), and -- behind `#if SGR_WITH_VARIANTS` inside the files above -- the transposed-accumulation
 # backward, the one-sweep radix sorts and the wave-cooperative row sum.  NOT part of the shipped library:
 # `python tools/build_variant.py <name> -DSGR_WITH_VARIANTS=1` builds a library that contains them (sgr_has_variants() = 1),
 # and the tests of those paths run only against such a build.
 VARIANT_SOURCES = [os.path.join("variants", "sgr_blend_bwd_sw.hip")]
-HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_ssim.h", "sgr_math.h", "sgr_launch.h", "sgr_tile_walk.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", "sgr_quat.h", "sgr_radix.h", "sgr_pergauss.h", os.path.join("..", "..", "include", "sgr.h"),
+HEADERS = ["sgr_common.h", "sgr_loss_internal.h", "sgr_ssim.h", "sgr_semantic.h", "sgr_math.h", "sgr_launch.h", "sgr_tile_walk.h", "sgr_reduce.h", "sgr_cube.h", "sgr_adam_math.h", "sgr_densify_rules.h", "sgr_quat.h", "sgr_radix.h", "sgr_pergauss.h", os.path.join("..", "..", "include", "sgr.h"),
            os.path.join("..", "..", "include", "sgr_scene.h"), os.path.join("..", "..", "include", "sgr_scene_frame.h"), os.path.join("..", "..", "include", "sgr_loss.h"), os.path.join("..", "..", "include", "sgr_densify.h"),
            os.path.join("..", "..", "include", "sgr_texture.h"), os.path.join("..", "..", "include", "sgr_optim.h"),
            os.path.join("..", "..", "include", "sgr_sky.h"), os.path.join("..", "..", "include", "sgr_actor_pose.h"),
-           os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_object_alpha.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h"), os.path.join("..", "..", "include", "sgr_frame_loss.h"),
+           os.path.join("..", "..", "include", "sgr_layers.h"), os.path.join("..", "..", "include", "sgr_object_alpha.h"), os.path.join("..", "..", "include", "sgr_densify_scene.h"), os.path.join("..", "..", "include", "sgr_frame_loss.h"), os.path.join("..", "..", "include", "sgr_semantic_loss.h"),
            os.path.join("..", "..", "include", "sgr_sky_step.h"), os.path.join("..", "..", "include", "sgr_scene_step.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 ops into v_pk_* and pays for it with v_mov
 # shuffles; measured on MI355X it costs 6 % in the blend backward and 7 % in the per-Gaussian backward.

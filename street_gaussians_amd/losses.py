@@ -6,6 +6,8 @@ of ~30 MIOpen / elementwise launches.  `train.py:100-104` keeps its two lines; o
 
 `frame_loss` is all of `train.py:100-133` as one op (csrc/sgr_frame_loss.hip): one backward kernel for the four image
 gradients and one device tensor with every scalar the loop logs; `psnr` is loss_utils.py:61-78 without its host wait.
+`semantic_loss` is the cross-entropy on the rendered semantic head (csrc/sgr_semantic_loss.hip), the term the reference
+renders for (`lambda_semantic`) and leaves to the trainer.
 
 Tensors must live on the GPU; there is no CPU implementation in the product."""
 from __future__ import annotations
@@ -359,3 +361,87 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor, mask: Optional[torch.Tensor] = 
     ws = torch.empty(_native.lib().sgr_mse_workspace_floats(Cc, H, W), dtype=torch.float32, device=dev)
     call("sgr_mse_forward", dev, Cc, H, W, a, b, _prep_mask(mask, H, W), out, ws)
     return out[1]
+
+
+# ---- cross-entropy on the rendered semantic head (include/sgr_semantic_loss.h) ------------------------------------------
+SEMANTIC_MODES = {"logits": 0, "probabilities": 1}                              # SGR_SEM_LOGITS, SGR_SEM_PROBABILITIES
+_SEM_LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}            # SGR_SEM_LABEL_U8 / I32 / I64
+_SEM_LABEL_CONVERTED = (torch.int16, torch.float32)                             # one .to(torch.int32)
+SEM_MAX_CHANNELS = 32                                                           # SGR_SEM_MAX_CHANNELS
+
+
+class SemanticTerms(NamedTuple):
+    """0-dim views of ``values`` (4 floats on the device, include/sgr_semantic_loss.h's enum order): the mean
+    cross-entropy over the valid pixels, their number, the number of labels >= S that are not ``ignore_index`` (a bad
+    label map shows here, without a device assert), and the share of valid pixels whose arg-max channel is the label.
+    ``pred`` is the uint8 [H, W] arg-max image with ``return_pred=True``, else None."""
+    loss: torch.Tensor
+    n_valid: torch.Tensor
+    n_out_of_range: torch.Tensor
+    accuracy: torch.Tensor
+    values: torch.Tensor
+    pred: Optional[torch.Tensor] = None
+
+
+class _SemanticLoss(torch.autograd.Function):
+    """The map kernel and one finishing workgroup forward, ONE kernel backward that writes dL/dsemantics -- the image the
+    rasterizer's backward reads -- with zeros on the pixels that do not count."""
+
+    @staticmethod
+    def forward(ctx, semantic, labels, label_dtype, ignore_index, mode, return_pred):
+        L = _native.lib()
+        S, H, W = semantic.shape
+        dev = semantic.device
+        values = torch.empty(4, dtype=torch.float32, device=dev)
+        pred = torch.empty(H, W, dtype=torch.uint8, device=dev) if return_pred else None
+        ws = torch.empty(L.sgr_semantic_loss_workspace_floats(S, H, W), dtype=torch.float32, device=dev)
+        call("sgr_semantic_loss_forward", dev, S, H, W, semantic, labels, label_dtype, ignore_index, mode, values, pred, ws)
+        ctx.save_for_backward(semantic, labels, values)
+        ctx.scalars = (label_dtype, ignore_index, mode)
+        ctx.mark_non_differentiable(values)
+        if pred is not None:
+            ctx.mark_non_differentiable(pred)
+        return values[0], values, pred
+
+    @staticmethod
+    def backward(ctx, upstream, _values, _pred):
+        semantic, labels, values = ctx.saved_tensors
+        S, H, W = semantic.shape
+        up = upstream.reshape(1).to(torch.float32).contiguous()
+        grad = torch.empty_like(semantic)
+        call("sgr_semantic_loss_backward", semantic.device, S, H, W, semantic, labels, *ctx.scalars, values, up, grad)
+        return grad, None, None, None, None, None
+
+
+def semantic_loss(semantic: torch.Tensor, labels: torch.Tensor, *, mode: str = "logits", ignore_index: int = -1,
+                  return_pred: bool = False):
+    """Cross-entropy of the rendered semantic head against a label map, in one op -> ``(loss, terms)``.
+
+    ``semantic`` is the rasterizer's fifth output, ``[S, H, W]`` float32 with ``S <= 32``; ``labels`` is ``[H, W]`` or
+    ``[1, H, W]``, uint8 / int32 / int64 as they are, int16 / float32 (what the reference's ``get_semantic_label``
+    returns) through one ``.to(torch.int32)``.  A pixel counts when its label is in ``[0, S)`` and is not
+    ``ignore_index`` (labels < 0 are invalid, lib/utils/sem_utils.py:35).  ``mode='logits'`` is
+    ``F.cross_entropy``; ``mode='probabilities'`` is street_gaussian_renderer.py:261-262 (normalise the alpha-weighted
+    probabilities, log with eps 1e-8) followed by ``F.nll_loss``.  ``loss`` (0-dim) is differentiable with respect to
+    ``semantic`` only; ``loss.backward()`` is one kernel.  ``terms`` (SemanticTerms) lives on the device: nothing here
+    waits on the host."""
+    if mode not in SEMANTIC_MODES:
+        raise ValueError(f"mode must be one of {sorted(SEMANTIC_MODES)}, not {mode!r}")
+    if semantic.dim() != 3:
+        raise ValueError("semantic must have dimensions (S, H, W)")
+    S, H, W = semantic.shape
+    if not 1 <= S <= SEM_MAX_CHANNELS:
+        raise ValueError(f"semantic has {S} channels: the rasterizer renders 1 to {SEM_MAX_CHANNELS}")
+    if labels.dim() == 3 and labels.shape[0] == 1:
+        labels = labels[0]
+    if tuple(labels.shape) != (H, W):
+        raise ValueError(f"labels must have dimensions ({H}, {W}) or (1, {H}, {W}), not {tuple(labels.shape)}")
+    if labels.dtype not in _SEM_LABEL_DTYPES and labels.dtype not in _SEM_LABEL_CONVERTED:
+        raise ValueError(f"labels of dtype {labels.dtype}: uint8, int16, int32, int64 or float32 are accepted")
+    require_hip("semantic and labels must be HIP (cuda) tensors: there is no CPU path", semantic, labels)
+    if labels.dtype in _SEM_LABEL_CONVERTED:
+        labels = labels.to(torch.int32)
+    loss, values, pred = _SemanticLoss.apply(semantic.to(torch.float32).contiguous(), labels.detach().contiguous(),
+                                             _SEM_LABEL_DTYPES[labels.dtype], int(ignore_index), SEMANTIC_MODES[mode],
+                                             bool(return_pred))
+    return loss, SemanticTerms(*values.unbind(0), values, pred)
