@@ -92,7 +92,11 @@ int sgr_forward_ex(sgr_alloc_fn geometry_buffer, void* geometry_user, sgr_alloc_
  * fully written (no zero-initialisation needed, cf. rasterize_points.cu:166-176):
  * dL_dmean2D[P,3] (z = sum |gx|+|gy|), dL_dopacity[P], dL_dcolor[P,3], dL_dmean3D[P,3], dL_dcov3D[P,6],
  * dL_dsh[P,M,3] (NULL if shs NULL), dL_dscale[P,3], dL_drot[P,4], dL_dsemantic[P,S].
- * (The reference's dL_dconic / dL_ddepth intermediates are internal here.) */
+ * (The reference's dL_dconic / dL_ddepth intermediates are internal here.)
+ * The camera arguments -- `scale_modifier`, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy -- are IGNORED: the backward
+ * reads the values the forward left in the geometry buffer's camera block, so a backward always differentiates the forward
+ * it follows (scale_modifier: tests/test_gpu_config_matrix.py).  As in the reference (backward.cu:295,323-325), dL_dscale
+ * is the gradient with respect to scale_modifier * scale, WITHOUT the chain factor scale_modifier; dL_drot has no such gap. */
 int sgr_backward(int P, int D, int M, int R, int S, const float* background, int width, int height,
                  const float* means3D, const float* shs, const float* colors_precomp, const float* semantics,
                  const float* alphas, const float* scales, float scale_modifier, const float* rotations,

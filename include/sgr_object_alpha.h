@@ -66,6 +66,8 @@ int sgr_layer_alpha_forward(int P, int R, int width, int height, int split, cons
  * rotations (or cov3D_precomp).  layer_alpha / layer_last: the forward's two images.  means3D, scales, rotations,
  * cov3D_precomp, radii (may be NULL: the forward's own) as given to sgr_forward.  Outputs of full length P, every element
  * written: dL_dmean3D [P,3], dL_dopacity [P], dL_dscale [P,3], dL_drot [P,4], dL_dcov3D [P,6] (NULL: not wanted).
+ * `scale_modifier` is IGNORED: the backward reads the value the forward left in the geometry buffer's camera block, and
+ * dL_dscale lacks the chain factor scale_modifier exactly as sgr_backward's does (include/sgr.h).
  * `scratch` is called once.  The binning buffer is written (the "touched" bytes, left cleared).  -SGR_E_INVALID, before any
  * HIP call and before the allocation callback, for the argument errors of the forward or a NULL input / output. */
 int sgr_layer_alpha_backward(int P, int R, int width, int height, int split, const float* means3D, const float* scales,

@@ -9,7 +9,9 @@ Two call sites, both executed FROM THE REFERENCE'S SOURCE in this container (no 
     files and run on a stub ``pc`` / camera / cfg, with ``diff_gaussian_rasterization`` replaced by a RECORDING
     rasterizer that stores the settings tuple and the keyword arguments of every call and returns outputs of the right
     shapes.  Variants: train mode with normals + semantics (the rasterizer's ``semantics`` input is their ``cat``),
-    eval mode (``means2D=None``), and the python SH / covariance path (``colors_precomp`` + ``cov3D_precomp``).
+    eval mode (``means2D=None``), the python SH / covariance path (``colors_precomp`` + ``cov3D_precomp``), each of the two
+    alone (``colors_precomp`` + ``scales`` / ``rotations``; ``shs`` + ``cov3D_precomp = get_covariance(0.6)`` with
+    ``scale_modifier = 0.6``) and ``override_color`` with ``scaling_modifier = 1.5``.
   * ``script/test_gaussian_rasterization.py`` (the reference's only test, BASELINE.json configs[0]): its ``__main__`` body
     with ``torch.manual_seed(0)`` in front; both calls (S = 0 and S = 15) are captured.
 
@@ -128,7 +130,10 @@ def make_camera(W, H, fx):
                                  world_view_transform=c.viewmatrix, full_proj_transform=c.projmatrix, camera_center=c.campos)
 
 
-def capture_render_kernel(mode, render_normal, use_semantic, convert_SHs_python, compute_cov3D_python, white_bg, seed):
+def capture_render_kernel(mode, render_normal, use_semantic, convert_SHs_python, compute_cov3D_python, white_bg, seed,
+                          scaling_modifier=None, override_color=False, P=3000):
+    """`scaling_modifier`: render_kernel's argument of that name (None: cfg.render.scaling_modifier = 1.0 is used);
+    `override_color`: render_kernel gets a seeded [P, 3] colour tensor as its override_color."""
     rec = Recorder()
     cfg = AttrDict(mode=mode, render=AttrDict(scaling_modifier=1.0, convert_SHs_python=convert_SHs_python,
                                              compute_cov3D_python=compute_cov3D_python, debug=False, render_normal=render_normal),
@@ -142,9 +147,14 @@ def capture_render_kernel(mode, render_normal, use_semantic, convert_SHs_python,
     exec(_func(os.path.join(REF, "lib/utils/camera_utils.py"), "make_rasterizer"), ns)
     exec(_func(os.path.join(REF, "lib/models/street_gaussian_renderer.py"), "render_kernel", method=True), ns)
     renderer = types.SimpleNamespace(cfg=cfg.render)
-    pc = make_pc(3000, 16, 16, seed)
+    pc = make_pc(P, 16, 16, seed)
     cam = make_camera(320, 208, 340.0)
-    out = ns["render_kernel"](renderer, cam, pc)
+    extra = {}
+    if scaling_modifier is not None:
+        extra["scaling_modifier"] = scaling_modifier
+    if override_color:
+        extra["override_color"] = torch.rand(P, 3, generator=torch.Generator().manual_seed(1000 + seed))
+    out = ns["render_kernel"](renderer, cam, pc, **extra)
     assert len(rec.calls) == 1 and "rgb" in out
     return rec.calls[0]
 
@@ -208,6 +218,14 @@ VARIANTS = {
                                      compute_cov3D_python=False, white_bg=True, seed=2),
     "render_kernel_train_python_sh_cov": dict(mode="train", render_normal=False, use_semantic=True, convert_SHs_python=True,
                                               compute_cov3D_python=True, white_bg=False, seed=3),
+    # the mixed input kinds and scaling modifiers other than 1 (P kept small: every file stays well under 1 MB)
+    "render_kernel_train_python_sh": dict(mode="train", render_normal=False, use_semantic=True, convert_SHs_python=True,
+                                          compute_cov3D_python=False, white_bg=False, seed=4, P=1500),
+    "render_kernel_train_python_cov_mod06": dict(mode="train", render_normal=False, use_semantic=True, convert_SHs_python=False,
+                                                 compute_cov3D_python=True, white_bg=False, seed=5, scaling_modifier=0.6, P=1500),
+    "render_kernel_train_override_color_mod15": dict(mode="train", render_normal=True, use_semantic=False,
+                                                     convert_SHs_python=False, compute_cov3D_python=False, white_bg=True, seed=6,
+                                                     scaling_modifier=1.5, override_color=True, P=1500),
 }
 
 

@@ -5,7 +5,7 @@ script/test_gaussian_rasterization.py pass to GaussianRasterizer -- captured by 
 rasterizer (tests/golden/make_callsite_fixture.py).  Here: (a) where /root/reference exists the capture is repeated and
 must reproduce the committed fixtures bit for bit, (b) the conventions the package relies on are asserted on the fixtures,
 (c) the oracle accepts the captured argument sets as they are (BASELINE.json configs[0]: the smoke-test recipe on the CPU
-path); tests/test_gpu_callsite.py replays them through the HIP path."""
+path; the mixed input kinds and the scaling modifiers 0.6 / 1.5 of render_kernel); tests/test_gpu_callsite.py replays them through the HIP path."""
 import glob
 import os
 
@@ -21,7 +21,7 @@ FIX = sorted(glob.glob(os.path.join(HERE, "golden", "callsite", "*.npz")))
 
 
 def test_fixtures_are_committed():
-    assert len(FIX) == 5
+    assert len(FIX) == 8
 
 
 @pytest.mark.skipif(not os.path.exists("/root/reference/lib/models/street_gaussian_renderer.py"),
@@ -68,13 +68,26 @@ def test_argument_conventions_of_the_reference_call_sites():
         if name == "render_kernel_train_python_sh_cov":
             assert kw["colors_precomp"].shape == (P, 3) and (kw["colors_precomp"] >= 0).all()  # clamp_min(sh2rgb + 0.5, 0)
             assert kw["cov3D_precomp"].shape == (P, 6)
+        if name == "render_kernel_train_python_sh":
+            # convert_SHs_python alone: colours from eval_sh, the covariance left to the rasterizer
+            assert kw["colors_precomp"].shape == (P, 3) and (kw["colors_precomp"] >= 0).all()
+            assert kw["scales"].shape == (P, 3) and kw["rotations"].shape == (P, 4) and st["scale_modifier"] == 1.0
+        if name == "render_kernel_train_python_cov_mod06":
+            # compute_cov3D_python alone: SH rows go down, cov3D_precomp = get_covariance(scaling_modifier) already holds
+            # the modifier -- and the SAME modifier is in the settings, where the rasterizer must ignore it
+            assert kw["shs"].shape == (P, 16, 3) and kw["cov3D_precomp"].shape == (P, 6) and st["scale_modifier"] == 0.6
+        if name == "render_kernel_train_override_color_mod15":
+            # override_color wins over SH; scales / rotations with scaling_modifier = 1.5 in the settings; normals only
+            assert kw["colors_precomp"].shape == (P, 3) and kw["shs"] is None and kw["scales"].shape == (P, 3)
+            assert st["scale_modifier"] == 1.5 and kw["semantics"].shape == (P, 3) and bool((st["bg"] == 1).all())
         if name.startswith("smoke_script"):
             # degree 0 with FOUR coefficients per Gaussian (M > (D+1)^2), un-normalised quaternions, debug=True
             assert st["sh_degree"] == 0 and kw["shs"].shape == (P, 4, 3) and st["debug"] is True and P == 10000
             assert (kw["rotations"][:, 0] == 1).all()
 
 
-@pytest.mark.parametrize("name", ["smoke_script_call2_sem15", "render_kernel_train_python_sh_cov"])
+@pytest.mark.parametrize("name", ["smoke_script_call2_sem15", "render_kernel_train_python_sh_cov", "render_kernel_train_python_sh",
+                                  "render_kernel_train_python_cov_mod06", "render_kernel_train_override_color_mod15"])
 def test_oracle_runs_the_captured_call(name):
     st, kw, meta = mk.load(os.path.join(HERE, "golden", "callsite", name + ".npz"))
     fw = oracle.forward(means3D=kw["means3D"], opacities=kw["opacities"], viewmatrix=st["viewmatrix"],

@@ -7,10 +7,14 @@ differentiable quantity is recomputed here.  Quirks of the reference that autogr
 reproduce are mimicked explicitly (each one cites the reference line):
   * alpha = min(0.99, o*G) has NO gradient mask (backward.cu:543,618,638)  -> straight-through;
   * the tan-fov clamp of t.x/t.z zeroes only dL/dt.x (backward.cu:175-176,262-264) -> detach;
-  * dL/dscale omits the scale_modifier chain factor (backward.cu:321-325) -> only mod == 1 is tested.
+  * dL/dscale is formed from s = mod * scale WITHOUT the chain factor mod (backward.cu:295,323-325; dL/drot is right)
+    -> not mimicked: autograd's scales.grad here is the true gradient, mod times the reference's.  The callers divide it
+    by mod: test_oracle.py::test_oracle_matches_float64_autograd holds the C oracle to scales.grad / mod at modifiers 0.6
+    and 1.5 (and states that the undivided comparison fails), tests/test_gpu_config_matrix.py holds the HIP path to it.
 """
 import math
 
+import numpy as np
 import torch
 
 SH_C0 = 0.28209479177387814
@@ -98,6 +102,67 @@ def preprocess(means3D, viewmatrix, projmatrix, campos, tanfovx, tanfovy, W, H, 
         rgb, clamped = colors_precomp, None
     return dict(depth=t[:, 2], pix=pix, conic=conic, radius=radius, rgb=rgb, clamped=clamped, cov3D=Sigma,
                 cov2=torch.stack([a, b, c], -1), opacity=opacities[:, 0])
+
+
+def render_batched(pre, point_list, ranges, W, H, bg, semantics=None):
+    """render() with every tile advanced together: step k blends entry k of EVERY tile's list over a [tiles, 256] block of
+    pixels, so the Python loop runs over the longest list instead of over all instances (a 160 x 104 frame of 1000
+    Gaussians: a fraction of a second instead of several).  Per pixel the same expressions in the same order as render();
+    test_oracle.py::test_render_batched_is_render holds the two together, values and gradients."""
+    S = 0 if semantics is None else semantics.shape[1]
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    T = gx * gy
+    f8 = dict(dtype=torch.float64)
+    rg = torch.from_numpy(np.asarray(ranges).astype(np.int64)).reshape(T, 2)
+    cnt = rg[:, 1] - rg[:, 0]
+    tiles = torch.arange(T)
+    lane = torch.arange(256)
+    py = ((tiles // gx) * 16)[:, None] + (lane // 16)[None]
+    px = ((tiles % gx) * 16)[:, None] + (lane % 16)[None]
+    inside = (py < H) & (px < W)
+    pxf, pyf = px.double(), py.double()
+    Tt = torch.ones(T, 256, **f8)
+    Cc = torch.zeros(T, 256, 3, **f8)
+    Dd = torch.zeros(T, 256, **f8)
+    Aa = torch.zeros(T, 256, **f8)
+    Ss = torch.zeros(T, 256, S, **f8)
+    done = torch.zeros(T, 256, dtype=torch.bool)
+    last = torch.zeros(T, 256, dtype=torch.int64)
+    R = point_list.shape[0]
+    for k in range(int(cnt.max()) if T and R else 0):
+        live = k < cnt  # a tile whose list is shorter blends nothing more (its index is a placeholder)
+        gi = torch.where(live, point_list[(rg[:, 0] + k).clamp(max=R - 1)], torch.zeros_like(cnt))
+        dx = pre["pix"][gi, 0][:, None] - pxf
+        dy = pre["pix"][gi, 1][:, None] - pyf
+        cn = pre["conic"][gi]
+        power = -0.5 * (cn[:, 0:1] * dx * dx + cn[:, 2:3] * dy * dy) - cn[:, 1:2] * dx * dy
+        og = pre["opacity"][gi][:, None] * torch.exp(power)
+        alpha = og + (og.clamp(max=0.99) - og).detach()
+        valid = (~done) & (power <= 0) & (alpha >= 1.0 / 255.0) & live[:, None]
+        testT = Tt * (1 - alpha)
+        newdone = valid & (testT < 1e-4)
+        contrib = valid & ~newdone
+        w = torch.where(contrib, alpha * Tt, torch.zeros_like(Tt))
+        Cc = Cc + w[:, :, None] * pre["rgb"][gi][:, None, :]
+        Dd = Dd + w * pre["depth"][gi][:, None]
+        Aa = Aa + w
+        if S:
+            Ss = Ss + w[:, :, None] * semantics[gi][:, None, :]
+        Tt = torch.where(contrib, testT, Tt)
+        last = torch.where(contrib, torch.full_like(last, k + 1), last)
+        done = done | newdone
+    Cc = Cc + Tt[:, :, None] * bg.double()[None, None]
+    yy, xx = py[inside], px[inside]
+    color, depth, alpha_o = torch.zeros(3, H, W, **f8), torch.zeros(1, H, W, **f8), torch.zeros(1, H, W, **f8)
+    sem = torch.zeros(S, H, W, **f8)
+    n_contrib = torch.zeros(H, W, dtype=torch.int64)
+    color[:, yy, xx] = Cc[inside].t()
+    depth[0, yy, xx] = Dd[inside]
+    alpha_o[0, yy, xx] = Aa[inside]
+    if S:
+        sem[:, yy, xx] = Ss[inside].t()
+    n_contrib[yy, xx] = last[inside]
+    return color, depth, alpha_o, sem, n_contrib
 
 
 def render(pre, point_list, ranges, W, H, bg, semantics=None):
