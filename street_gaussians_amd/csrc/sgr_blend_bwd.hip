@@ -318,6 +318,11 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     sgr_f2 acc01 = {0.f, 0.f}, acc2D = {0.f, 0.f}, last01 = {0.f, 0.f}, last2D = {0.f, 0.f};
     const sgr_f2 dL01 = {dLdC0, dLdC1}, dL2D = {dLdC2, dLdD};
     float accA = 0.f, last_alpha = 0.f;
+    // 1 - last_alpha is the `oma` of the visit that set last_alpha: carried in a register of its own it saves the subtraction
+    // on every visit.  Only where the register is free -- the parity-mode S = 0 kernel; the default-mode S = 0 kernels and the
+    // channel-carrying ones pay for it with scratch or an occupancy step (tools/occupancy_audit.py) and subtract as before.
+    constexpr bool CARRY_OMA = EXACT && SGR_EXACT_BWD_FAST && SMAX == 0;
+    float last_oma = 1.f;
     constexpr int NREC = SGR_FACTORED ? 1 : NS;
     float accS[NREC], lastS[NREC];
 #pragma unroll
@@ -533,7 +538,7 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                     // and two residual corrections (sgr_div_by: the bits of `/` for these operand ranges)
                     T = (EXACT && !SGR_EXACT_BWD_FAST) ? (SGR_EXACT_TRIM ? sgr_div_by(T, oma, inv1ma) : T / oma) : T * inv1ma;
                     wm = alpha * T;
-                    const float one_m_la = 1.0f - last_alpha;
+                    const float one_m_la = CARRY_OMA ? last_oma : 1.0f - last_alpha;
                     float d;
                     if (SGR_FACTORED) {
                         Arec = fmaf(last_alpha, u_last, one_m_la * Arec);  // before u: u can then be formed in u_last's register
@@ -582,12 +587,17 @@ sgr_blend_bwd_body(const uint2* __restrict__ ranges, const uint32_t* __restrict_
                     last2D = c2D;
                     }
                     last_alpha = alpha;
+                    if (CARRY_OMA) last_oma = oma;
                     d *= T;
                     // backward.cu:611-614.  EXACT with a black background (bg_zero, wave-uniform): (-T_final / oma) * 0 adds a
-                    // signed zero -- the second quotient is skipped
-                    if (EXACT && SGR_EXACT_BWD_FAST)
-                        Gd = bg_zero ? G * d : G * (d + (-T_final * inv1ma) * bgdot);
-                    else if (EXACT)
+                    // signed zero -- the second quotient is skipped.  Skipped by a BRANCH: written as `bg_zero ? G * d : ...`
+                    // hipcc formed both arms on every visit (two multiplies, a subtraction and a select on the mask);
+                    // sgr_keep_branch is what keeps the optimiser from turning the branch back into that select
+                    if (EXACT && SGR_EXACT_BWD_FAST) {
+                        float dbg = d;
+                        if (!bg_zero) dbg = sgr_keep_branch(d + (-T_final * inv1ma) * bgdot);
+                        Gd = G * dbg;
+                    } else if (EXACT)
                         Gd = (SGR_EXACT_TRIM && bg_zero) ? G * d
                                                          : G * (d + (SGR_EXACT_TRIM ? sgr_div_by(-T_final, oma, inv1ma) : -T_final / oma) * bgdot);
                     else

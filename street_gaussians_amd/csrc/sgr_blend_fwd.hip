@@ -153,18 +153,17 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
                 // This kernel's sums on top of one blend step of list slot v.j.  The walk's bookkeeping is scalar (SALU issues
                 // once per four cycles per SIMD, and this kernel issues about as many scalar as vector instructions): bits are
                 // taken with s_ff1 + s_bitset0, the hit record is one s_bitset1.
-                sgr_walk_pairs<EXACT, false>(m, chunk, sA, sB, tp.pxf, tp.pyf, [&](const SgrVisit& v) __attribute__((always_inline)) {
-                    SgrBlendStep<SGR_FWD_SEL != 0> b;
+                sgr_walk_pairs<EXACT, false, EXACT && SMAX == 0>(m, chunk, sA, sB, tp.pxf, tp.pyf, [&](const SgrVisit& v) __attribute__((always_inline)) {
+                    SgrBlendStep<SGR_FWD_SEL != 0, EXACT> b;  // parity mode: the step hands out ae and forms w from it
                     if (!sgr_blend_begin(b, T, thr, v.power, v.alpha)) return;
                     const int j = v.j;
-                    const float alpha = v.alpha, w = b.w;
-                    const float4 c = sC[j];
+                    const float w = b.w, ae = EXACT ? b.ae : 0.0f;  // ae = blends ? alpha : 0: the factor of the unfused sums
+                    const float4 c = sgr_slot(sC, v.ja);
                     if (EXACT) {
                         // the reference's association, unfused: C[ch] += features[ch] * alpha * T (forward.cu:438-441) -- for the
                         // DEPTH (and semantic) sums, whose images the parity mode reproduces bit for bit.  The colour sums take the
                         // fused form (SGR_EXACT_COLOR_FUSED): their inputs already differ from the reference's in the last bit
                         // (the SH evaluation), the image is held to rel 1e-4, and no gradient depends on it
-                        const float ae = b.sel(alpha, 0.0f);
                         if (SGR_EXACT_COLOR_FUSED) {
                             C0 = fmaf(c.x, w, C0);
                             C1 = fmaf(c.y, w, C1);
@@ -184,7 +183,6 @@ sgr_blend_fwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restric
                     Wt += w;
                     if (SMAX > 0) {
                         const float4* sj = reinterpret_cast<const float4*>(&sSem[j * SMAX]);
-                        const float ae = b.sel(alpha, 0.0f);
 #pragma unroll
                         for (int c4 = 0; c4 < SMAX / 4; c4++) {
                             const float4 sv = sj[c4];

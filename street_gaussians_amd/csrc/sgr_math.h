@@ -369,6 +369,15 @@ SGR_HD float sgr_power2(float qa, float qb, float qc, float dx, float dy) {
     return fmaf(qc * dy, dy, u * dx);
 }
 
+// The weight of a forward blend step, "this lane blends ? alpha * T : 0", from ae = "blends ? alpha : 0" -- the factor the
+// unfused parity-mode sums need anyway, so that one select per visit serves both.  Same bits as selecting the product: on a
+// blending lane it is the product; elsewhere it is 0 * T = +0, T being a transmittance (finite, positive; never updated
+// below 1e-4).  tests/test_blend_step_host_cpu.py holds the identity.
+SGR_HD float sgr_blend_weight(float ae, float T) {
+#pragma clang fp contract(off)
+    return ae * T;
+}
+
 // "Exact" (parity) mode of the blend kernels: the reference's own expression, operation by operation and without
 // contraction (forward.cu:420, backward.cu:536), followed by the library's accurate expf -- the arithmetic of oracle/_ref's
 // strict build and of the C oracle, so that alpha_out (and with it T_final = 1 - alpha_out, the amplifier of every

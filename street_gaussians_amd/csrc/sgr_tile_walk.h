@@ -41,6 +41,24 @@ __device__ __forceinline__ float sgr_sel_mask(uint64_t m, float a, float b) {
     return r;
 }
 
+// x, through an empty volatile asm: a statement the optimiser may not execute speculatively.  An `if` on a wave-uniform
+// condition whose only statement assigns sgr_keep_branch(...) stays a scalar branch around that arithmetic; without it
+// hipcc computes both arms on every lane and selects (v_cndmask), which costs a loop the skipped arm on every trip.
+__device__ __forceinline__ float sgr_keep_branch(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// min(0.99, x), the alpha cap, for an x that a multiplication produced.  fminf() has to quiet a signalling NaN first, and
+// where hipcc cannot see the producer of x (another basic block: the second visit of a pair) it issues v_max_f32 x, x
+// for that in front of the v_min_f32.  A product is never a signalling NaN, so the bare v_min_f32 returns fminf's bits:
+// the smaller operand, and 0.99 for a (quiet) NaN.
+__device__ __forceinline__ float sgr_alpha_cap(float x) {
+    float r;
+    asm("v_min_f32 %0, 0x3f7d70a4, %1" : "=v"(r) : "v"(x));  // 0.99f
+    return r;
+}
+
 // __syncthreads() preceded by an explicit LDS drain.  hipcc (ROCm 7.2, gfx950) emits the post-walk barrier of the blend
 // backward as a bare s_barrier at a branch target: the last trip's ds_add_f32 / ds_write_b32 of a wave may still be in
 // flight when the other waves are released and flush the rows (seen on MI355X as a rare wrong row with 64-entry
@@ -110,45 +128,71 @@ __device__ __forceinline__ float sgr_G_bwd(const float power, const float opacit
     }
 }
 
+// alpha = min(0.99, opacity * G).  BARE: through sgr_alpha_cap (same bits) -- for the second visit of a pair in the parity
+// mode's backward family, whose guard (sgr_G_bwd) splits the pair's blocks: hipcc keeps the product in the first block and
+// sinks the fminf to the second visit, where it paid the canonicalisation.  Everywhere else the product and its fminf share a
+// block, hipcc issues none, and the plain form stays (an asm statement there only costs the s_nop hipcc puts behind it).
+template <bool BARE>
+__device__ __forceinline__ float sgr_alpha_of(const float opacity, const float G) {
+    return BARE ? sgr_alpha_cap(opacity * G) : fminf(0.99f, opacity * G);
+}
+
 // One (quadrant, entry) visit as the walk hands it to a kernel's step: LDS slot j = chunk * 64 + bit of the batch, the
 // staged record q, the pixel's offsets, power, G and alpha = min(0.99, opacity * G).  Wave-uniform: j, bit, q.
 struct SgrVisit {
     int j, bit;
+    uint32_t ja;  // byte offset of slot j in the staged float4 arrays (sgr_slot_addr): sgr_slot(sC, v.ja) = sC[v.j]
     float4 q;
     float dx, dy, power, G, alpha;
 };
 
+// The byte offset of slot j in a staged float4 array, and the slot at such an offset.  j is wave-uniform, so the address
+// register of the LDS reads is a v_mov from a scalar; hipcc lets the 128-bit read of the record land on it and
+// rematerialises it for the step's own read (sC).  KEEP: the move is an asm statement, which cannot be rematerialised --
+// one register held from the walk's reads to the step's, one v_mov less per visit that blends.  Where that register has
+// to be spilled instead (tools/occupancy_audit.py), leave KEEP off.
+template <bool KEEP>
+__device__ __forceinline__ uint32_t sgr_slot_addr(const int j) {
+    uint32_t a = (uint32_t)j * 16u;
+    if constexpr (KEEP) asm("v_mov_b32 %0, %1" : "=v"(a) : "s"(a));
+    return a;
+}
+__device__ __forceinline__ float4 sgr_slot(const float4* s, const uint32_t ja) {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s) + ja);
+}
 // Walks the set bits of m -- the survivors of chunk `chunk`, lowest (= first in walk order) first -- and calls step(visit)
 // for each.  Scalar bookkeeping kept short (SALU issues once per four cycles per SIMD): s_ff1 + s_bitset0 per survivor, and
 // the odd survivor is taken first so that the loop is pairs only.  A step may clear m to end the walk (the wave finished).
-// BWD: G from sgr_G_bwd (the backward family) instead of sgr_exp_fwd.
-template <bool EXACT, bool BWD, class Step>
+// BWD: G from sgr_G_bwd (the backward family) instead of sgr_exp_fwd.  KEEP: see sgr_slot_addr.
+template <bool EXACT, bool BWD, bool KEEP = false, class Step>
 __device__ __forceinline__ void sgr_walk_pairs(uint64_t& m, const int chunk, const float4* sA, const float4* sB, const float pxf,
                                                const float pyf, Step step) {
     if (__builtin_popcountll(m) & 1) {
         const int b0 = sgr_pop_lowest(m);
         const int j0 = chunk * 64 + b0;
-        const float4 a0 = sA[j0], q0 = sB[j0];
+        const uint32_t ja0 = sgr_slot_addr<KEEP>(j0);
+        const float4 a0 = sgr_slot(sA, ja0), q0 = sgr_slot(sB, ja0);
         const float dx0 = a0.x - pxf, dy0 = a0.y - pyf;
         const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, dx0, dy0) : sgr_power2(q0.x, q0.y, q0.z, dx0, dy0);
         const float G0 = BWD ? sgr_G_bwd<EXACT>(pw0, q0.w) : sgr_exp_fwd<EXACT>(pw0);
-        step(SgrVisit{j0, b0, q0, dx0, dy0, pw0, G0, fminf(0.99f, q0.w * G0)});
+        step(SgrVisit{j0, b0, ja0, q0, dx0, dy0, pw0, G0, sgr_alpha_of<false>(q0.w, G0)});
     }
     while (m) {
         // two survivors per trip: their LDS reads and exp() are independent of each other, only the steps are ordered
         const int b0 = sgr_pop_lowest(m);
         const int b1 = sgr_pop_lowest(m);
         const int j0 = chunk * 64 + b0, j1 = chunk * 64 + b1;
-        const float4 a0 = sA[j0], q0 = sB[j0];
-        const float4 a1 = sA[j1], q1 = sB[j1];
+        const uint32_t ja0 = sgr_slot_addr<KEEP>(j0), ja1 = sgr_slot_addr<KEEP>(j1);
+        const float4 a0 = sgr_slot(sA, ja0), q0 = sgr_slot(sB, ja0);
+        const float4 a1 = sgr_slot(sA, ja1), q1 = sgr_slot(sB, ja1);
         const float dx0 = a0.x - pxf, dy0 = a0.y - pyf, dx1 = a1.x - pxf, dy1 = a1.y - pyf;
         const float pw0 = EXACT ? sgr_power_ref_staged(q0.x, q0.y, q0.z, dx0, dy0) : sgr_power2(q0.x, q0.y, q0.z, dx0, dy0);
         const float pw1 = EXACT ? sgr_power_ref_staged(q1.x, q1.y, q1.z, dx1, dy1) : sgr_power2(q1.x, q1.y, q1.z, dx1, dy1);
         const float G0 = BWD ? sgr_G_bwd<EXACT>(pw0, q0.w) : sgr_exp_fwd<EXACT>(pw0);
         const float G1 = BWD ? sgr_G_bwd<EXACT>(pw1, q1.w) : sgr_exp_fwd<EXACT>(pw1);
-        const float al0 = fminf(0.99f, q0.w * G0), al1 = fminf(0.99f, q1.w * G1);
-        step(SgrVisit{j0, b0, q0, dx0, dy0, pw0, G0, al0});
-        step(SgrVisit{j1, b1, q1, dx1, dy1, pw1, G1, al1});  // forward: if the wave finished on j0 every threshold is +inf, a no-op
+        const float al0 = sgr_alpha_of<false>(q0.w, G0), al1 = sgr_alpha_of<EXACT && BWD>(q1.w, G1);
+        step(SgrVisit{j0, b0, ja0, q0, dx0, dy0, pw0, G0, al0});
+        step(SgrVisit{j1, b1, ja1, q1, dx1, dy1, pw1, G1, al1});  // forward: if the wave finished on j0 every threshold is +inf, a no-op
     }
 }
 
@@ -179,16 +223,20 @@ struct SgrBlendSel {
 //     sgr_blend_end(b, T, thr, done_mask, m);                      // T, finished pixels; clears m when the wave is finished
 // (Some lane passing is a superset of some lane blending: if every passing lane finishes on this very entry nothing is
 // blended.)
-template <bool MASK>
+// AE: the kernel also sums on ae = "blends ? alpha : 0" (the parity mode's unfused depth and channel sums).  The step then
+// selects ae and forms w = ae * T -- one select for both, the bits of the selected product (sgr_blend_weight, sgr_math.h).
+// A kernel that sums on w alone keeps the selected product: the same instruction count, and the code it had.
+template <bool MASK, bool AE = false>
 struct SgrBlendStep {
     SgrBlendSel<MASK> sel;  // this lane blends ? a : b
+    float ae;               // AE: blends ? alpha : 0
     float w;                // blends ? alpha * T : 0
     float test_T;
     uint64_t sm;            // the lanes that finish on this entry
     bool fin;               // ... this lane among them
 };
-template <bool MASK>
-__device__ __forceinline__ bool sgr_blend_begin(SgrBlendStep<MASK>& b, const float T, const float thr, const float power, const float alpha) {
+template <bool MASK, bool AE>
+__device__ __forceinline__ bool sgr_blend_begin(SgrBlendStep<MASK, AE>& b, const float T, const float thr, const float power, const float alpha) {
     // skip if power > 0 or alpha < 1/255 (or the pixel is finished: thr = inf)
     const bool k1 = !(power > 0.0f), k2 = !(alpha < thr);
     const uint64_t hm = __builtin_amdgcn_ballot_w64(k1) & __builtin_amdgcn_ballot_w64(k2);
@@ -197,13 +245,18 @@ __device__ __forceinline__ bool sgr_blend_begin(SgrBlendStep<MASK>& b, const flo
     const bool k3 = b.test_T < 0.0001f;  // forward.cu:431-436
     const uint64_t k3m = __builtin_amdgcn_ballot_w64(k3);
     b.sel = SgrBlendSel<MASK>{hm & ~k3m, k1 && k2 && !k3};
-    b.w = b.sel(alpha * T, 0.0f);
+    if constexpr (AE) {
+        b.ae = b.sel(alpha, 0.0f);
+        b.w = sgr_blend_weight(b.ae, T);
+    } else {
+        b.w = b.sel(alpha * T, 0.0f);
+    }
     b.sm = hm & k3m;
     b.fin = k1 && k2 && k3;
     return true;
 }
-template <bool MASK>
-__device__ __forceinline__ void sgr_blend_end(const SgrBlendStep<MASK>& b, float& T, float& thr, uint64_t& done_mask, uint64_t& m) {
+template <bool MASK, bool AE>
+__device__ __forceinline__ void sgr_blend_end(const SgrBlendStep<MASK, AE>& b, float& T, float& thr, uint64_t& done_mask, uint64_t& m) {
     T = b.sel(b.test_T, T);
     if (b.sm != 0) {
         thr = b.fin ? __builtin_inff() : thr;
